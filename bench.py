@@ -6,6 +6,11 @@ one rank per GPU.  A "step" is one pass of the whole hot path (assembly -> conti
 over one batch of synthetic regions whose packed reads already sit in HBM.  Workload = BASELINE.json configs[1]:
 256 synthetic 50 kb regions, 30x HiFi-like 15 kb reads, per GPU (weak scaling: every rank gets its own 256 regions).
 Rank 0 prints ONE JSON line.
+
+A plain run only sets up, warms up, times the K steps and prints the headline line (regions/s, ms_per_step).  --full adds
+what takes work or runs of its own: planted-truth scoring of the timed and hold-out regions, the per-kernel table and
+roofline (one-lane passes after the timed region), the H2D figure, the CPU baseline and the GPU-vs-CPU call comparison.
+--dump-outputs DIR writes what the last timed step handed its caller (VCF calls, contigs) as float64 / float32 .npy files.
 """
 import argparse
 import json
@@ -103,6 +108,54 @@ def sum_stats(dicts):
         else:
             out[k] = v
     return out
+
+
+SVTYPE_CODE = {"DEL": 1, "INS": 2, "DUP": 3, "INV": 4, "BND": 5, "TRA": 5}
+DUMP_BASES = 8 << 20      # contig bases kept in contig_bases.npy (float32: 32 MB)
+DUMP_SAMPLE_REGIONS = 32  # regions whose contigs' bases are dumped when there are more
+
+
+def call_rows(lines):
+    """VCF body lines -> float64 rows (chromosome number, POS, SVLEN, SVTYPE code, GT code, len(REF), len(ALT), crc32 of REF + ALT,
+    crc32 of the whole line); GT code = 10 * allele 1 + allele 2 (+ 100 when phased, 9 for '.')"""
+    import zlib
+    import numpy as np
+    rows = []
+    for l in lines:
+        d = l.rstrip('\n').split('\t')
+        num = d[0][3:] if d[0].startswith('chr') else d[0]
+        info = dict(kv.split('=', 1) for kv in d[7].split(';') if '=' in kv)
+        gt = d[9].split(':')[0]
+        al = [int(a) if a.isdigit() else 9 for a in gt.replace('|', '/').split('/')] + [9]
+        rows.append([int(num) if num.isdigit() else {"X": 23, "Y": 24, "M": 25}.get(num, 0), int(d[1]), int(info.get("SVLEN", 0)),
+                     SVTYPE_CODE.get(info.get("SVTYPE"), 0), 10 * al[0] + al[1] + (100 if '|' in gt else 0), len(d[3]), len(d[4]),
+                     zlib.crc32((d[3] + '\t' + d[4]).encode()), zlib.crc32(l.rstrip('\n').encode())])
+    return np.array(rows, dtype=np.float64).reshape(-1, 9)
+
+
+def dump_outputs(out_dir, lines, res=None):
+    """--dump-outputs: what the last timed step handed its caller, as .npy files under out_dir.  vcf_calls = the final VCF body
+    (call_rows); with the step's CallResult also vcf_raw_calls (before the read-support filter and redundancy removal),
+    contigs (region, haplotype, length, status, crc32 per contig), set_status, and contig_bases: the bases (ASCII codes) of every
+    contig of a fixed, seeded sample of DUMP_SAMPLE_REGIONS regions (all regions when there are no more), in contig order,
+    at most DUMP_BASES of them"""
+    import zlib
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"vcf_calls": call_rows(lines)}
+    if res is not None:
+        arrays["vcf_raw_calls"] = call_rows(res.raw_lines)
+        seqs = [res.contig_batch[i] for i in range(len(res.contig_region))]
+        arrays["contigs"] = np.array([[ri, hp, len(s), st, zlib.crc32(s)] for ri, hp, s, st in
+                                      zip(res.contig_region, res.contig_hp, seqs, res.contig_status)], dtype=np.float64).reshape(-1, 5)
+        arrays["set_status"] = np.asarray(res.set_status, dtype=np.float64)
+        n_reg = 1 + max(res.contig_region, default=-1)
+        keep = set(range(n_reg)) if n_reg <= DUMP_SAMPLE_REGIONS else \
+            set(np.random.default_rng(0).choice(n_reg, DUMP_SAMPLE_REGIONS, replace=False).tolist())
+        bases = b"".join(s for ri, s in zip(res.contig_region, seqs) if ri in keep)[:DUMP_BASES]
+        arrays["contig_bases"] = np.frombuffer(bases, dtype=np.uint8).astype(np.float32)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def load_bed(which, limit):
@@ -231,6 +284,8 @@ def run_bed(args):
             out["sv_vs_truth"] = {"truth": len(sc_truth), "tp": tp, "fp": fp, "fn": fn, "gt_ok": gt_ok,
                                   "note": "windows of neighbouring BED lines overlap once the margins are added: an SV planted in the shared stretch of one region is "
                                           "not carried by the other region's haplotypes, so fn / fp counts here are an upper bound of the path's own misses"}
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, all_lines)
         print(json.dumps(out))
     fence()
     for c in ctxs:
@@ -243,7 +298,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=24)
-    ap.add_argument("--holdout", type=int, default=256, help="regions of a disjoint seed range (indices 5000...) scored against planted truth, untimed (0 = skip)")
+    ap.add_argument("--holdout", type=int, default=256, help="--full: regions of a disjoint seed range (indices 5000...) scored against planted truth, untimed (0 = skip)")
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--regions", type=int, default=256, help="regions per GPU (BASELINE.json configs[1]: 256)")
     ap.add_argument("--lanes", type=int, default=int(os.environ.get("FSV_BENCH_LANES", "0")),
@@ -251,7 +306,12 @@ def main():
     ap.add_argument("--lane-mode", choices=["split", "steps"], default=os.environ.get("FSV_BENCH_LANE_MODE", "steps"),
                     help="split: every step's batch is halved over the lanes; steps: every lane takes whole steps (one batch in flight per lane)")
     ap.add_argument("--stagger", type=float, default=float(os.environ.get("FSV_BENCH_STAGGER", "0.0")), help="seconds between the lanes' first steps")
-    ap.add_argument("--cpu-sample", type=int, default=8, help="regions the CPU baseline runs (0 = skip)")
+    ap.add_argument("--cpu-sample", type=int, default=8, help="--full: regions the CPU baseline runs (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: planted-truth scoring, per-kernel table and roofline (extra one-lane passes), "
+                         "H2D figure, hold-out regions, CPU baseline and GPU-vs-CPU calls")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (VCF calls, contigs) to DIR/<name>.npy")
     ap.add_argument("--second-round", type=int, choices=(0, 1), default=None,
                     help="fsv_asm_params.second_round: 1 = hifiasm's second consensus pass over the window junctions on the GPU, 0 = the junction-insertion "
                          "vote that stands in for it; default: the library's default")
@@ -297,8 +357,6 @@ def main():
     idx0 = rank * n
     regions = [synth.make_region(idx0 + i, start=(idx0 + i) * 60000, profile=args.profile) for i in range(n)]
     inputs = [pipeline.region_from_synth(r) for r in regions]
-    truth = [(r.chrom, t.svtype, r.start + t.pos, t.length, t.gt) for r in regions for t in r.truth]
-    truth_left = [(r.chrom, t.svtype, r.start + t.pos_left, t.length, t.gt) for r in regions for t in r.truth]
 
     # two lanes per GPU (pipeline.run_hot_path_lanes): halves of the batch on their own context / stream / host thread
     if args.lanes <= 0:
@@ -381,14 +439,33 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     dt = float(t.item())
 
-    # correctness on this rank's regions (the gathered VCF holds every rank's calls; filter to ours)
-    mine = [l for l in lines if idx0 * 60000 <= int(l.split('\t')[1]) < (idx0 + n) * 60000]
-    calls = pipeline.parse_calls(mine)
     ont = args.profile == "ont"      # contigs of 10 %-error reads keep a wrong base every ~2 kb: +-20 bp, +-2 % SVLEN (strict count reported too)
-    tp, fp, fn, gt_ok = pipeline.match_truth(calls, truth, bp_tol=20 if ont else 1, len_tol=0.02, left_shift_ok=2000)
-    tp1, _, _, _ = pipeline.match_truth(calls, truth_left, bp_tol=1, len_tol=0.0 if ont else 0.02, left_shift_ok=0)
-
     if rank == 0:
+        out = {
+            "metric": "target regions/sec (50 kb, 30x HiFi)", "value": round(world * n * args.steps / dt, 3), "unit": "regions/s",
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 2),
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u32", "data": "synthetic",
+            "config": {"workload": (f"{n} synthetic 50 kb regions per GPU, 30x ONT-profile reads U(10k,30k), 10% error, seed 1000+i (BASELINE.json configs[4]); "
+                                    "parity unpinned: the reference runs Flye / Shasta on such reads" if ont else
+                                    f"{n} synthetic 50 kb regions per GPU, 30x HiFi-like reads U(10k,20k), 0.2% error, seed 1000+i (BASELINE.json configs[1])"), "regions_per_gpu": n, "parallelism": f"regions sharded over {world} GPU(s), RCCL VCF gather; {lanes} concurrent lanes (streams) per GPU, " + ("each taking whole steps (one batch in flight per lane, the host half of a batch on its own thread)" if by_steps else "each half of every step's batch")},
+            "lanes": lanes, "lane_mode": args.lane_mode,
+            # whole-batch passes of the hot path this process ran (warm-up + priming + timed, + the one-lane passes of --full): what a
+            # profiler's per-kernel sums over the process have to be divided by
+            "hot_path_passes": (args.warmup + priming if by_steps else args.warmup) + args.steps,
+            "lane_priming_steps": priming,
+        }
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, lines, res)
+
+    if rank == 0 and args.full:
+        # correctness on this rank's regions (the gathered VCF holds every rank's calls; filter to ours)
+        truth = [(r.chrom, t.svtype, r.start + t.pos, t.length, t.gt) for r in regions for t in r.truth]
+        truth_left = [(r.chrom, t.svtype, r.start + t.pos_left, t.length, t.gt) for r in regions for t in r.truth]
+        mine = [l for l in lines if idx0 * 60000 <= int(l.split('\t')[1]) < (idx0 + n) * 60000]
+        calls = pipeline.parse_calls(mine)
+        tp, fp, fn, gt_ok = pipeline.match_truth(calls, truth, bp_tol=20 if ont else 1, len_tol=0.02, left_shift_ok=2000)
+        tp1, _, _, _ = pipeline.match_truth(calls, truth_left, bp_tol=1, len_tol=0.0 if ont else 0.02, left_shift_ok=0)
+
         # library statistics averaged over the timed steps (a single step can catch a clock or host hiccup)
         def avg(dicts):
             out = {}
@@ -490,24 +567,14 @@ def main():
                                 "sq": f"profiles/{sq_name}" if kd.get("sq_wait_any") is not None else None},
                     "note": "bound is what the contract asks to price against; this is an integer join / DP path served from LDS and L2, nowhere near the HBM roof by "
                             "construction (SURVEY.md 7, 8d) -- measured_limiter and valu say what it is bound by"}
-        out = {
-            "metric": "target regions/sec (50 kb, 30x HiFi)", "value": round(world * n * args.steps / dt, 3), "unit": "regions/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 2),
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u32", "data": "synthetic",
-            "config": {"workload": (f"{n} synthetic 50 kb regions per GPU, 30x ONT-profile reads U(10k,30k), 10% error, seed 1000+i (BASELINE.json configs[4]); "
-                                    "parity unpinned: the reference runs Flye / Shasta on such reads" if ont else
-                                    f"{n} synthetic 50 kb regions per GPU, 30x HiFi-like reads U(10k,20k), 0.2% error, seed 1000+i (BASELINE.json configs[1])"), "regions_per_gpu": n, "parallelism": f"regions sharded over {world} GPU(s), RCCL VCF gather; {lanes} concurrent lanes (streams) per GPU, " + ("each taking whole steps (one batch in flight per lane, the host half of a batch on its own thread)" if by_steps else "each half of every step's batch")},
+        out.update({
             "sv_vs_truth": {"truth": len(truth), "tp": tp, "fp": fp, "fn": fn, "gt_ok": gt_ok, "tp_within_1bp_of_left_aligned_truth": tp1},
             "aligner_parity": "unpinned against minimap2 2.24 (absent from the reference tree and this image): chaining / z-drop are this project's own; pinned: "
                               "the DP recurrence (in-tree ksw2 goldens), mm_fix_cigar's gap left-alignment as published, planted truth",
             "stage_ms": {k: round(v, 2) for k, v in a.items() if k.startswith("ms_")},
             "kernels": kernels,
             "align_ms": {k: round(v, 2) for k, v in l.items() if k.startswith("ms_")},
-            "lanes": lanes, "lane_mode": args.lane_mode,
-            # whole-batch passes of the hot path this process ran (warm-up + priming + timed + the two one-lane passes): what a profiler's
-            # per-kernel sums over the process have to be divided by
-            "hot_path_passes": (args.warmup + priming if by_steps else args.warmup) + args.steps + (SOLO_PASSES if kern else 0),
-            "lane_priming_steps": priming,
+            "hot_path_passes": out["hot_path_passes"] + (SOLO_PASSES if kern else 0),
             "host_ms": res.host_ms,
             # companion compute figure: banded DP column-steps of K5 + K6 (windows x their x_len, 31-row bands)
             "dp": {"column_steps_per_step": int(a.get("dp_columns", 0)), "windows_per_step": int(a.get("n_windows", 0)),
@@ -518,7 +585,7 @@ def main():
             "roofline": roof,
             "byte_model_check": {"ok": not over, "kernels_whose_model_exceeds_counter_traffic": over,
                                  "checked": sorted(k2 for k2, v in kernels.items() if v.get("traffic_per_launch"))},
-        }
+        })
         # the boundary takes host buffers: what the H2D copy of the read store adds when it is not overlapped (never part of `value`)
         try:
             words = batches[0].packed.words
@@ -566,6 +633,7 @@ def main():
                                      "gt_ok": gtc, "f1": round(2 * tpc / max(1, 2 * tpc + fpc + fnc), 4),
                                      "identical_vcf_text": [l for l in res.raw_lines if int(l.split('\t')[1]) < lim] == cpu_lines}
             out["cpu_baseline"] = cb
+    if rank == 0:
         print(json.dumps(out))
     fence()
     for b_ in batches:

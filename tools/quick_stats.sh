@@ -5,7 +5,7 @@ tag=${1:-q}
 out=gpurun_out/qstats_$tag
 rm -rf $out && mkdir -p $out
 export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $out/st -- python3 bench.py --lanes 1 --steps 2 --warmup 0 --cpu-sample 0 --holdout 0 ${@:2} > $out/log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $out/st -- python3 bench.py --full --lanes 1 --steps 2 --warmup 0 --cpu-sample 0 --holdout 0 ${@:2} > $out/log 2>&1
 f=$(find $out -name "*kernel_stats.csv" | head -1)
 python3 - "$f" <<'P'
 import csv, re, sys
