@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 from focalsv_amd import _lib
+from tests import kernel_cases as KC
 from tests import oracle_lib as O
 from tests.kernel_cases import tasks_from_cases, usable
 
@@ -136,3 +137,66 @@ def test_k5_wide_bands_vs_oracle(ctx):
             n_wide += c["k"] > 31
             assert int(r["end_site"]) == site, c
     assert n_hit > 2000 and n_wide > 1000
+
+
+# ---- windows at real read geometry (tests/kernel_cases.py: placements) ------------------------------------------
+# any bit offset in x and y, both strands, windows ending at a read's last base, clipped at either end of y, both sides of the
+# geometric rejection rule; 'wide' routes the same placements through k5_bpm_wide_kernel
+
+PROFILES = ["main", "wide"]
+
+
+@pytest.mark.parametrize("profile", PROFILES)
+def test_k5_placements_vs_oracle(ctx, profile):
+    """err and end_site equal the oracle on the plain-string operands; y_beg / extra_begin / extra_end equal the restated
+    determine_overlap_region for every accepted window (hit or not); a rejected window is all -1"""
+    P = KC.suite_list(profile)
+    words, tasks = P.pack()
+    n_hit = KC.check_windows(P, ctx.bpm_windows(words, tasks))
+    C = P.coverage()
+    print("\nK5", profile, len(P.specs), "tasks:", {str(k): v for k, v in sorted(C.items(), key=str)})
+    assert n_hit == C["hits"]
+    if profile == "wide":
+        KC.check_floors(C, ["k>31"], 300, 100)
+
+
+@pytest.mark.parametrize("profile", PROFILES)
+def test_k5_placements_at_the_end_of_the_store(ctx, profile):
+    """32 stores of their own: the last read an x read or a y read, its length every residue modulo 16, and in each at least one
+    hit whose window takes in the last base the store holds (the kernels load whole words past it: the store's slack words)"""
+    for P, last, residue in KC.suite_end_stores(profile):
+        words, tasks = P.pack()
+        KC.check_windows(P, ctx.bpm_windows(words, tasks))
+        assert any(KC.at_store_end(P, i) and P.hit(i)[1] >= 0 for i in range(len(P.specs))), (last, residue)
+
+
+@pytest.mark.parametrize("profile", PROFILES)
+def test_k5_placements_order_and_list_length(ctx, profile):
+    """a window's result depends on the window alone: the same tasks permuted, and every prefix that ends at a wave, block or
+    8-block edge of the launch, give what the full list gave"""
+    P = KC.suite_list(profile)
+    words, tasks = P.pack()
+    full = ctx.bpm_windows(words, tasks)
+    order = list(range(len(tasks)))
+    random.Random(505).shuffle(order)
+    res = ctx.bpm_windows(words, P.pack(order=order)[1])
+    assert not KC.differing_results(res, full[order])
+    for n in KC.PREFIXES:
+        assert n <= len(tasks)
+        assert not KC.differing_results(ctx.bpm_windows(words, tasks[:n]), full[:n]), n
+
+
+@pytest.mark.parametrize("profile", PROFILES)
+def test_k5_placements_ignore_other_reads(ctx, profile):
+    """nothing outside a read is read as a base: a read of other content in front of and behind every read (once all A, once
+    random bases, same lengths) and the store's slack words set to match leave every result as it was.  What this guards is the
+    bounds of the word loads (words outside a read must read as 0 whatever lies there); a wrong validity mask inside a read's own
+    last word shows in the comparison with the oracle above, not here"""
+    P = KC.suite_list(profile)
+    plain = ctx.bpm_windows(*P.pack())
+    res_a = ctx.bpm_windows(*P.pack(filler="A", seed=7))
+    res_r = ctx.bpm_windows(*P.pack(filler="random", seed=7))
+    assert not KC.differing_results(res_a, res_r)
+    assert not KC.differing_results(res_a, plain)
+    for Q, last, residue in KC.suite_end_stores(profile):
+        assert not KC.differing_results(ctx.bpm_windows(*Q.pack(filler="A", seed=residue)), ctx.bpm_windows(*Q.pack(filler="random", seed=residue))), (last, residue)
