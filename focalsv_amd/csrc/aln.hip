@@ -10,7 +10,7 @@
 //   k_gap_shift         every gap of the stitched CIGAR to its leftmost position (minimap2's mm_fix_cigar rule)
 //   k_nw                dual-affine global DP of one event on anti-diagonals (one workgroup per event), the
 //                       recurrence / tie rules / backtrack of the in-tree ksw2 (ksw2_extz2_sse.c:171-196, ksw2.h:115-150)
-#include "asm_kernels.h"
+#include "k_sketch.h"
 #include <algorithm>
 #include <chrono>
 #include <cstdio>
@@ -829,8 +829,6 @@ __global__ __launch_bounds__(256) void k_nw_any(const uint32_t *__restrict__ sto
 }
 
 // ------------------------------------------------------------------------------------------------ host side
-struct DevBuf { void *p = nullptr; size_t cap = 0; };
-
 struct AlnWs {
     DevBuf store, nmask, ascii, asc_off, word_off, len, wper, pair_q, pair_t, sk_ends, sk_low, sk_high, mz, mz_off, mz_cnt, warn, chain, hdr, events, ev_packed, ev_count, tasks, bt, rows, cg, cg_n, scores, gaps, gap_shift, thin, box_src, corner, corner_out;
     fsv_aln_stats stats;
@@ -839,14 +837,12 @@ struct AlnWs {
     hipEvent_t fork = nullptr, join[3] = {nullptr, nullptr, nullptr};
     AlnWs *sub = nullptr;       // the workspace of the boxes of oversize events (a second, smaller alignment pass)
     const uint32_t *nm() const { return (const uint32_t *)nmask.p + FSV_NM_LEAD; }     // the N mask of the store (the kernels drop it when the batch has no N: nm_active)
-    std::vector<DevBuf *> all() { return {&store, &nmask, &ascii, &asc_off, &word_off, &len, &wper, &pair_q, &pair_t, &sk_ends, &sk_low, &sk_high, &mz, &mz_off, &mz_cnt, &warn, &chain, &hdr, &events, &ev_packed, &ev_count, &tasks, &bt, &rows, &cg, &cg_n, &scores, &gaps, &gap_shift, &thin, &box_src, &corner, &corner_out}; }
 };
 
 void aln_ws_release(AlnWs *w)
 {
     if (!w) return;
     if (w->sub) aln_ws_release(w->sub);
-    for (DevBuf *b : w->all()) if (b->p) (void)hipFree(b->p);
     for (int i = 0; i < 3; i++) { if (w->side[i]) (void)hipStreamDestroy(w->side[i]); if (w->join[i]) (void)hipEventDestroy(w->join[i]); }
     if (w->fork) (void)hipEventDestroy(w->fork);
     delete w;
@@ -864,22 +860,6 @@ AlnWs *aln_ws_get(fsv_ctx *ctx)
     return (AlnWs *)ctx->aln_ws;
 }
 
-int ensure(fsv_ctx *ctx, DevBuf &b, size_t bytes)
-{
-    if (bytes <= b.cap && b.p) return FSV_OK;
-    if (b.p) { FSV_HIP(ctx, hipStreamSynchronize(ctx->stream)); FSV_HIP(ctx, hipFree(b.p)); b.p = nullptr; b.cap = 0; }
-    size_t want = bytes + bytes / 8 + 256;
-    FSV_HIP(ctx, hipMalloc(&b.p, want));
-    b.cap = want;
-    return FSV_OK;
-}
-#define TRY(x) do { int rc_ = (x); if (rc_ != FSV_OK) return rc_; } while (0)
-template <class T> int upload(fsv_ctx *ctx, DevBuf &b, const std::vector<T> &v)
-{
-    TRY(ensure(ctx, b, std::max<size_t>(v.size(), 1) * sizeof(T)));
-    if (!v.empty()) FSV_HIP(ctx, hipMemcpyAsync(b.p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, ctx->stream));
-    return FSV_OK;
-}
 struct Timer {
     std::chrono::steady_clock::time_point t0; fsv_ctx *ctx;
     explicit Timer(fsv_ctx *c) : ctx(c) { (void)hipStreamSynchronize(c->stream); t0 = std::chrono::steady_clock::now(); }

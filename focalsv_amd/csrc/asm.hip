@@ -2,7 +2,7 @@
 //
 // Replaces the process boundary `hifiasm -o <prefix> -t T <reads.fa>` + GFA read-back
 // (focalsv/3_assembly/run_assembly.py:15-44, post_assembly.py:79-95).  All base-level work runs in the
-// kernels of asm_kernels.h; the host only sizes buffers between stages and walks the (tiny, <= a few
+// kernels of asm_kernels.h and k_sketch.h; the host only sizes buffers between stages and walks the (tiny, <= a few
 // hundred nodes per set) overlap graph, which is host code in hifiasm as well (Overlaps.cpp).
 #include "asm_kernels.h"
 #include "layout.h"
@@ -16,11 +16,6 @@
 #include <atomic>
 
 namespace {
-
-struct DevBuf {
-    void *p = nullptr;
-    size_t cap = 0;
-};
 
 // HIP-event timing of kernels and of whole stages on the context's stream: recorded while the work is queued, resolved once
 // at the end of the batch -- nothing here waits for the GPU (round 1's stage timers synchronised the stream twice each)
@@ -73,7 +68,8 @@ struct AsmWs {
     fsv_asm_stats stats;
     KTimes kt;
     void *h_pin = nullptr; size_t h_pin_cap = 0; // pinned host staging (exact hits)
-    std::vector<DevBuf *> all()
+    // only the chunking budget reads this list (what this context already holds): a buffer missing from it is undercounted there, not leaked
+    std::vector<const DevBuf *> all() const
     {
         return {&store[0], &store[1], &cols_sb, &contig_all, &word_off, &len, &set_start, &read_set, &pair_base, &mz, &mz_off, &mz_cnt, &ovl, &tasks, &res, &paths,
                 &counters, &dp_list, &dp_list2, &dp_list3, &dp_list16, &dp_list_e3, &dp_wide, &dp_xwide, &cols_wide, &set_cols, &site_cnt, &site_rec, &site_off, &site_vec, &site_cursor, &redo, &site_lists, &read_dirty, &cov3, &lb, &sr_store, &brel_off, &tasks2, &res2, &paths2, &idx2, &bc_idx, &bc_rec, &bc_win, &left_list, &fix_list, &tasks3, &res3, &src3, &bnd_flag, &bnd_list, &bnd_patch, &bnd_bytes, &changed, &pair_read, &wide_list, &cols, &tmp, &gwin_off, &gwin_read, &sk_ends, &sk_low, &sk_high, &hits, &hits_packed, &set_hits, &ovl_prev, &exact_flag, &inexact_list, &upair_base, &upair_tab, &upair_tab_sw, &ovl_c, &gwin_tab, &cwin, &cwin_len, &warn, &thr_tab, &pieces, &contig_out, &new_len, &unpack_off};
@@ -84,7 +80,6 @@ void ws_free(fsv_ctx *ctx)
 {
     AsmWs *w = (AsmWs *)ctx->asm_ws;
     if (!w) return;
-    for (DevBuf *b : w->all()) if (b->p) (void)hipFree(b->p);
     if (w->h_pin) (void)hipHostFree(w->h_pin);
     delete w;
     ctx->asm_ws = nullptr;
@@ -94,25 +89,6 @@ AsmWs *ws_get(fsv_ctx *ctx)
 {
     if (!ctx->asm_ws) { ctx->asm_ws = new AsmWs(); ctx->asm_ws_free = ws_free; memset(&((AsmWs *)ctx->asm_ws)->stats, 0, sizeof(fsv_asm_stats)); }
     return (AsmWs *)ctx->asm_ws;
-}
-
-int ensure(fsv_ctx *ctx, DevBuf &b, size_t bytes)
-{
-    if (bytes <= b.cap && b.p) return FSV_OK;
-    if (b.p) { FSV_HIP(ctx, hipStreamSynchronize(ctx->stream)); FSV_HIP(ctx, hipFree(b.p)); b.p = nullptr; b.cap = 0; }
-    size_t want = bytes + bytes / 8 + 256;
-    FSV_HIP(ctx, hipMalloc(&b.p, want));
-    b.cap = want;
-    return FSV_OK;
-}
-
-#define TRY(x) do { int rc_ = (x); if (rc_ != FSV_OK) return rc_; } while (0)
-
-template <class T> int upload(fsv_ctx *ctx, DevBuf &b, const std::vector<T> &v)
-{
-    TRY(ensure(ctx, b, v.size() * sizeof(T)));
-    FSV_HIP(ctx, hipMemcpyAsync(b.p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, ctx->stream));
-    return FSV_OK;
 }
 
 uint8_t thr_for_len_host(int x_len, int rate_pm)
@@ -414,9 +390,7 @@ static int fsv_bpm_paths_impl(fsv_ctx *ctx, const uint32_t *store, size_t store_
     const int k_cap = kmax > FSV_K_MAX ? kmax : FSV_K_MAX;     // a threshold above 31 anywhere: K5 of the whole list through the wide kernel
     FSV_HIP(ctx, hipSetDevice(ctx->device));
     DevBuf d_store, d_tasks, d_res, d_paths, d_ovl, d_list, d_list2, d_list3, d_list16, d_list_e3, d_wide, d_xwide, d_cnt, d_cols, d_cols_sb, d_cols_wide;
-    auto cleanup = [&]() { for (DevBuf *b : {&d_store, &d_tasks, &d_res, &d_paths, &d_ovl, &d_list, &d_list2, &d_list3, &d_list16, &d_list_e3, &d_wide, &d_xwide, &d_cnt, &d_cols, &d_cols_sb, &d_cols_wide}) if (b->p) (void)hipFree(b->p); };
-    int rc = FSV_OK;
-    auto run = [&]() -> int {
+    {
         std::vector<fsv_wtask> t(tasks, tasks + n_tasks);
         for (auto &x : t) x.ovl = 0;
         fsv_ovl o; memset(&o, 0, sizeof(o)); o.valid = 1; o.is_match = 1;
@@ -469,11 +443,8 @@ static int fsv_bpm_paths_impl(fsv_ctx *ctx, const uint32_t *store, size_t store_
         FSV_HIP(ctx, hipMemcpyAsync(res, d_res.p, (size_t)n_tasks * sizeof(fsv_wres), hipMemcpyDeviceToHost, ctx->stream));
         FSV_HIP(ctx, hipMemcpyAsync(paths, d_paths.p, (size_t)n_tasks * sizeof(fsv_wpath), hipMemcpyDeviceToHost, ctx->stream));
         FSV_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        return FSV_OK;
-    };
-    rc = run();
-    cleanup();
-    return rc;
+    }
+    return FSV_OK;
 }
 
 extern "C" int fsv_asm_last_stats(const fsv_ctx *ctx, fsv_asm_stats *out)
@@ -1103,8 +1074,11 @@ static int assemble_chunk(fsv_ctx *ctx, const fsv_readsets *sets, const fsv_asm_
     {
         const uint32_t nthr = std::max(1u, std::min({8u, std::thread::hardware_concurrency(), B.n_sets / 16 + 1}));
         std::atomic<uint32_t> next{0};
+        // a worker never lets an exception out (it would end the process): the first failure is kept and returned after the join
+        std::atomic<int> rc_work{FSV_OK};
         auto work = [&]() {
-            for (uint32_t s = next.fetch_add(1); s < B.n_sets; s = next.fetch_add(1)) {
+            try {
+            for (uint32_t s = next.fetch_add(1); s < B.n_sets && rc_work.load() == FSV_OK; s = next.fetch_add(1)) {
                 const uint32_t r0 = B.set_start[s], ns = B.set_start[s + 1] - r0;
                 if (ns == 0) continue;
                 const uint32_t nh_s = hit_first[s + 1] - hit_first[s];
@@ -1131,11 +1105,19 @@ static int assemble_chunk(fsv_ctx *ctx, const fsv_readsets *sets, const fsv_asm_
                 }
                 layout_set(len.data() + r0, ns, hraw + hit_first[s], nh_s, P.min_contig_reads, lay[s].contigs, lay[s].fallback);
             }
+            } catch (const std::bad_alloc &) { int ok = FSV_OK; rc_work.compare_exchange_strong(ok, FSV_ENOMEM); }
+            catch (...) { int ok = FSV_OK; rc_work.compare_exchange_strong(ok, FSV_EINTERNAL); }
         };
-        std::vector<std::thread> thr;
-        for (uint32_t t = 1; t < nthr; t++) thr.emplace_back(work);
-        work();
-        for (auto &t : thr) t.join();
+        // joined on every way out of this scope, an exception from emplace_back (a thread that cannot start) included: no joinable
+        // std::thread is ever destroyed
+        struct Joiner { std::vector<std::thread> thr; ~Joiner() { for (auto &t : thr) if (t.joinable()) t.join(); } };
+        {
+            Joiner j;
+            j.thr.reserve(nthr);
+            for (uint32_t t = 1; t < nthr; t++) j.thr.emplace_back(work);
+            work();
+        }
+        if (rc_work.load() != FSV_OK) return fsv_fail(ctx, rc_work.load(), rc_work.load() == FSV_ENOMEM ? "out of host memory (layout)" : "exception in the layout of a read set");
     }
     for (uint32_t s = 0; s < B.n_sets && rc_out == FSV_OK; s++) {
         const uint32_t r0 = B.set_start[s], ns = B.set_start[s + 1] - r0;
@@ -1294,7 +1276,7 @@ static int fsv_assemble_batch_impl(fsv_ctx *ctx, const fsv_readsets *sets, const
     double budget = 0.4 * (double)ctx->hbm_bytes;
     {
         size_t free_b = 0, total_b = 0, own = 0;
-        for (DevBuf *b : W.all()) own += b->cap;
+        for (const DevBuf *b : W.all()) own += b->cap;
         if (hipMemGetInfo(&free_b, &total_b) == hipSuccess)
             budget = std::min(budget, 0.9 * ((double)free_b / (double)std::max(1, fsv_live_contexts(ctx->device)) + (double)own));
     }
@@ -1344,8 +1326,7 @@ static int fsv_assemble_batch_impl(fsv_ctx *ctx, const fsv_readsets *sets, const
                 TRY(ensure(ctx, bigger, std::max<uint64_t>((used + bytes) * 2, 1u << 20)));
                 if (used) FSV_HIP(ctx, hipMemcpyAsync(bigger.p, W.contig_all.p, used, hipMemcpyDeviceToDevice, ctx->stream));
                 FSV_HIP(ctx, hipStreamSynchronize(ctx->stream));
-                if (W.contig_all.p) FSV_HIP(ctx, hipFree(W.contig_all.p));
-                W.contig_all = bigger;
+                W.contig_all.swap(bigger);      // (the old allocation goes with `bigger`)
             }
             FSV_HIP(ctx, hipMemcpyAsync((char *)W.contig_all.p + used, W.contig_out.p, bytes, hipMemcpyDeviceToDevice, ctx->stream));
         }
@@ -1390,8 +1371,6 @@ static int fsv_asm_fetch_reads_impl(fsv_ctx *ctx, char *seq, uint64_t seq_cap, u
         if (hipGetLastError() != hipSuccess) rc = FSV_EHIP;
     }
     if (rc == FSV_OK) rc = fsv_d2h(ctx, seq, d_out.p, o[n_reads]);
-    if (d_off.p) (void)hipFree(d_off.p);
-    if (d_out.p) (void)hipFree(d_out.p);
     memcpy(off, o.data(), (n_reads + 1) * sizeof(uint64_t));
     return rc;
 }

@@ -56,6 +56,25 @@ __device__ __forceinline__ uint32_t fsv_base_at(const uint32_t *__restrict__ sto
     return rev ? (3u - b) : b;
 }
 
+// wave-wide max, uniform result.  __shfl_xor goes through the LDS crossbar (ds_bpermute, ~6 dependent round trips);
+// DPP row operations reduce each 16-lane row in four VALU ops and the four row results are read as scalars.
+__device__ __forceinline__ int wave_max_i32(int v)
+{
+    const int lowest = -2147483647 - 1;
+    v = max(v, __builtin_amdgcn_update_dpp(lowest, v, 0xB1, 0xF, 0xF, false));  // quad_perm [1,0,3,2]
+    v = max(v, __builtin_amdgcn_update_dpp(lowest, v, 0x4E, 0xF, 0xF, false));  // quad_perm [2,3,0,1]
+    v = max(v, __builtin_amdgcn_update_dpp(lowest, v, 0x141, 0xF, 0xF, false)); // row_half_mirror
+    v = max(v, __builtin_amdgcn_update_dpp(lowest, v, 0x140, 0xF, 0xF, false)); // row_mirror
+    const int a = __builtin_amdgcn_readlane(v, 0), b = __builtin_amdgcn_readlane(v, 16);
+    const int c = __builtin_amdgcn_readlane(v, 32), d = __builtin_amdgcn_readlane(v, 48);
+    return max(max(a, b), max(c, d));
+}
+__device__ __forceinline__ long long wave_max_i64(long long v)
+{
+    for (int off = 32; off > 0; off >>= 1) { long long o = __shfl_xor(v, off, 64); v = o > v ? o : v; }
+    return v;
+}
+
 int fsv_live_contexts(int device);   // ctx.hip: contexts alive on a device
 
 // the C entry points never let a C++ exception through (a std::bad_alloc from a vector sized by caller data, a std::system_error
@@ -67,6 +86,40 @@ int fsv_live_contexts(int device);   // ctx.hip: contexts alive on a device
     catch (...) { return fsv_fail(ctx, FSV_EINTERNAL, "unknown exception"); }
 
 static inline unsigned fsv_grid_for(uint64_t n, unsigned block) { return (unsigned)((n + block - 1) / block); }
+
+#define TRY(x) do { int rc_ = (x); if (rc_ != FSV_OK) return rc_; } while (0)
+
+// ---- device buffers -------------------------------------------------------------------
+// A device allocation that only grows.  It owns its memory: the destructor frees it, so deleting a workspace frees its buffers.
+struct DevBuf {
+    void *p = nullptr;
+    size_t cap = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    ~DevBuf() { if (p) (void)hipFree(p); }
+    void swap(DevBuf &o) { void *tp = p; p = o.p; o.p = tp; const size_t tc = cap; cap = o.cap; o.cap = tc; }
+};
+
+// room for `bytes` (an eighth more, so that a slowly growing batch does not reallocate every call).  What the buffer held is
+// lost when it grows; the stream is drained before the old allocation goes.
+static inline int ensure(fsv_ctx *ctx, DevBuf &b, size_t bytes)
+{
+    if (bytes <= b.cap && b.p) return FSV_OK;
+    if (b.p) { FSV_HIP(ctx, hipStreamSynchronize(ctx->stream)); FSV_HIP(ctx, hipFree(b.p)); b.p = nullptr; b.cap = 0; }
+    const size_t want = bytes + bytes / 8 + 256;
+    FSV_HIP(ctx, hipMalloc(&b.p, want));
+    b.cap = want;
+    return FSV_OK;
+}
+
+// (an empty vector still leaves a valid pointer behind: kernels are handed b.p whatever the count)
+template <class T> int upload(fsv_ctx *ctx, DevBuf &b, const std::vector<T> &v)
+{
+    TRY(ensure(ctx, b, (v.empty() ? 1 : v.size()) * sizeof(T)));
+    if (!v.empty()) FSV_HIP(ctx, hipMemcpyAsync(b.p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, ctx->stream));
+    return FSV_OK;
+}
 
 // K5 with the task count left on the device (k5_bpm.hip): n_tasks sizes the grid, *n_dev is the count the kernel uses
 // k_cap: the largest threshold of the batch's error model (31 = hifiasm's; above it every window goes through the wide-band kernel)

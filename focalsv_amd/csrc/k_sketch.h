@@ -1,0 +1,517 @@
+// k_sketch.h -- minimizer sketch and per-read index: k_sketch (replay, even k), k_sketch_fast (position-parallel, odd k),
+// k_uniq / k_uniq_walk.  Included by asm.hip (through asm_kernels.h) and by aln.hip; each of the two translation units gets its own
+// copy of these kernels and of nothing else.
+#pragma once
+#include "fsv_internal.h"
+
+#define FSV_UQ_MAX     4096  // minimizers per read sorted in LDS
+
+namespace {
+
+// ------------------------------------------------------------------------------------------------ k_sketch
+__device__ __forceinline__ uint64_t mix64(uint64_t key)
+{
+    key = ~key + (key << 21);
+    key = key ^ key >> 24;
+    key = (key + (key << 3)) + (key << 8);
+    key = key ^ key >> 14;
+    key = (key + (key << 2)) + (key << 4);
+    key = key ^ key >> 28;
+    key = key + (key << 31);
+    return key;
+}
+
+// One wavefront per read.  The minimizer recurrence is sequential, but what it emits at a position only depends on
+// the w entries around it (and on the k HPC bases behind them), so every lane replays the recurrence over its own 1/64
+// of the read plus a warm-up of w+k+4 homopolymer runs in front and w+2 runs behind, and keeps only the minimizers whose
+// end position falls inside its own slice.  Output order is arbitrary (k_uniq sorts).
+//
+// The reference keeps a w-slot ring and rescans it whenever the minimum slides out (two passes over w slots); in SIMT
+// some lane rescans at almost every step, so the whole wave would pay ~2w LDS reads per step.  The replay therefore
+// uses a monotone deque (hashes non-decreasing front to back, ties kept) that holds exactly the window elements which
+// can still become a minimum.  ha_sketch emits an element exactly once iff it equals the minimum of some window that
+// ends at or after the first full one -- as the "best" when that is replaced / slides out / the read ends, or as an
+// "identical k-mer" copy when a rescan (or the first full window) finds it (sketch.cpp:101-135) -- so here an element
+// is emitted the moment it joins the deque's front run.  The one irregular step is the first full window (l == w+k-1):
+// copies of the previous partial window's minimum are emitted and that minimum itself is dropped silently if the
+// incoming k-mer ties or beats it (sketch.cpp:101-106 run before 116-118 with l < w+k); replicated literally below.
+// Dynamic LDS: [w x 64 hashes][read words][w x 64 pos|span][w x 64 time|flag|rev][(k+1) x 64 run lengths].
+__host__ __device__ inline size_t sketch_lds_bytes(int w, uint32_t read_words) { return (size_t)read_words * 4 + (size_t)w * 64 * 14 + 64 * 64 + 16; }
+
+struct WordCache { // sequential base access through one cached 16-base word
+    const uint32_t *p; uint32_t w; int idx;
+    __device__ __forceinline__ uint32_t get(int i) { const int wi = i >> 4; if (wi != idx) { w = p[wi]; idx = wi; } return (w >> ((i & 15) << 1)) & 3u; }
+};
+
+__global__ __launch_bounds__(64) void k_sketch(const uint32_t *__restrict__ store, const uint32_t *__restrict__ word_off,
+                                               const int32_t *__restrict__ read_len, const uint32_t *__restrict__ mz_off,
+                                               fsv_mz *__restrict__ mz, uint32_t *__restrict__ mz_cnt, uint32_t n_reads, int w, int k,
+                                               int hpc, uint32_t *__restrict__ warn, const uint8_t *__restrict__ w_per_read, int w_max,
+                                               uint32_t lds_words)
+{
+    extern __shared__ __attribute__((aligned(16))) uint8_t s_dyn[];
+    const int lane = threadIdx.x;
+    const uint32_t r = blockIdx.x;
+    if (r >= n_reads) return;
+    const uint32_t woff = word_off[r];
+    const int len = read_len[r];
+    const uint32_t cap = mz_off[r + 1] - mz_off[r];
+    fsv_mz *out = mz + mz_off[r];
+    if (w_per_read) w = w_per_read[r];
+    uint64_t *d_hash = (uint64_t *)s_dyn;                               // [w_max][64]
+    uint32_t *s_words = (uint32_t *)(d_hash + (size_t)w_max * 64);      // [lds_words]
+    uint32_t *d_ps = s_words + lds_words;                               // [w_max][64]   pos << 8 | span
+    uint16_t *d_tf = (uint16_t *)(d_ps + (size_t)w_max * 64);           // [w_max][64]   (time & 0x3fff) << 2 | rev << 1 | emitted
+    uint8_t *q_run = (uint8_t *)(d_tf + (size_t)w_max * 64);            // [64][64]      saturating run lengths
+#define D_HASH(j) d_hash[(j) * 64 + lane]
+#define D_PS(j) d_ps[(j) * 64 + lane]
+#define D_TF(j) d_tf[(j) * 64 + lane]
+#define Q_RUN(j) q_run[(j) * 64 + lane]
+    const uint32_t nwords = ((uint32_t)len + 15u) >> 4;
+    const bool staged = nwords <= lds_words;
+    if (staged) for (uint32_t i = lane; i < nwords; i += 64) s_words[i] = store[woff + i];
+    __syncthreads();
+    WordCache B{staged ? (const uint32_t *)s_words : store + woff, 0u, -1};
+    // For even k palindromic k-mers are skipped (sketch.cpp:84), so a fixed warm-up cannot guarantee w entries: lane 0 then
+    // replays the whole read from base 0 (exact, 64x less parallel; hifiasm's k = 51 and minimap2's 19 are odd and use k_sketch_fast).
+    const bool single = (k & 1) == 0;
+    const int c0 = single ? 0 : (int)((long long)len * lane / 64), c1 = single ? (lane == 0 ? len : 0) : (int)((long long)len * (lane + 1) / 64);
+    if (c1 <= c0) return;
+    int b0 = c0;
+    if (hpc) {
+        while (b0 > 0 && B.get(b0 - 1) == B.get(b0)) b0--;
+        for (int n = 0; n < w + k + 4 && b0 > 0; n++) {
+            b0--;
+            const uint32_t c = B.get(b0);
+            while (b0 > 0 && B.get(b0 - 1) == c) b0--;
+        }
+    } else {
+        b0 = max(0, c0 - (w + k + 4));
+    }
+    const uint64_t NONE = ~0ull;
+    const uint64_t mask = (1ull << k) - 1;
+    uint64_t km0 = 0, km1 = 0, km2 = 0, km3 = 0;
+    int run_head = 0, run_cnt = 0, span = 0;
+    int head = 0, cnt = 0;          // deque = slots (head + j) mod w, j < cnt
+    int l = b0 > 0 ? w + k + 1 : 0; // past the start-up phase every "l >= ..." test of the reference holds
+    int tail = -1;                  // runs still to replay once the slice is done
+
+#define EMIT_SLOT(sl)                                                                                      \
+    do {                                                                                                   \
+        const uint32_t ps_ = D_PS(sl); const uint16_t tf_ = D_TF(sl);                                      \
+        const int p_ = (int)(ps_ >> 8);                                                                    \
+        if (p_ >= c0 && p_ < c1) {                                                                         \
+            const uint32_t at_ = atomicAdd(&mz_cnt[r], 1u);                                                \
+            if (at_ < cap) { fsv_mz m_; m_.hash = D_HASH(sl); m_.pos = (uint32_t)p_; m_.rev = (uint8_t)((tf_ >> 1) & 1u); m_.span = (uint8_t)(ps_ & 0xffu); m_.pad = 0; out[at_] = m_; } \
+            else atomicOr(&warn[r], (uint32_t)FSV_W_MZ_TRUNC);                                             \
+        }                                                                                                  \
+        D_TF(sl) = (uint16_t)(tf_ | 1u);                                                                   \
+    } while (0)
+#define WRAP(x) ((x) >= w ? (x) - w : (x))
+
+    int i = b0;
+    for (; i < len; i++) {
+        if (i >= c1) { if (tail < 0) tail = w + 2; if (tail-- == 0) break; }
+        const uint32_t c = B.get(i);
+        uint64_t cur_h = NONE; uint32_t cur_ps = 0; uint32_t cur_rev = 0;
+        if (hpc) {
+            int run = 1;
+            while (i + run < len && B.get(i + run) == c) run++;
+            i += run - 1;
+            const int rs = min(run, 255); // saturating: one run >= 255 puts the span at >= 256 (= no minimizer) either way
+            Q_RUN((run_head + run_cnt++) & 63) = (uint8_t)rs;
+            span += rs;
+            if (run_cnt > k) { span -= Q_RUN(run_head); run_head = (run_head + 1) & 63; run_cnt--; }
+        } else {
+            span = l + 1 < k ? l + 1 : k;
+        }
+        km0 = (km0 << 1 | (uint64_t)(c & 1u)) & mask;
+        km1 = (km1 << 1 | (uint64_t)(c >> 1)) & mask;
+        km2 = km2 >> 1 | (uint64_t)(1u - (c & 1u)) << (k - 1);
+        km3 = km3 >> 1 | (uint64_t)(1u - (c >> 1)) << (k - 1);
+        if (km1 == km3) continue; // palindrome: not an entry (sketch.cpp:84)
+        const int z = km1 < km3 ? 0 : 1;
+        ++l;
+        if (l >= k && span < 256) {
+            cur_h = z ? mix64(km2) + mix64(km3) : mix64(km0) + mix64(km1);
+            cur_ps = ((uint32_t)i << 8) | (uint32_t)span;
+            cur_rev = (uint32_t)z;
+        }
+        const int tcur = l & 0x3fff; // entry time, modulo 2^14 (windows are at most 64 entries long)
+        // expire what has left the window of the last w entries
+        while (cnt > 0 && (((tcur - (int)(D_TF(head) >> 2)) & 0x3fff) >= w)) { head = WRAP(head + 1); cnt--; }
+        if (l == w + k - 1 && cnt > 0 && D_HASH(head) != NONE) {
+            // first full window (only lanes that replay from base 0 get here): copies of the partial window's minimum
+            // are emitted (sketch.cpp:101-106); the minimum itself is lost if the incoming k-mer ties or beats it (:116-118)
+            const uint64_t m = D_HASH(head);
+            int run = 1;
+            while (run < cnt && D_HASH(WRAP(head + run)) == m) run++;
+            for (int j = 0; j + 1 < run; j++) { const int sl = WRAP(head + j); EMIT_SLOT(sl); }
+            if (cur_h <= m) { const int sl = WRAP(head + run - 1); D_TF(sl) = (uint16_t)(D_TF(sl) | 1u); }
+        }
+        // keep hashes non-decreasing front to back (ties stay: they are the "identical k-mers")
+        while (cnt > 0 && D_HASH(WRAP(head + cnt - 1)) > cur_h) cnt--;
+        {
+            const int sl = WRAP(head + cnt);
+            D_HASH(sl) = cur_h; D_PS(sl) = cur_ps; D_TF(sl) = (uint16_t)((uint32_t)tcur << 2 | cur_rev << 1);
+            cnt++;
+        }
+        if (l >= w + k - 1) {
+            const uint64_t m = D_HASH(head);
+            if (m != NONE)
+                for (int j = 0; j < cnt; j++) {
+                    const int sl = WRAP(head + j);
+                    if (D_HASH(sl) != m) break;
+                    if (!(D_TF(sl) & 1u)) EMIT_SLOT(sl);
+                }
+        }
+    }
+    if (i >= len && l < w + k - 1 && cnt > 0 && D_HASH(head) != NONE) {
+        // a read shorter than one window: only the last minimum is reported (sketch.cpp:134-135)
+        const uint64_t m = D_HASH(head);
+        int run = 1;
+        while (run < cnt && D_HASH(WRAP(head + run)) == m) run++;
+        const int sl = WRAP(head + run - 1);
+        EMIT_SLOT(sl);
+    }
+#undef EMIT_SLOT
+#undef WRAP
+#undef D_HASH
+#undef D_PS
+#undef D_TF
+#undef Q_RUN
+}
+
+// ------------------------------------------------------------------------------------------------ k_uniq
+// One workgroup per read: bitonic sort of (hash, pos) in LDS, keep hashes that occur exactly once.
+template <int UQ_MAX>
+__device__ __forceinline__ void uniq_read(const uint32_t r, fsv_mz *__restrict__ mz, const uint32_t *__restrict__ mz_off, uint32_t *__restrict__ mz_cnt,
+                                          uint32_t *__restrict__ warn, const uint32_t *__restrict__ only_changed, uint32_t lo_cnt, uint32_t hi_cnt,
+                                          unsigned long long *__restrict__ total, const uint32_t max_occ = 1u)
+{
+    __shared__ uint64_t s_hash[UQ_MAX];
+    __shared__ uint64_t s_pay[UQ_MAX]; // pos | rev << 32 | span << 40
+    __shared__ uint32_t s_scan[256];
+    const int tid = threadIdx.x;
+    if (only_changed && !only_changed[r]) return;   // lists of an unchanged read are already in place
+    // The sort holds a read's list in LDS, so the kernel is instantiated for short and for long lists (many reads per CU for
+    // the former) and launched once per size class: lo_cnt < raw count <= hi_cnt.  The small class runs first -- it replaces
+    // the raw count by the unique count, which can only be smaller, so the large class skips what the small one has done.
+    { const uint32_t raw = mz_cnt[r]; if (raw <= lo_cnt || raw > hi_cnt) return; }
+    fsv_mz *a = mz + mz_off[r];
+    uint32_t n = min(mz_cnt[r], mz_off[r + 1] - mz_off[r]); // k_sketch counts past the cap when it truncates
+    const uint32_t n_raw = n;
+    if (n > UQ_MAX) { if (tid == 0) atomicOr(&warn[r], (uint32_t)FSV_W_MZ_TRUNC); n = UQ_MAX; }
+    uint32_t np = 1;
+    while (np < n) np <<= 1;
+    for (uint32_t i = tid; i < np; i += 256) {
+        if (i < n) { fsv_mz m = a[i]; s_hash[i] = m.hash; s_pay[i] = (uint64_t)m.pos | (uint64_t)m.rev << 32 | (uint64_t)m.span << 40; }
+        else { s_hash[i] = ~0ull; s_pay[i] = ~0ull; }
+    }
+    __syncthreads();
+    for (uint32_t sz = 2; sz <= np; sz <<= 1)
+        for (uint32_t st = sz >> 1; st > 0; st >>= 1) {
+            for (uint32_t t = tid; t < np / 2; t += 256) { // one compare-exchange per thread and trip: pair t = (i, i | st)
+                const uint32_t i = ((t & ~(st - 1)) << 1) | (t & (st - 1)), j = i | st;
+                const bool up = (i & sz) == 0;
+                const uint64_t hi = s_hash[i], hj = s_hash[j], pi = s_pay[i], pj = s_pay[j];
+                const bool gt = hi > hj || (hi == hj && (uint32_t)pi > (uint32_t)pj);
+                if (gt == up) { s_hash[i] = hj; s_hash[j] = hi; s_pay[i] = pj; s_pay[j] = pi; }
+            }
+            __syncthreads();
+        }
+    // unique flags + block compaction (each thread owns a contiguous chunk; its survivors wait in registers until every
+    // thread has read its chunk, because they move towards lower indices, i.e. into other threads' chunks)
+    const uint32_t per = (n + 255) / 256;
+    const uint32_t lo = min(n, tid * per), hi = min(n, lo + per);
+    uint64_t kh[UQ_MAX / 256], kp[UQ_MAX / 256];
+    uint32_t cnt = 0;
+#pragma unroll
+    for (uint32_t j = 0; j < UQ_MAX / 256; j++) {
+        const uint32_t i = lo + j;
+        if (i < hi) {
+            bool u = (i == 0 || s_hash[i - 1] != s_hash[i]) && (i + 1 >= n || s_hash[i + 1] != s_hash[i]);
+            if (max_occ > 1u && !u) {   // the aligner's second seeding of an oversize event keeps hashes that occur up to max_occ times
+                uint32_t run = 1;
+                for (uint32_t d = 1; d <= max_occ && i >= d && s_hash[i - d] == s_hash[i]; d++) run++;
+                for (uint32_t d = 1; d <= max_occ && i + d < n && s_hash[i + d] == s_hash[i]; d++) run++;
+                u = run <= max_occ;
+            }
+            if (u) { kh[cnt] = s_hash[i]; kp[cnt] = s_pay[i]; cnt++; }
+        }
+    }
+    s_scan[tid] = cnt;
+    __syncthreads();
+    if (tid == 0) {
+        uint32_t acc = 0;
+        for (int i = 0; i < 256; i++) { uint32_t c = s_scan[i]; s_scan[i] = acc; acc += c; }
+        mz_cnt[r] = acc;
+        if (total) {   // statistics of the launch: unique minimizers; minimizers the sketch produced; bases of the reads it sketched
+            atomicAdd(total, (unsigned long long)acc);
+            atomicAdd(total + 3, (unsigned long long)n_raw);                                     // CT_MZRAW (asm.hip)
+            atomicAdd(total + 4, (unsigned long long)(mz_off[r + 1] - mz_off[r] - 64u));         // CT_BASES: a slot holds len + 64 entries
+        }
+    }
+    __syncthreads();
+    const uint32_t m = mz_cnt[r];
+    const uint32_t o0 = s_scan[tid];
+    const uint32_t slot_cap = mz_off[r + 1] - mz_off[r];
+    __syncthreads();
+#pragma unroll
+    for (uint32_t j = 0; j < UQ_MAX / 256; j++)
+        if (j < cnt) { s_hash[o0 + j] = kh[j]; s_pay[o0 + j] = kp[j]; }
+    __syncthreads();
+    // [0, m): sorted by hash (the "target" role: binary-searched)
+    for (uint32_t i = tid; i < m; i += 256) { fsv_mz x; x.hash = s_hash[i]; const uint64_t p = s_pay[i]; x.pos = (uint32_t)p; x.rev = (uint8_t)(p >> 32); x.span = (uint8_t)(p >> 40); x.pad = 0; a[i] = x; }
+    // [m, 2m): the same minimizers sorted by position (the "query" role: anchors then come out in query order and the
+    // chain kernels need no per-pair sort)
+    if (2 * m <= slot_cap) {
+        uint32_t mp = 1;
+        while (mp < m) mp <<= 1;
+        for (uint32_t i = m + tid; i < mp; i += 256) { s_hash[i] = ~0ull; s_pay[i] = ~0ull; }
+        __syncthreads();
+        for (uint32_t sz = 2; sz <= mp; sz <<= 1)
+            for (uint32_t st = sz >> 1; st > 0; st >>= 1) {
+                for (uint32_t t = tid; t < mp / 2; t += 256) {
+                    const uint32_t i = ((t & ~(st - 1)) << 1) | (t & (st - 1)), j = i | st;
+                    const bool up = (i & sz) == 0;
+                    const uint64_t pi = s_pay[i], pj = s_pay[j];
+                    bool gt = (uint32_t)pi > (uint32_t)pj || ((uint32_t)pi == (uint32_t)pj && pi > pj);
+                    if (pi == ~0ull && pj != ~0ull) gt = true; else if (pj == ~0ull) gt = false;
+                    if (gt == up) { const uint64_t hi2 = s_hash[i], hj = s_hash[j]; s_hash[i] = hj; s_hash[j] = hi2; s_pay[i] = pj; s_pay[j] = pi; }
+                }
+                __syncthreads();
+            }
+        for (uint32_t i = tid; i < m; i += 256) { fsv_mz x; x.hash = s_hash[i]; const uint64_t p = s_pay[i]; x.pos = (uint32_t)p; x.rev = (uint8_t)(p >> 32); x.span = (uint8_t)(p >> 40); x.pad = 0; a[m + i] = x; }
+    } else if (tid == 0) atomicOr(&warn[r], (uint32_t)FSV_W_INTERNAL); // cannot happen: at most one minimizer per base and slots hold len + 64
+}
+
+template <int UQ_MAX>
+__global__ __launch_bounds__(256) void k_uniq(fsv_mz *__restrict__ mz, const uint32_t *__restrict__ mz_off, uint32_t *__restrict__ mz_cnt,
+                                              uint32_t *__restrict__ warn, const uint32_t *__restrict__ only_changed = nullptr,
+                                              uint32_t lo_cnt = 0u, uint32_t hi_cnt = 0xffffffffu, unsigned long long *__restrict__ total = nullptr,
+                                              uint32_t max_occ = 1u)
+{
+    uniq_read<UQ_MAX>(blockIdx.x, mz, mz_off, mz_cnt, warn, only_changed, lo_cnt, hi_cnt, total, max_occ);
+}
+
+// the same for a size class that is usually empty (lists above 1 024 entries in a HiFi batch): a few blocks walk all reads, so the
+// 64 KB of LDS a block of this instantiation needs are claimed a few hundred times, not once per read (under three lanes the
+// one-block-per-read launch averaged 2.8 ms against 0.01 alone: every block waited for LDS only to find its read in the other class)
+template <int UQ_MAX>
+__global__ __launch_bounds__(256) void k_uniq_walk(fsv_mz *__restrict__ mz, const uint32_t *__restrict__ mz_off, uint32_t *__restrict__ mz_cnt,
+                                                   uint32_t *__restrict__ warn, const uint32_t *__restrict__ only_changed, uint32_t lo_cnt, uint32_t hi_cnt,
+                                                   unsigned long long *__restrict__ total, uint32_t n_reads)
+{
+    for (uint32_t r = blockIdx.x; r < n_reads; r += gridDim.x) {
+        uniq_read<UQ_MAX>(r, mz, mz_off, mz_cnt, warn, only_changed, lo_cnt, hi_cnt, total);
+        __syncthreads();
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ k_sketch_fast
+// Position-parallel form of ha_sketch (sketch.cpp:39-137) for odd k (hifiasm's 51, minimap2's 19): no sequential replay.
+//   phase 0  homopolymer compression in parallel: run ends are found per 16-base word, a block scan gives every kept
+//            base its entry index; the compressed bases go to two bit planes, the run-end positions to an array
+//            (per-read slices of an HBM scratch, L2-resident for the block that wrote them);
+//   phase 1  every entry's k-mer is cut out of the bit planes with funnel shifts (forward strand = bit-reversed,
+//            reverse strand = complemented), hashed, and the span is a difference of two run-end positions;
+//   phase 2  ha_sketch reports an entry iff it equals the minimum of some window of w entries that ends at or after the
+//            first full one (as the window's "best" or as an identical-k-mer copy); window minima and the test are
+//            brute-force scans of an LDS tile.  The irregular first full window (l == w+k-1: copies of the previous
+//            partial window's minimum are reported, that minimum itself only if the incoming k-mer is larger) and reads
+//            shorter than one window (only the last minimum) are handled explicitly.
+// Equivalent to the monotone-deque replay in k_sketch (which stays for even k); both are checked against the oracle.
+#define SKF_T 1024
+#define SKF_V ((SKF_T + 2 * 256 + 255) / 256)   // elements of the doubling passes per thread
+__global__ __launch_bounds__(256) void k_sketch_fast(const uint32_t *__restrict__ store, const uint32_t *__restrict__ word_off,
+                                                     const int32_t *__restrict__ read_len, const uint32_t *__restrict__ mz_off,
+                                                     fsv_mz *__restrict__ mz, uint32_t *__restrict__ mz_cnt, uint32_t n_reads, int w, int k,
+                                                     int hpc, uint32_t *__restrict__ warn, const uint8_t *__restrict__ w_per_read,
+                                                     uint32_t *__restrict__ sc_ends, uint32_t *__restrict__ sc_low, uint32_t *__restrict__ sc_high,
+                                                     const uint32_t *__restrict__ only_changed)
+{
+    __shared__ uint64_t s_h[SKF_T + 2 * 256];   // w <= 255
+    __shared__ uint64_t s_wmin[SKF_T + 2 * 256];
+    __shared__ uint32_t s_scan[4];
+    __shared__ uint32_t s_carry;
+    __shared__ uint64_t s_am, s_ah;   // start anomaly: minimum of the partial window, hash of entry T0
+    __shared__ int s_abest, s_short;  // its rightmost position; the single minimizer of a read shorter than one window
+    const int tid = threadIdx.x;
+    const uint32_t r = blockIdx.x;
+    if (r >= n_reads) return;
+    // a read the last correction round left as it was keeps the minimizers of that round (same sequence, same slot)
+    if (only_changed && !only_changed[r]) return;
+    const uint32_t woff = word_off[r];
+    const int len = read_len[r];
+    const uint32_t cap = mz_off[r + 1] - mz_off[r];
+    fsv_mz *out = mz + mz_off[r];
+    if (w_per_read) w = w_per_read[r];
+    if (tid == 0) mz_cnt[r] = 0;   // (the first emit comes after several barriers)
+    uint32_t *ends = sc_ends + (size_t)woff * 16;          // entry -> index of the run's last base
+    uint32_t *low = sc_low + woff + r, *high = sc_high + woff + r; // bit planes of the compressed bases (zeroed by the host)
+    const uint64_t NONE = ~0ull;
+    const uint64_t kmask = (1ull << k) - 1;
+    // ---- phase 0
+    const int nwords = (len + 15) >> 4;
+    if (tid == 0) s_carry = 0;
+    __syncthreads();
+    for (int wbase = 0; wbase < nwords; wbase += 256) {
+        const int wi = wbase + tid;
+        uint32_t flags = 0, word = 0;
+        int nb = 0;
+        if (wi < nwords) {
+            word = store[woff + wi];
+            nb = min(16, len - wi * 16);
+            if (hpc) {
+                const uint32_t nextb = (wi + 1 < nwords) ? (store[woff + wi + 1] & 3u) : 4u;
+                // base j ends a run when it differs from base j+1 (the read's last base always does)
+                const uint32_t shifted = (word >> 2) | (nextb << 30);
+                uint32_t d = word ^ shifted;
+                d = (d | (d >> 1)) & 0x55555555u; // field j non-zero <=> base j != base j+1
+                // even bits -> 16-bit mask; the read's last base always ends a run
+                d = (d | (d >> 1)) & 0x33333333u; d = (d | (d >> 2)) & 0x0f0f0f0fu; d = (d | (d >> 4)) & 0x00ff00ffu; d = (d | (d >> 8)) & 0xffffu;
+                flags = nb >= 16 ? d : (d & ((1u << nb) - 1u));
+                if (len - 1 - wi * 16 < 16) flags |= 1u << (len - 1 - wi * 16);
+            } else flags = nb >= 16 ? 0xffffu : ((1u << nb) - 1u);
+        }
+        const uint32_t cnt = __popc(flags);
+        // exclusive scan over the 256 threads: shuffle scan inside each wave, the four wave totals through LDS
+        uint32_t incl = cnt;
+        for (int off = 1; off < 64; off <<= 1) { const uint32_t o2 = __shfl_up(incl, off, 64); if ((tid & 63) >= off) incl += o2; }
+        if ((tid & 63) == 63) s_scan[tid >> 6] = incl;
+        __syncthreads();
+        uint32_t wave_before = 0, tile_total = 0;
+#pragma unroll
+        for (int wv = 0; wv < 4; wv++) { const uint32_t v = s_scan[wv]; if (wv < (tid >> 6)) wave_before += v; tile_total += v; }
+        const uint32_t base = s_carry + wave_before + incl - cnt;
+        if (cnt) {
+            uint32_t lo = 0, hi = 0, rank = 0;
+            for (int j = 0; j < nb; j++)
+                if ((flags >> j) & 1u) {
+                    const uint32_t b = (word >> (2 * j)) & 3u;
+                    lo |= (b & 1u) << rank; hi |= (b >> 1) << rank;
+                    ends[base + rank] = (uint32_t)(wi * 16 + j);
+                    rank++;
+                }
+            const uint32_t wd = base >> 5, sh = base & 31u;
+            atomicOr(&low[wd], lo << sh); atomicOr(&high[wd], hi << sh);
+            if (sh + cnt > 32) { atomicOr(&low[wd + 1], lo >> (32 - sh)); atomicOr(&high[wd + 1], hi >> (32 - sh)); }
+        }
+        __syncthreads();
+        if (tid == 0) s_carry += tile_total;
+        __syncthreads();
+    }
+    const int M = (int)s_carry; // entries
+    const int T0 = w + k - 2;   // entry index of the first full window (l == w+k-1)
+    __threadfence_block();
+    __syncthreads();
+    // k consecutive plane bits starting at entry a (a >= 0), bit i = entry a+i
+    auto cut = [&](const uint32_t *pl, int a) -> uint64_t {
+        const int wd = a >> 5, sh = a & 31;
+        const uint64_t lo64 = (uint64_t)pl[wd] | (uint64_t)pl[wd + 1] << 32;
+        uint64_t v = lo64 >> sh;
+        if (sh) v |= (uint64_t)pl[wd + 2] << (64 - sh);
+        return v & kmask;
+    };
+    auto entry_hash = [&](int e, int *z_out) -> uint64_t {
+        if (e < k - 1 || e >= M) return NONE;
+        const int span = (int)ends[e] - (e - k >= 0 ? (int)ends[e - k] : -1);
+        if (hpc && span >= 256) return NONE;
+        const uint64_t lo = cut(low, e - k + 1), hi = cut(high, e - k + 1);
+        // forward strand: oldest base in the top bit; reverse strand: complement, oldest base in bit 0
+        const uint64_t f0 = __brevll(lo) >> (64 - k), f1 = __brevll(hi) >> (64 - k);
+        const uint64_t r0 = ~lo & kmask, r1 = ~hi & kmask;
+        const int z = f1 < r1 ? 0 : 1;
+        if (z_out) *z_out = z;
+        return mix64(z ? r0 : f0) + mix64(z ? r1 : f1);   // the strand is chosen first: two hashes per entry, not four
+    };
+    auto emit = [&](int p) {
+        int z = 0;
+        const uint64_t h = entry_hash(p, &z);
+        const int span = hpc ? (int)ends[p] - (p - k >= 0 ? (int)ends[p - k] : -1) : k;
+        const uint32_t at = atomicAdd(&mz_cnt[r], 1u);
+        if (at < cap) { fsv_mz m; m.hash = h; m.pos = ends[p]; m.rev = (uint8_t)z; m.span = (uint8_t)span; m.pad = 0; out[at] = m; }
+        else atomicOr(&warn[r], (uint32_t)FSV_W_MZ_TRUNC);
+    };
+    for (int t0 = 0; t0 < M; t0 += SKF_T) {
+        const int e0 = t0 - (w - 1); // entry held by s_h[0]
+        for (int idx = tid; idx < SKF_T + 2 * (w - 1); idx += 256) s_h[idx] = entry_hash(e0 + idx, nullptr);
+        __syncthreads();
+        // window minima: s_wmin[i] = min over entries (t0+i)-(w-1) .. (t0+i) = min(s_h[i .. i+w-1]), by doubling: after the
+        // pass with distance d an element covers 2d entries; two overlapping power-of-two ranges make the window of w
+        const int NW = SKF_T + 2 * (w - 1);
+        int p2 = 1;
+        while (p2 * 2 <= w) p2 <<= 1;
+        // every thread keeps its own elements in registers between the passes and only reads its partner's from the tile
+        uint64_t v[SKF_V];
+#pragma unroll
+        for (int c = 0; c < SKF_V; c++) { const int i = tid + 256 * c; v[c] = i < NW ? s_h[i] : NONE; }
+        auto pass = [&](const uint64_t *src, int d, bool is_max) {   // s_wmin[i] = op(own[i], src[i+d]) for every i < NW
+#pragma unroll
+            for (int c = 0; c < SKF_V; c++) {
+                const int i = tid + 256 * c;
+                if (i < NW) {
+                    const uint64_t b = i + d < NW ? src[i + d] : (is_max ? 0ull : NONE);
+                    v[c] = is_max ? max(v[c], b) : min(v[c], b);
+                }
+            }
+            __syncthreads();
+#pragma unroll
+            for (int c = 0; c < SKF_V; c++) { const int i = tid + 256 * c; if (i < NW) s_wmin[i] = v[c]; }
+            __syncthreads();
+        };
+        if (w == 1) pass(s_h, 0, false);
+        else {
+            pass(s_h, 1, false);
+            for (int d = 2; d < p2; d <<= 1) pass(s_wmin, d, false);
+            if (w > p2) pass(s_wmin, w - p2, false);
+        }
+        if (t0 == 0 && tid == 0) {
+            s_short = -1; s_abest = -1; s_am = NONE; s_ah = NONE;
+            if (M <= T0) { // shorter than one window: only the last minimum (rightmost on ties)
+                uint64_t m = NONE; int bp = -1;
+                for (int p = max(0, M - w); p < M; p++) { const uint64_t h = s_h[p - e0]; if (h != NONE && h <= m) { m = h; bp = p; } }
+                s_short = bp;
+            } else {
+                uint64_t m = NONE; int bp = -1;
+                for (int p = T0 - w + 1; p <= T0 - 1; p++) { const uint64_t h = s_h[p - e0]; if (h != NONE && h <= m) { m = h; bp = p; } }
+                s_am = m; s_abest = bp; s_ah = s_h[T0 - e0];
+            }
+        }
+        __syncthreads();
+        // an entry is reported iff it equals the minimum of one of the windows that contain it and end in [T0, M-1]; every such
+        // minimum is <= the entry's hash, so the test is "sliding maximum of the (masked) window minima == hash", doubled the same way
+        if (M > T0) {
+            {
+                // in place: every thread rewrites its own elements
+#pragma unroll
+                for (int c = 0; c < SKF_V; c++) {
+                    const int i = tid + 256 * c, t = t0 + i;
+                    if (i < NW && !(t >= T0 && t <= M - 1 && i < SKF_T + w - 1)) { s_wmin[i] = 0ull; v[c] = 0ull; }
+                }
+                __syncthreads();
+            }
+            if (w > 1) {
+                for (int d = 1; d < p2; d <<= 1) pass(s_wmin, d, true);
+                if (w > p2) pass(s_wmin, w - p2, true);
+            }
+        }
+        for (int pi = tid; pi < SKF_T; pi += 256) {
+            const int p = t0 + pi;
+            if (p >= M) break;
+            const uint64_t hp = s_h[pi + (w - 1)];
+            if (hp == NONE) continue;
+            bool e;
+            if (M <= T0) e = (p == s_short);
+            else {
+                e = (p + w - 1 >= T0) && s_wmin[pi] == hp;
+                if (p >= T0 - w + 1 && p <= T0 - 1 && s_am != NONE && hp == s_am) e = (p != s_abest) ? true : (s_ah > s_am);
+            }
+            if (e) emit(p);
+        }
+        __syncthreads();
+    }
+}
+
+} // namespace
