@@ -830,13 +830,27 @@ __global__ __launch_bounds__(256) void k_nw_any(const uint32_t *__restrict__ sto
 
 // ------------------------------------------------------------------------------------------------ host side
 struct AlnWs {
-    DevBuf store, nmask, ascii, asc_off, word_off, len, wper, pair_q, pair_t, sk_ends, sk_low, sk_high, mz, mz_off, mz_cnt, warn, chain, hdr, events, ev_packed, ev_count, tasks, bt, rows, cg, cg_n, scores, gaps, gap_shift, thin, box_src, corner, corner_out;
+    Dev<uint32_t> store, word_off, pair_q, pair_t, sk_ends, sk_low, sk_high, mz_off, mz_cnt, warn, ev_count, cg, cg_n;
+    Dev<uint32_t> nmask;      // FSV_NM_LEAD lead words (the first: "some window has an N"), then a mask word per store word
+    Dev<int32_t> len, rows, scores, gap_shift;
+    Dev<char> ascii;
+    Dev<uint64_t> asc_off, chain;
+    Dev<uint8_t> wper, bt;
+    Dev<uint16_t> thin;
+    Dev<fsv_mz> mz;
+    Dev<AlnHeader> hdr;
+    Dev<AlnEvent> events, ev_packed;
+    Dev<NwTask> tasks;
+    Dev<GapQuery> gaps;
+    Dev<BoxSrc> box_src;
+    Dev<CornerTask> corner;
+    Dev<int2> corner_out;
     fsv_aln_stats stats;
     // the size classes of the event DP run side by side: a class is a handful of long-running blocks, never a full chip
     hipStream_t side[3] = {nullptr, nullptr, nullptr};
     hipEvent_t fork = nullptr, join[3] = {nullptr, nullptr, nullptr};
     AlnWs *sub = nullptr;       // the workspace of the boxes of oversize events (a second, smaller alignment pass)
-    const uint32_t *nm() const { return (const uint32_t *)nmask.p + FSV_NM_LEAD; }     // the N mask of the store (the kernels drop it when the batch has no N: nm_active)
+    const uint32_t *nm() const { return nmask.p + FSV_NM_LEAD; }     // the N mask of the store (the kernels drop it when the batch has no N: nm_active)
 };
 
 void aln_ws_release(AlnWs *w)
@@ -913,24 +927,22 @@ int pack_pairs(fsv_ctx *ctx, AlnWs &W, const std::vector<const char *> &seq, con
     // sequences dev_first.. are already on the device, back to back at dev_src (contigs of the last assembly): one D2D copy
     const uint32_t n_host = dev_src ? dev_first : n;
     if (dev_src && n > dev_first)
-        FSV_HIP(ctx, hipMemcpyAsync((char *)W.ascii.p + asc_off[dev_first], dev_src, asc_off[n] - asc_off[dev_first], hipMemcpyDeviceToDevice, ctx->stream));
+        FSV_HIP(ctx, hipMemcpyAsync(W.ascii.p + asc_off[dev_first], dev_src, asc_off[n] - asc_off[dev_first], hipMemcpyDeviceToDevice, ctx->stream));
     for (uint32_t r = 0; r < n_host;) {
         uint32_t e = r + 1;
         while (e < n_host && seq[e] == seq[e - 1] + slen[e - 1]) e++;
-        FSV_HIP(ctx, hipMemcpyAsync((char *)W.ascii.p + asc_off[r], seq[r], asc_off[e] - asc_off[r], hipMemcpyHostToDevice, ctx->stream));
+        FSV_HIP(ctx, hipMemcpyAsync(W.ascii.p + asc_off[r], seq[r], asc_off[e] - asc_off[r], hipMemcpyHostToDevice, ctx->stream));
         r = e;
     }
     TRY(upload(ctx, W.asc_off, asc_off));
     TRY(upload(ctx, W.word_off, word_off));
     TRY(upload(ctx, W.len, len));
-    TRY(ensure(ctx, W.store, (w + 8) * 4));
-    FSV_HIP(ctx, hipMemsetAsync((uint32_t *)W.store.p + w, 0, 32, ctx->stream));
-    TRY(ensure(ctx, W.nmask, (w + 8 + FSV_NM_LEAD) * 4));
-    FSV_HIP(ctx, hipMemsetAsync(W.nmask.p, 0, FSV_NM_LEAD * 4, ctx->stream));      // the "some window has an N" word (set on the device: the host never looks at the text)
-    FSV_HIP(ctx, hipMemsetAsync((uint32_t *)W.nmask.p + FSV_NM_LEAD + w, 0, 32, ctx->stream));
-    hipLaunchKernelGGL(k_pack_ascii, dim3(fsv_grid_for(w, 256)), dim3(256), 0, ctx->stream, (const char *)W.ascii.p, (const uint64_t *)W.asc_off.p,
-                       (const uint32_t *)W.word_off.p, (const int32_t *)W.len.p, n, (uint32_t)w, (uint32_t *)W.store.p, (uint32_t *)W.nmask.p + FSV_NM_LEAD);
-    FSV_HIP(ctx, hipGetLastError());
+    TRY(ensure(ctx, W.store, w + 8));
+    FSV_HIP(ctx, hipMemsetAsync(W.store.p + w, 0, 32, ctx->stream));
+    TRY(ensure(ctx, W.nmask, w + 8 + FSV_NM_LEAD));
+    TRY(zero(ctx, W.nmask, FSV_NM_LEAD));      // the "some window has an N" word (set on the device: the host never looks at the text)
+    FSV_HIP(ctx, hipMemsetAsync(W.nmask.p + FSV_NM_LEAD + w, 0, 32, ctx->stream));
+    FSV_LAUNCH(ctx, ctx->stream, k_pack_ascii, dim3(fsv_grid_for(w, 256)), dim3(256), 0, W.ascii.p, W.asc_off.p, W.word_off.p, W.len.p, n, (uint32_t)w, W.store.p, W.nmask.p + FSV_NM_LEAD);
     return FSV_OK;
 }
 
@@ -955,10 +967,10 @@ int run_nw(fsv_ctx *ctx, AlnWs &W, const std::vector<NwTask> &tasks, uint64_t bt
     for (size_t i = 0; i < n; i++) { sorted[i] = tasks[order[i]]; sorted[i].cg_off = order[i] * (uint32_t)ALN_CG_CAP; sorted[i].out_idx = order[i]; }
     TRY(upload(ctx, W.tasks, sorted));
     TRY(ensure(ctx, W.bt, bt_bytes + 16));
-    TRY(ensure(ctx, W.rows, row_words * 4 + 16));
-    TRY(ensure(ctx, W.cg, n * (size_t)ALN_CG_CAP * 4));
-    TRY(ensure(ctx, W.cg_n, n * 4));
-    TRY(ensure(ctx, W.scores, n * 4));
+    TRY(ensure(ctx, W.rows, row_words + 4));
+    TRY(ensure(ctx, W.cg, n * (size_t)ALN_CG_CAP));
+    TRY(ensure(ctx, W.cg_n, n));
+    TRY(ensure(ctx, W.scores, n));
     if (!W.fork) {
         FSV_HIP(ctx, hipEventCreateWithFlags(&W.fork, hipEventDisableTiming));
         for (int i = 0; i < 3; i++) {
@@ -973,28 +985,13 @@ int run_nw(fsv_ctx *ctx, AlnWs &W, const std::vector<NwTask> &tasks, uint64_t bt
     for (int c = 1; c < 4; c++)
         if (cls_end[c] > cls_end[c - 1]) { used[c] = true; FSV_HIP(ctx, hipStreamWaitEvent(W.side[c - 1], W.fork, 0)); }
     if (cls_end[0])
-        hipLaunchKernelGGL((k_nw<256, 64>), dim3((uint32_t)cls_end[0]), dim3(64), 0, lane(0), (const uint32_t *)W.store.p, W.nm(), (const uint32_t *)W.word_off.p,
-                           (const int32_t *)W.len.p, (const uint32_t *)W.pair_q.p, (const uint32_t *)W.pair_t.p, (const AlnHeader *)W.hdr.p,
-                           (const NwTask *)W.tasks.p, (uint8_t *)W.bt.p, (uint32_t *)W.cg.p, (uint32_t *)W.cg_n.p, (int32_t *)W.scores.p, P);
-    FSV_HIP(ctx, hipGetLastError());
+        FSV_LAUNCH(ctx, lane(0), (k_nw<256, 64>), dim3((uint32_t)cls_end[0]), dim3(64), 0, W.store.p, W.nm(), W.word_off.p, W.len.p, W.pair_q.p, W.pair_t.p, W.hdr.p, W.tasks.p, W.bt.p, W.cg.p, W.cg_n.p, W.scores.p, P);
     if (used[1])
-        hipLaunchKernelGGL((k_nw<NW_LDS_Q, 1024>), dim3((uint32_t)(cls_end[1] - cls_end[0])), dim3(1024), 0, lane(1), (const uint32_t *)W.store.p, W.nm(),
-                           (const uint32_t *)W.word_off.p, (const int32_t *)W.len.p, (const uint32_t *)W.pair_q.p, (const uint32_t *)W.pair_t.p,
-                           (const AlnHeader *)W.hdr.p, (const NwTask *)W.tasks.p + cls_end[0], (uint8_t *)W.bt.p, (uint32_t *)W.cg.p,
-                           (uint32_t *)W.cg_n.p, (int32_t *)W.scores.p, P);
-    FSV_HIP(ctx, hipGetLastError());
+        FSV_LAUNCH(ctx, lane(1), (k_nw<NW_LDS_Q, 1024>), dim3((uint32_t)(cls_end[1] - cls_end[0])), dim3(1024), 0, W.store.p, W.nm(), W.word_off.p, W.len.p, W.pair_q.p, W.pair_t.p, W.hdr.p, W.tasks.p + cls_end[0], W.bt.p, W.cg.p, W.cg_n.p, W.scores.p, P);
     if (used[2])
-        hipLaunchKernelGGL(k_nw_any, dim3((uint32_t)(cls_end[2] - cls_end[1])), dim3(256), 0, lane(2), (const uint32_t *)W.store.p, W.nm(),
-                           (const uint32_t *)W.word_off.p, (const int32_t *)W.len.p, (const uint32_t *)W.pair_q.p, (const uint32_t *)W.pair_t.p,
-                           (const AlnHeader *)W.hdr.p, (const NwTask *)W.tasks.p + cls_end[1], (uint8_t *)W.bt.p, (int32_t *)W.rows.p, (uint32_t *)W.cg.p,
-                           (uint32_t *)W.cg_n.p, (int32_t *)W.scores.p, P);
-    FSV_HIP(ctx, hipGetLastError());
+        FSV_LAUNCH(ctx, lane(2), k_nw_any, dim3((uint32_t)(cls_end[2] - cls_end[1])), dim3(256), 0, W.store.p, W.nm(), W.word_off.p, W.len.p, W.pair_q.p, W.pair_t.p, W.hdr.p, W.tasks.p + cls_end[1], W.bt.p, W.rows.p, W.cg.p, W.cg_n.p, W.scores.p, P);
     if (used[3])
-        hipLaunchKernelGGL((k_nw_rows<256, 64>), dim3((uint32_t)(cls_end[3] - cls_end[2])), dim3(64), 0, lane(3), (const uint32_t *)W.store.p, W.nm(),
-                           (const uint32_t *)W.word_off.p, (const int32_t *)W.len.p, (const uint32_t *)W.pair_q.p, (const uint32_t *)W.pair_t.p,
-                           (const AlnHeader *)W.hdr.p, (const NwTask *)W.tasks.p + cls_end[2], (uint8_t *)W.bt.p, (uint32_t *)W.cg.p,
-                           (uint32_t *)W.cg_n.p, (int32_t *)W.scores.p, P);
-    FSV_HIP(ctx, hipGetLastError());
+        FSV_LAUNCH(ctx, lane(3), (k_nw_rows<256, 64>), dim3((uint32_t)(cls_end[3] - cls_end[2])), dim3(64), 0, W.store.p, W.nm(), W.word_off.p, W.len.p, W.pair_q.p, W.pair_t.p, W.hdr.p, W.tasks.p + cls_end[2], W.bt.p, W.cg.p, W.cg_n.p, W.scores.p, P);
     for (int c = 1; c < 4; c++)
         if (used[c]) { FSV_HIP(ctx, hipEventRecord(W.join[c - 1], W.side[c - 1])); FSV_HIP(ctx, hipStreamWaitEvent(ctx->stream, W.join[c - 1], 0)); }
     return FSV_OK;
@@ -1054,83 +1051,51 @@ int align_pass(fsv_ctx *ctx, AlnWs &W, const PassIn &S, const fsv_aln_params &P,
     if (m >= (1ull << 32)) return fsv_fail(ctx, FSV_EUNSUP, "alignment batch too large; split it");
     mz_off[nr] = (uint32_t)m;
     TRY(upload(ctx, W.mz_off, mz_off));
-    TRY(ensure(ctx, W.mz, m * sizeof(fsv_mz)));
-    TRY(ensure(ctx, W.mz_cnt, (size_t)nr * 4));
-    TRY(ensure(ctx, W.warn, (size_t)nr * 4));
-    FSV_HIP(ctx, hipMemsetAsync(W.warn.p, 0, (size_t)nr * 4, ctx->stream));
-    FSV_HIP(ctx, hipMemsetAsync(W.mz_cnt.p, 0, (size_t)nr * 4, ctx->stream));
-    if (P.k & 1) {
-        const size_t total_words = word_off[nr];
-        TRY(ensure(ctx, W.sk_ends, (total_words * 16 + 64) * 4));
-        TRY(ensure(ctx, W.sk_low, (total_words + nr + 8) * 4));
-        TRY(ensure(ctx, W.sk_high, (total_words + nr + 8) * 4));
-        FSV_HIP(ctx, hipMemsetAsync(W.sk_low.p, 0, (total_words + nr + 8) * 4, ctx->stream));
-        FSV_HIP(ctx, hipMemsetAsync(W.sk_high.p, 0, (total_words + nr + 8) * 4, ctx->stream));
-        hipLaunchKernelGGL(k_sketch_fast, dim3(nr), dim3(256), 0, ctx->stream, (const uint32_t *)W.store.p, (const uint32_t *)W.word_off.p,
-                           (const int32_t *)W.len.p, (const uint32_t *)W.mz_off.p, (fsv_mz *)W.mz.p, (uint32_t *)W.mz_cnt.p, nr, P.w, P.k, 0,
-                           (uint32_t *)W.warn.p, (const uint8_t *)W.wper.p, (uint32_t *)W.sk_ends.p, (uint32_t *)W.sk_low.p, (uint32_t *)W.sk_high.p,
-                           (const uint32_t *)nullptr);
-    } else {
-        uint32_t max_words = 1; int w_max = 1;
+    TRY(ensure(ctx, W.mz, m));
+    TRY(ensure(ctx, W.mz_cnt, nr));
+    TRY(ensure(ctx, W.warn, nr));
+    TRY(zero(ctx, W.warn, nr));
+    uint32_t max_words = 1; int w_max = 1;      // (the replay kernel's LDS tile: even k only)
+    if (!(P.k & 1))
         for (uint32_t r = 0; r < nr; r++) { max_words = std::max<uint32_t>(max_words, (uint32_t)((len[r] + 15) / 16)); w_max = std::max<int>(w_max, S.wper[r]); }
-        const uint32_t lds_words = std::min<uint32_t>(max_words, 8192u);
-        FSV_HIP(ctx, hipFuncSetAttribute((const void *)k_sketch, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sketch_lds_bytes(w_max, lds_words)));
-        hipLaunchKernelGGL(k_sketch, dim3(nr), dim3(64), sketch_lds_bytes(w_max, lds_words), ctx->stream, (const uint32_t *)W.store.p,
-                           (const uint32_t *)W.word_off.p, (const int32_t *)W.len.p, (const uint32_t *)W.mz_off.p, (fsv_mz *)W.mz.p,
-                           (uint32_t *)W.mz_cnt.p, nr, P.w, P.k, 0, (uint32_t *)W.warn.p, (const uint8_t *)W.wper.p, w_max, lds_words);
-    }
-    FSV_HIP(ctx, hipGetLastError());
+    TRY(launch_sketch(ctx, W, SketchJob{W.store.p, nr, word_off[nr], max_words, P.w, P.k, 0, W.wper.p, w_max, false, nullptr}));
     bool any_thin = false;
     for (uint32_t r = 0; r < nr; r++) any_thin |= S.thin[r] > 1;
     if (any_thin) {
         TRY(upload(ctx, W.thin, S.thin));
-        hipLaunchKernelGGL(k_thin_seeds, dim3(nr), dim3(256), 0, ctx->stream, (fsv_mz *)W.mz.p, (const uint32_t *)W.mz_off.p, (uint32_t *)W.mz_cnt.p,
-                           (const uint16_t *)W.thin.p);
-        FSV_HIP(ctx, hipGetLastError());
+        FSV_LAUNCH(ctx, ctx->stream, k_thin_seeds, dim3(nr), dim3(256), 0, W.mz.p, W.mz_off.p, W.mz_cnt.p, W.thin.p);
     }
     // first pass: seeds unique in their sequence; boxes: seeds that occur at most twice in their side
-    hipLaunchKernelGGL(k_uniq<ALN_AMAX>, dim3(nr), dim3(256), 0, ctx->stream, (fsv_mz *)W.mz.p, (const uint32_t *)W.mz_off.p, (uint32_t *)W.mz_cnt.p,
-                       (uint32_t *)W.warn.p, (const uint32_t *)nullptr, 0u, 0xffffffffu, (unsigned long long *)nullptr, depth == 0 ? 1u : (uint32_t)ALN_SUB_OCC);
-    FSV_HIP(ctx, hipGetLastError());
+    FSV_LAUNCH(ctx, ctx->stream, k_uniq<ALN_AMAX>, dim3(nr), dim3(256), 0, W.mz.p, W.mz_off.p, W.mz_cnt.p, W.warn.p, (const uint32_t *)nullptr, 0u, 0xffffffffu, (unsigned long long *)nullptr, depth == 0 ? 1u : (uint32_t)ALN_SUB_OCC);
     trace("sketch+uniq");
     if (stats) stats->ms_seed = tseed.stop();
     Timer tchain(ctx);
-    TRY(ensure(ctx, W.chain, (size_t)ns * ALN_CHAIN_STRIDE * 8));
-    TRY(ensure(ctx, W.hdr, (size_t)ns * sizeof(AlnHeader)));
-    TRY(ensure(ctx, W.events, (size_t)ns * ALN_EV_CAP * sizeof(AlnEvent)));
+    TRY(ensure(ctx, W.chain, (size_t)ns * ALN_CHAIN_STRIDE));
+    TRY(ensure(ctx, W.hdr, ns));
+    TRY(ensure(ctx, W.events, (size_t)ns * ALN_EV_CAP));
     if (depth == 0)
-        hipLaunchKernelGGL(k_chain_aln<false>, dim3(np), dim3(64), 0, ctx->stream, (const int32_t *)W.len.p,
-                           (const fsv_mz *)W.mz.p, (const uint32_t *)W.mz_off.p, (const uint32_t *)W.mz_cnt.p, (const uint32_t *)W.pair_q.p,
-                           (const uint32_t *)W.pair_t.p, (uint64_t *)W.chain.p, (AlnHeader *)W.hdr.p, R, P);
+        FSV_LAUNCH(ctx, ctx->stream, k_chain_aln<false>, dim3(np), dim3(64), 0, W.len.p, W.mz.p, W.mz_off.p, W.mz_cnt.p, W.pair_q.p, W.pair_t.p, W.chain.p, W.hdr.p, R, P);
     else
-        hipLaunchKernelGGL(k_chain_aln<true>, dim3(np), dim3(64), 0, ctx->stream, (const int32_t *)W.len.p,
-                           (const fsv_mz *)W.mz.p, (const uint32_t *)W.mz_off.p, (const uint32_t *)W.mz_cnt.p, (const uint32_t *)W.pair_q.p,
-                           (const uint32_t *)W.pair_t.p, (uint64_t *)W.chain.p, (AlnHeader *)W.hdr.p, R, P);
-    FSV_HIP(ctx, hipGetLastError());
+        FSV_LAUNCH(ctx, ctx->stream, k_chain_aln<true>, dim3(np), dim3(64), 0, W.len.p, W.mz.p, W.mz_off.p, W.mz_cnt.p, W.pair_q.p, W.pair_t.p, W.chain.p, W.hdr.p, R, P);
     trace("chain");
     if (stats) stats->ms_chain = tchain.stop();
     Timer tev(ctx);
-    TRY(ensure(ctx, W.ev_packed, (size_t)ns * ALN_EV_CAP * sizeof(AlnEvent)));
-    TRY(ensure(ctx, W.ev_count, 16));
-    FSV_HIP(ctx, hipMemsetAsync(W.ev_count.p, 0, 4, ctx->stream));
+    TRY(ensure(ctx, W.ev_packed, (size_t)ns * ALN_EV_CAP));
+    TRY(ensure(ctx, W.ev_count, 4));
+    TRY(zero(ctx, W.ev_count, 1));
     if (depth == 0)
-        hipLaunchKernelGGL(k_aln_events<false>, dim3(ns), dim3(256), 0, ctx->stream, (const uint32_t *)W.store.p, W.nm(), (const uint32_t *)W.word_off.p,
-                           (const int32_t *)W.len.p, (const uint32_t *)W.pair_q.p, (const uint32_t *)W.pair_t.p, (const uint64_t *)W.chain.p,
-                           (AlnHeader *)W.hdr.p, (AlnEvent *)W.events.p, (AlnEvent *)W.ev_packed.p, (uint32_t *)W.ev_count.p, P);
+        FSV_LAUNCH(ctx, ctx->stream, k_aln_events<false>, dim3(ns), dim3(256), 0, W.store.p, W.nm(), W.word_off.p, W.len.p, W.pair_q.p, W.pair_t.p, W.chain.p, W.hdr.p, W.events.p, W.ev_packed.p, W.ev_count.p, P);
     else
-        hipLaunchKernelGGL(k_aln_events<true>, dim3(ns), dim3(256), 0, ctx->stream, (const uint32_t *)W.store.p, W.nm(), (const uint32_t *)W.word_off.p,
-                           (const int32_t *)W.len.p, (const uint32_t *)W.pair_q.p, (const uint32_t *)W.pair_t.p, (const uint64_t *)W.chain.p,
-                           (AlnHeader *)W.hdr.p, (AlnEvent *)W.events.p, (AlnEvent *)W.ev_packed.p, (uint32_t *)W.ev_count.p, P);
-    FSV_HIP(ctx, hipGetLastError());
+        FSV_LAUNCH(ctx, ctx->stream, k_aln_events<true>, dim3(ns), dim3(256), 0, W.store.p, W.nm(), W.word_off.p, W.len.p, W.pair_q.p, W.pair_t.p, W.chain.p, W.hdr.p, W.events.p, W.ev_packed.p, W.ev_count.p, P);
     std::vector<AlnHeader> &hdr = O.hdr;
     hdr.assign(ns, AlnHeader());
     uint32_t n_ev = 0;
-    FSV_HIP(ctx, hipMemcpyAsync(hdr.data(), W.hdr.p, (size_t)ns * sizeof(AlnHeader), hipMemcpyDeviceToHost, ctx->stream));
-    FSV_HIP(ctx, hipMemcpyAsync(&n_ev, W.ev_count.p, 4, hipMemcpyDeviceToHost, ctx->stream));
+    TRY(download(ctx, hdr.data(), W.hdr, ns));
+    TRY(download(ctx, &n_ev, W.ev_count, 1));
     FSV_HIP(ctx, hipStreamSynchronize(ctx->stream));
     std::vector<AlnEvent> events(n_ev);
     if (n_ev) {
-        FSV_HIP(ctx, hipMemcpyAsync(events.data(), W.ev_packed.p, (size_t)n_ev * sizeof(AlnEvent), hipMemcpyDeviceToHost, ctx->stream));
+        TRY(download(ctx, events.data(), W.ev_packed, n_ev));
         FSV_HIP(ctx, hipStreamSynchronize(ctx->stream));
     }
     trace("events");
@@ -1171,14 +1136,14 @@ int align_pass(fsv_ctx *ctx, AlnWs &W, const PassIn &S, const fsv_aln_params &P,
     if (!tasks.empty()) {
         if (tasks.size() * (uint64_t)ALN_CG_CAP >= (1ull << 32)) return fsv_fail(ctx, FSV_EUNSUP, "too many DP events in one batch");
         TRY(run_nw(ctx, W, tasks, bt, rows, P));
-        FSV_HIP(ctx, hipMemcpyAsync(cg_n.data(), W.cg_n.p, tasks.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
+        TRY(download(ctx, cg_n.data(), W.cg_n, tasks.size()));
         FSV_HIP(ctx, hipMemcpy2DAsync(cg_head.data(), CG_HEAD * 4, W.cg.p, (size_t)ALN_CG_CAP * 4, CG_HEAD * 4, tasks.size(), hipMemcpyDeviceToHost, ctx->stream));
         FSV_HIP(ctx, hipStreamSynchronize(ctx->stream));
         bool any = false;
         for (size_t t = 0; t < tasks.size(); t++)
             if (cg_n[t] != 0xffffffffu && cg_n[t] > CG_HEAD) {
                 cg_long[t].resize(cg_n[t]);
-                FSV_HIP(ctx, hipMemcpyAsync(cg_long[t].data(), (const uint32_t *)W.cg.p + t * (size_t)ALN_CG_CAP, (size_t)cg_n[t] * 4, hipMemcpyDeviceToHost, ctx->stream));
+                FSV_HIP(ctx, hipMemcpyAsync(cg_long[t].data(), W.cg.p + t * (size_t)ALN_CG_CAP, (size_t)cg_n[t] * 4, hipMemcpyDeviceToHost, ctx->stream));
                 any = true;
             }
         if (any) FSV_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -1212,13 +1177,11 @@ int align_pass(fsv_ctx *ctx, AlnWs &W, const PassIn &S, const fsv_aln_params &P,
         TRY(upload(ctx, W2.word_off, S2.word_off));
         TRY(upload(ctx, W2.len, S2.len));
         TRY(upload(ctx, W2.box_src, src));
-        TRY(ensure(ctx, W2.store, (w + 8) * 4));
-        FSV_HIP(ctx, hipMemsetAsync((uint32_t *)W2.store.p + w, 0, 32, ctx->stream));
-        TRY(ensure(ctx, W2.nmask, (w + 8 + FSV_NM_LEAD) * 4));
-        FSV_HIP(ctx, hipMemsetAsync((uint32_t *)W2.nmask.p + FSV_NM_LEAD + w, 0, 32, ctx->stream));
-        hipLaunchKernelGGL(k_extract_boxes, dim3(fsv_grid_for(w, 256)), dim3(256), 0, ctx->stream, (const uint32_t *)W.store.p, W.nm(), (const BoxSrc *)W2.box_src.p,
-                           (const uint32_t *)W2.word_off.p, (const int32_t *)W2.len.p, 2 * nb, (uint32_t)w, (uint32_t *)W2.store.p, (uint32_t *)W2.nmask.p + FSV_NM_LEAD);
-        FSV_HIP(ctx, hipGetLastError());
+        TRY(ensure(ctx, W2.store, w + 8));
+        FSV_HIP(ctx, hipMemsetAsync(W2.store.p + w, 0, 32, ctx->stream));
+        TRY(ensure(ctx, W2.nmask, w + 8 + FSV_NM_LEAD));
+        FSV_HIP(ctx, hipMemsetAsync(W2.nmask.p + FSV_NM_LEAD + w, 0, 32, ctx->stream));
+        FSV_LAUNCH(ctx, ctx->stream, k_extract_boxes, dim3(fsv_grid_for(w, 256)), dim3(256), 0, W.store.p, W.nm(), W2.box_src.p, W2.word_off.p, W2.len.p, 2 * nb, (uint32_t)w, W2.store.p, W2.nmask.p + FSV_NM_LEAD);
         PassOut O2;
         TRY(align_pass(ctx, W2, S2, P, 1, O2, nullptr));
         for (uint32_t b = 0; b < nb; b++) {
@@ -1232,12 +1195,9 @@ int align_pass(fsv_ctx *ctx, AlnWs &W, const PassIn &S, const fsv_aln_params &P,
         for (size_t b = 0; b < bigs.size(); b++) ct[b] = CornerTask{bigs[b].slot, bigs[b].qs, bigs[b].qe - bigs[b].qs + 1, bigs[b].ts, bigs[b].te - bigs[b].ts + 1};
         std::vector<int2> lr(bigs.size());
         TRY(upload(ctx, W.corner, ct));
-        TRY(ensure(ctx, W.corner_out, bigs.size() * sizeof(int2)));
-        hipLaunchKernelGGL(k_corner, dim3((uint32_t)bigs.size()), dim3(64), 0, ctx->stream, (const uint32_t *)W.store.p, W.nm(), (const uint32_t *)W.word_off.p,
-                           (const int32_t *)W.len.p, (const uint32_t *)W.pair_q.p, (const uint32_t *)W.pair_t.p, (const AlnHeader *)W.hdr.p,
-                           (const CornerTask *)W.corner.p, (int2 *)W.corner_out.p, P);
-        FSV_HIP(ctx, hipGetLastError());
-        FSV_HIP(ctx, hipMemcpyAsync(lr.data(), W.corner_out.p, bigs.size() * sizeof(int2), hipMemcpyDeviceToHost, ctx->stream));
+        TRY(ensure(ctx, W.corner_out, bigs.size()));
+        FSV_LAUNCH(ctx, ctx->stream, k_corner, dim3((uint32_t)bigs.size()), dim3(64), 0, W.store.p, W.nm(), W.word_off.p, W.len.p, W.pair_q.p, W.pair_t.p, W.hdr.p, W.corner.p, W.corner_out.p, P);
+        TRY(download(ctx, lr.data(), W.corner_out, bigs.size()));
         FSV_HIP(ctx, hipStreamSynchronize(ctx->stream));
         for (size_t b = 0; b < bigs.size(); b++) {
             const int ql = ct[b].ql, tl = ct[b].tl, l = lr[b].x, r = lr[b].y;
@@ -1320,11 +1280,11 @@ static int nw_impl(fsv_ctx *ctx, const char *target, int32_t tl, const char *que
     tasks[0] = NwTask{0u, 0, ql, 0, tl, 0u, 0ull, 0ull, 0u, 0u};
     TRY(run_nw(ctx, W, tasks, nw_bt_bytes(ql, tl), nw_class(ql, tl) == 2 ? 11ull * ql : 0, P));
     uint32_t n = 0; int32_t sc = 0;
-    FSV_HIP(ctx, hipMemcpyAsync(&n, W.cg_n.p, 4, hipMemcpyDeviceToHost, ctx->stream));
-    FSV_HIP(ctx, hipMemcpyAsync(&sc, W.scores.p, 4, hipMemcpyDeviceToHost, ctx->stream));
+    TRY(download(ctx, &n, W.cg_n, 1));
+    TRY(download(ctx, &sc, W.scores, 1));
     FSV_HIP(ctx, hipStreamSynchronize(ctx->stream));
     if (n == 0xffffffffu || n > cigar_cap) return FSV_ECAP;
-    FSV_HIP(ctx, hipMemcpyAsync(cigar, W.cg.p, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    TRY(download(ctx, cigar, W.cg, n));
     FSV_HIP(ctx, hipStreamSynchronize(ctx->stream));
     *n_cigar = n; *score = sc;
     return FSV_OK;
@@ -1426,12 +1386,9 @@ static int align_batch_impl(fsv_ctx *ctx, const char *contig_seq, const uint64_t
     std::vector<int32_t> max_shift(gaps.size());
     if (!gaps.empty()) {
         TRY(upload(ctx, W.gaps, gaps));
-        TRY(ensure(ctx, W.gap_shift, gaps.size() * 4));
-        hipLaunchKernelGGL(k_gap_shift, dim3((uint32_t)gaps.size()), dim3(64), 0, ctx->stream, (const uint32_t *)W.store.p, W.nm(), (const uint32_t *)W.word_off.p,
-                           (const int32_t *)W.len.p, (const uint32_t *)W.pair_q.p, (const uint32_t *)W.pair_t.p, (const AlnHeader *)W.hdr.p,
-                           (const GapQuery *)W.gaps.p, (int32_t *)W.gap_shift.p);
-        FSV_HIP(ctx, hipGetLastError());
-        FSV_HIP(ctx, hipMemcpyAsync(max_shift.data(), W.gap_shift.p, gaps.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
+        TRY(ensure(ctx, W.gap_shift, gaps.size()));
+        FSV_LAUNCH(ctx, ctx->stream, k_gap_shift, dim3((uint32_t)gaps.size()), dim3(64), 0, W.store.p, W.nm(), W.word_off.p, W.len.p, W.pair_q.p, W.pair_t.p, W.hdr.p, W.gaps.p, W.gap_shift.p);
+        TRY(download(ctx, max_shift.data(), W.gap_shift, gaps.size()));
         FSV_HIP(ctx, hipStreamSynchronize(ctx->stream));
     }
     {

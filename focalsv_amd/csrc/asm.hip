@@ -17,6 +17,14 @@
 
 namespace {
 
+enum { KN_SKETCH, KN_UNIQ, KN_CHAIN, KN_BPM, KN_RESCUE, KN_PATH_FAST, KN_PATH_DP, KN_CONSENSUS, KN_REPACK, KN_EXACT, KN_STITCH, KN_PARTITION, KN_BND, KN_BND_CONS, KN_COUNT,
+       ST_SKETCH = KN_COUNT, ST_CHAIN, ST_VERIFY, ST_PATH, ST_CONSENSUS, ST_FINAL };
+const char *const kn_names[KN_COUNT] = {"k_sketch", "k_uniq", "k_chain", "k5_bpm", "k_rescue_accept", "k_path_fast", "k_path_dp", "k_consensus",
+                                        "k_repack", "k_exact", "k_stitch", "k_partition", "k_bnd_tasks", "k_bnd_consensus"};
+// the task lists of a round: its window tasks, the junction tasks of its second consensus pass, the junction cigars of its partition
+// (PASS_NONE: a list outside a batch -- fsv_bpm_paths).  Pass p of round r keeps its device counters in row p (n_rounds + 1) + r.
+enum { PASS_NONE = -1, PASS_WINDOWS, PASS_JUNCTIONS, PASS_BCIG, PASS_COUNT };
+
 // HIP-event timing of kernels and of whole stages on the context's stream: recorded while the work is queued, resolved once
 // at the end of the batch -- nothing here waits for the GPU (round 1's stage timers synchronised the stream twice each)
 struct KTimes {
@@ -24,17 +32,17 @@ struct KTimes {
     std::vector<Rec> recs;
     std::vector<hipEvent_t> pool;
     size_t used = 0;
+    // the records whose byte counts are only known when the batch ends: (pass, kernel) -> record index, one per round in order
+    std::vector<size_t> by[PASS_COUNT][KN_COUNT];
     hipEvent_t get() { if (used == pool.size()) { hipEvent_t e; (void)hipEventCreate(&e); pool.push_back(e); } return pool[used++]; }
     size_t begin(fsv_ctx *ctx, int k, uint64_t bytes) { Rec r{k, get(), get(), bytes}; (void)hipEventRecord(r.a, ctx->stream); recs.push_back(r); return recs.size() - 1; }
+    void begin(fsv_ctx *ctx, int pass, int k, uint64_t bytes) { const size_t i = begin(ctx, k, bytes); if (pass != PASS_NONE) by[pass][k].push_back(i); }
     void end(fsv_ctx *ctx) { (void)hipEventRecord(recs.back().b, ctx->stream); }
     void end(fsv_ctx *ctx, size_t idx) { (void)hipEventRecord(recs[idx].b, ctx->stream); }
-    void reset() { recs.clear(); used = 0; }
+    uint64_t *bytes_of(int pass, int k, size_t round) { const auto &v = by[pass][k]; return round < v.size() ? &recs[v[round]].bytes : nullptr; }
+    void reset() { recs.clear(); used = 0; for (auto &p : by) for (auto &v : p) v.clear(); }
     ~KTimes() { for (auto e : pool) (void)hipEventDestroy(e); }
 };
-enum { KN_SKETCH, KN_UNIQ, KN_CHAIN, KN_BPM, KN_RESCUE, KN_PATH_FAST, KN_PATH_DP, KN_CONSENSUS, KN_REPACK, KN_EXACT, KN_STITCH, KN_PARTITION, KN_BND, KN_BND_CONS, KN_COUNT,
-       ST_SKETCH = KN_COUNT, ST_CHAIN, ST_VERIFY, ST_PATH, ST_CONSENSUS, ST_FINAL };
-const char *const kn_names[KN_COUNT] = {"k_sketch", "k_uniq", "k_chain", "k5_bpm", "k_rescue_accept", "k_path_fast", "k_path_dp", "k_consensus",
-                                        "k_repack", "k_exact", "k_stitch", "k_partition", "k_bnd_tasks", "k_bnd_consensus"};
 
 // a stage: from construction to stop(), in stream order
 struct Span {
@@ -53,13 +61,27 @@ enum { CT_TASKS = 0, CT_OVERFLOW = 1, CT_DP = 2, CT_INEXACT = 3, CT_COLS_LO = 4,
        CT_FIX = 22, CT_FIXED = 23,   // fix_boundary's candidates (k_path_fast) and the windows it moved
        CT_SLOT = 24 };      // even: the 64-bit sums stay aligned in every slot
 
+template <class... Ts> size_t cap_sum(const Ts &...b) { return (b.cap + ... + 0); }
+
 struct AsmWs {
-    DevBuf store[2], cols_sb, contig_all, word_off, len, set_start, read_set, pair_base, mz, mz_off, mz_cnt, ovl, tasks, res, paths, counters, dp_list, dp_list2, dp_list3, dp_list16, dp_list_e3, dp_wide, dp_xwide, cols_wide, set_cols, site_cnt, site_rec, site_off, site_vec, site_cursor, redo, site_lists, read_dirty, cov3, lb, sr_store, brel_off, tasks2, res2, paths2, idx2, bc_idx, bc_rec, bc_win, left_list, fix_list, tasks3, res3, src3, bnd_flag, bnd_list, bnd_patch, bnd_bytes, changed, pair_read, wide_list,
-        cols, tmp, gwin_off, gwin_read, sk_ends, sk_low, sk_high, hits, hits_packed, set_hits, ovl_prev, exact_flag, inexact_list, upair_base, upair_tab, upair_tab_sw, ovl_c, gwin_tab, cwin, cwin_len, warn, thr_tab, pieces, contig_out, new_len, unpack_off;
+    Dev<uint32_t> store[2], word_off, set_start, read_set, pair_base, upair_base, pair_read, mz_off, mz_cnt, counters, warn, set_cols, changed, read_dirty,
+        dp_list, dp_list2, dp_list3, dp_list16, dp_list_e3, dp_wide, dp_xwide, left_list, fix_list, wide_list, inexact_list, cols_wide,
+        gwin_off, gwin_read, lb, unpack_off, brel_off, src3, bnd_flag, bnd_list, site_cnt, site_off, redo, sk_ends, sk_low, sk_high;
+    Dev<uint32_t> sr_store;      // the round's reads, then the first consensus pass's result as a second store behind them
+    Dev<uint32_t> site_cursor;   // four counters: [0] vectors, [1] listed windows, [3] site records
+    Dev<uint32_t> site_lists;    // two lists of n_gwin entries: windows with a site, windows to redo
+    Dev<uint32_t> set_hits;      // hits per set, then (behind them) n_sets + 1 offsets
+    Dev<int32_t> len, new_len, idx2, bc_idx;
+    Dev<int32_t> bc_win;         // three words per grid window
+    Dev<fsv_mz> mz; Dev<fsv_ovl> ovl, ovl_prev; Dev<fsv_hit> hits, hits_packed; Dev<fsv_piece> pieces; Dev<BndPatch> bnd_patch;
+    Dev<fsv_wtask> tasks, tasks2, tasks3; Dev<fsv_wres> res, res2, res3; Dev<fsv_wpath> paths, paths2;
+    Dev<uint4> cols_sb, ovl_c, upair_tab, upair_tab_sw, gwin_tab, bc_rec; Dev<uint2> site_rec; Dev<int8_t> site_vec;
+    Dev<uint64_t> cols;          // k_path_dp's column scratch: 64-bit columns, or 32-bit ones in the same bytes
+    Dev<unsigned long long> tmp; // cycle stamps of the diagnostic runs
+    Dev<uint8_t> cov3, bnd_bytes, exact_flag, cwin, thr_tab; Dev<uint16_t> cwin_len; Dev<char> contig_out, contig_all;
     std::vector<uint32_t> h_store;   // the corrected reads of the sets whose layout compares bases (kept between calls: no 96 MB zero-fill a step)
     int occ_sb = 0, occ_fr[3] = {0, 0, 0}, occ_wide = 0;   // blocks per CU of the persistent K6 kernels (hipOccupancyMaxActiveBlocksPerMultiprocessor: asked once)
     ChainArgs last_chain;   // arguments of the last k_chain launch (the final pass re-chains a few pairs with another bandwidth)
-    std::vector<size_t> sk_rec, uq_rec, chain_rec, bpm_rec, rescue_rec, fast_rec, dp_rec, cons_rec, bnd_rec, bpm2_rec, fast2_rec, dp2_rec, bndc_rec, bc_bpm_rec, bc_fast_rec, bc_dp_rec;   // KTimes records of the k_chain launches of this batch (their byte counts are filled in at the end)
     // state of the last run (for fsv_asm_fetch_reads / stats)
     std::vector<uint32_t> h_word_off;
     std::vector<int32_t> h_len;
@@ -68,11 +90,16 @@ struct AsmWs {
     fsv_asm_stats stats;
     KTimes kt;
     void *h_pin = nullptr; size_t h_pin_cap = 0; // pinned host staging (exact hits)
-    // only the chunking budget reads this list (what this context already holds): a buffer missing from it is undercounted there, not leaked
-    std::vector<const DevBuf *> all() const
+    uint32_t *ct_of(int row) { return counters.p + (size_t)row * CT_SLOT; }   // a row of the counter block (valid until counters grows)
+    // bytes this context holds.  Only the chunking budget reads it: a buffer missing from the list is undercounted there, not leaked
+    size_t held() const
     {
-        return {&store[0], &store[1], &cols_sb, &contig_all, &word_off, &len, &set_start, &read_set, &pair_base, &mz, &mz_off, &mz_cnt, &ovl, &tasks, &res, &paths,
-                &counters, &dp_list, &dp_list2, &dp_list3, &dp_list16, &dp_list_e3, &dp_wide, &dp_xwide, &cols_wide, &set_cols, &site_cnt, &site_rec, &site_off, &site_vec, &site_cursor, &redo, &site_lists, &read_dirty, &cov3, &lb, &sr_store, &brel_off, &tasks2, &res2, &paths2, &idx2, &bc_idx, &bc_rec, &bc_win, &left_list, &fix_list, &tasks3, &res3, &src3, &bnd_flag, &bnd_list, &bnd_patch, &bnd_bytes, &changed, &pair_read, &wide_list, &cols, &tmp, &gwin_off, &gwin_read, &sk_ends, &sk_low, &sk_high, &hits, &hits_packed, &set_hits, &ovl_prev, &exact_flag, &inexact_list, &upair_base, &upair_tab, &upair_tab_sw, &ovl_c, &gwin_tab, &cwin, &cwin_len, &warn, &thr_tab, &pieces, &contig_out, &new_len, &unpack_off};
+        return cap_sum(store[0], store[1], cols_sb, contig_all, word_off, len, set_start, read_set, pair_base, mz, mz_off, mz_cnt, ovl, tasks, res, paths,
+                       counters, dp_list, dp_list2, dp_list3, dp_list16, dp_list_e3, dp_wide, dp_xwide, cols_wide, set_cols, site_cnt, site_rec, site_off, site_vec,
+                       site_cursor, redo, site_lists, read_dirty, cov3, lb, sr_store, brel_off, tasks2, res2, paths2, idx2, bc_idx, bc_rec, bc_win, left_list, fix_list,
+                       tasks3, res3, src3, bnd_flag, bnd_list, bnd_patch, bnd_bytes, changed, pair_read, wide_list, cols, tmp, gwin_off, gwin_read, sk_ends, sk_low, sk_high,
+                       hits, hits_packed, set_hits, ovl_prev, exact_flag, inexact_list, upair_base, upair_tab, upair_tab_sw, ovl_c, gwin_tab, cwin, cwin_len, warn, thr_tab,
+                       pieces, contig_out, new_len, unpack_off);
     }
 };
 
@@ -152,103 +179,123 @@ template <class F> int lds_opt_in(fsv_ctx *ctx, F f, size_t bytes)
     return FSV_OK;
 }
 
-// sketch + per-read index + chaining on the current store; fills ws.ovl (and ws.tasks when emit_tasks).  Nothing here waits
-// for the GPU: launches are sized from the read lengths the host already has, counts stay in the round's counter slot `ct`.
-int overlap_stage(fsv_ctx *ctx, AsmWs &W, const Batch &B, const Geometry &G, const uint32_t *store, const fsv_asm_params &P, int bw,
-                  bool emit_tasks, uint32_t task_cap, uint32_t *ct, bool short_reads, bool wide_anchors, int w, const uint32_t *only_changed = nullptr)
+// What a correction round, and the final pass after the last one, carries from stage to stage
+struct Round {
+    const fsv_asm_params &P;
+    Batch B;
+    const uint8_t *set_flags = nullptr;
+    const uint32_t *store = nullptr; std::vector<int32_t> len; Geometry G;   // the reads as they are now: the caller's in round 0, then the store the last round repacked
+    std::vector<uint32_t> mz_fixed;  // minimizer slots: fixed for the whole call
+    bool wide_bands = false;         // the error model allows thresholds above hifiasm's 31: wide-band K5 / K6 / rescue
+    bool short_reads = true;         // every read below 65 536 bases: k_chain's compact LDS layout
+    int round = 0; uint32_t task_cap = 0, n_gwin = 0;
+    uint32_t *ct = nullptr;          // the round's (or the final pass's) row of device counters
+    ConsArgs C;
+    std::vector<uint32_t> h_ct;      // the counter rows on the host, as on the device
+    uint64_t reads_in_bytes = 0;
+    const std::chrono::steady_clock::time_point t_enter = std::chrono::steady_clock::now();
+    explicit Round(const fsv_asm_params &p) : P(p) {}
+    int row(int pass) const { return pass * (P.n_rounds + 1) + round; }
+};
+
+// k_chain in its three forms: a block per chunk of pairs, a block per pair (or per entry of A.pair_list), persistent blocks
+// walking A.wide_list with the large tile.  The one place that picks the LDS layout and opts in to its size.
+enum ChainKind { CHAIN_CHUNKS, CHAIN_PAIRS, CHAIN_WIDE_LIST };
+template <bool SHORT> int launch_chain_as(fsv_ctx *ctx, ChainKind kind, uint32_t grid, const ChainArgs &A, uint32_t n_upairs)
 {
+    const size_t lds = chain_lds_bytes(SHORT, A.amax);
+    if (kind == CHAIN_CHUNKS) { TRY(lds_opt_in(ctx, k_chain_chunks<SHORT>, lds)); FSV_LAUNCH(ctx, ctx->stream, k_chain_chunks<SHORT>, dim3(grid), dim3(64), lds, A, n_upairs); }
+    else if (kind == CHAIN_PAIRS) { TRY(lds_opt_in(ctx, k_chain<SHORT>, lds)); FSV_LAUNCH(ctx, ctx->stream, k_chain<SHORT>, dim3(grid), dim3(64), lds, A); }
+    else { TRY(lds_opt_in(ctx, k_chain_wide_list<SHORT>, lds)); FSV_LAUNCH(ctx, ctx->stream, k_chain_wide_list<SHORT>, dim3(grid), dim3(64), lds, A); }
+    return FSV_OK;
+}
+int launch_chain(fsv_ctx *ctx, ChainKind kind, bool short_reads, uint32_t grid, const ChainArgs &A, uint32_t n_upairs)
+{
+    return short_reads ? launch_chain_as<true>(ctx, kind, grid, A, n_upairs) : launch_chain_as<false>(ctx, kind, grid, A, n_upairs);
+}
+// the pairs a k_chain launch set aside (both lists beyond its tile: reads above ~25 kb), chained with the large tile
+int chain_wide_pairs(fsv_ctx *ctx, const ChainArgs &A, bool short_reads, uint32_t n_upairs)
+{
+    ChainArgs AW = A;
+    AW.amax = short_reads ? FSV_AMAX_WIDE : FSV_AMAX_WIDE_LONG; AW.stamps = nullptr; AW.pair_list = nullptr; AW.n_list_dev = nullptr;   // (the kernel walks AW.wide_list)
+    return launch_chain(ctx, CHAIN_WIDE_LIST, short_reads, std::min<uint32_t>(n_upairs, 2u * (uint32_t)ctx->n_cu), AW, n_upairs);
+}
+
+// sketch + per-read index + chaining on the current store; fills ws.ovl (and, in a correction round, ws.tasks).  Nothing here waits
+// for the GPU: launches are sized from the read lengths the host already has, counts stay in the counter row R.ct.
+int overlap_stage(fsv_ctx *ctx, AsmWs &W, const Round &R, bool final_pass)
+{
+    const fsv_asm_params &P = R.P; const Batch &B = R.B; const Geometry &G = R.G;
+    uint32_t *ct = R.ct;
+    // ONT-profile batches: dense seeds and 4 096-anchor tiles for the first round only (noisy reads share few minimizers, but nothing bounds
+    // them); from the second round on the reads are accurate and the sparser seeds keep a pair below 1 024 anchors
+    const int w = ((final_pass || R.round > 0) && P.w_later > 0) ? P.w_later : P.w;
+    const bool wide_anchors = R.wide_bands && w == P.w;
+    // hifiasm's final pass keeps every pair that shares a minimizer on a strand, however short the overlap (the graph sorts them out)
+    const int min_anchors = final_pass && P.min_anchors_final > 0 ? P.min_anchors_final : P.min_anchors;
+    const int min_ovlp = final_pass && P.min_ovlp_final > 0 ? P.min_ovlp_final : P.min_ovlp;
+    // in the final pass the reads the last round left untouched keep that round's minimizer lists (the last round does not
+    // reverse-complement) -- when that round sketched with the same window, and only with the position-parallel kernel (odd k):
+    // the replay kernel always sketches every read
+    const bool keep_lists = final_pass && P.n_rounds > 0 && (P.n_rounds > 1 || w == P.w) && (P.k & 1);
+    const uint32_t *only_changed = keep_lists ? W.changed.p : nullptr;
     Span ts(ctx, W.kt, ST_SKETCH);
-    TRY(ensure(ctx, W.mz, (size_t)G.mz_off[B.n_reads] * sizeof(fsv_mz)));
-    TRY(ensure(ctx, W.mz_cnt, (size_t)B.n_reads * 4));
-    TRY(ensure(ctx, W.ovl, (size_t)std::max(1u, B.n_pairs) * sizeof(fsv_ovl)));
-    TRY(ensure(ctx, W.ovl_c, (size_t)std::max(1u, B.n_pairs) * sizeof(uint4)));
-    W.sk_rec.push_back(W.kt.begin(ctx, KN_SKETCH, 0));    // bytes: filled in from the round's counters (minimizers produced, bases sketched)
-    if (!(only_changed && (P.k & 1))) FSV_HIP(ctx, hipMemsetAsync(W.mz_cnt.p, 0, (size_t)B.n_reads * 4, ctx->stream));
-    // (with only_changed the unchanged reads keep their count; the kernel zeroes the others itself)
-    if (!(P.k & 1)) only_changed = nullptr; // the replay kernel (even k) always sketches every read
-    if (P.k & 1) {
-        // position-parallel sketch (odd k): per-read scratch for run ends (4 B / base) and two bit planes, planes zeroed per launch
-        const size_t total_words = G.word_off[B.n_reads];
-        TRY(ensure(ctx, W.sk_ends, (total_words * 16 + 64) * 4));
-        TRY(ensure(ctx, W.sk_low, (total_words + B.n_reads + 8) * 4));
-        TRY(ensure(ctx, W.sk_high, (total_words + B.n_reads + 8) * 4));
-        FSV_HIP(ctx, hipMemsetAsync(W.sk_low.p, 0, (total_words + B.n_reads + 8) * 4, ctx->stream));
-        FSV_HIP(ctx, hipMemsetAsync(W.sk_high.p, 0, (total_words + B.n_reads + 8) * 4, ctx->stream));
-        hipLaunchKernelGGL(k_sketch_fast, dim3(B.n_reads), dim3(256), 0, ctx->stream, store, (const uint32_t *)W.word_off.p,
-                           (const int32_t *)W.len.p, (const uint32_t *)W.mz_off.p, (fsv_mz *)W.mz.p, (uint32_t *)W.mz_cnt.p, B.n_reads, w, P.k,
-                           P.hpc, (uint32_t *)W.warn.p, (const uint8_t *)nullptr, (uint32_t *)W.sk_ends.p, (uint32_t *)W.sk_low.p, (uint32_t *)W.sk_high.p,
-                           only_changed);
-        FSV_HIP(ctx, hipGetLastError());
-    } else {
-        const uint32_t lds_words = std::min<uint32_t>(G.max_words, 8192u);
-        FSV_HIP(ctx, hipFuncSetAttribute((const void *)k_sketch, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sketch_lds_bytes(w, lds_words)));
-        hipLaunchKernelGGL(k_sketch, dim3(B.n_reads), dim3(64), sketch_lds_bytes(w, lds_words), ctx->stream, store, (const uint32_t *)W.word_off.p,
-                           (const int32_t *)W.len.p, (const uint32_t *)W.mz_off.p, (fsv_mz *)W.mz.p, (uint32_t *)W.mz_cnt.p, B.n_reads, w, P.k,
-                           P.hpc, (uint32_t *)W.warn.p, (const uint8_t *)nullptr, w, lds_words);
-        FSV_HIP(ctx, hipGetLastError());
-    }
+    TRY(ensure(ctx, W.mz, G.mz_off[B.n_reads]));
+    TRY(ensure(ctx, W.mz_cnt, B.n_reads));
+    TRY(ensure(ctx, W.ovl, std::max(1u, B.n_pairs)));
+    TRY(ensure(ctx, W.ovl_c, std::max(1u, B.n_pairs)));
+    W.kt.begin(ctx, PASS_WINDOWS, KN_SKETCH, 0);    // bytes: filled in from the round's counters (minimizers produced, bases sketched)
+    TRY(launch_sketch(ctx, W, SketchJob{R.store, B.n_reads, G.word_off[B.n_reads], G.max_words, w, P.k, P.hpc, nullptr, w, false, only_changed}));
     W.kt.end(ctx);
     // the sort in k_uniq holds a read's minimizers in LDS (16 B per entry): one instantiation for lists up to 1 024 entries (many
     // reads per CU), one for longer ones; each launch skips the reads of the other size class, so the host need not know the
     // longest list of the batch (round 1 read the counts back to choose)
     unsigned long long *mz_total = (unsigned long long *)(ct + CT_MZ_LO);
-    W.uq_rec.push_back(W.kt.begin(ctx, KN_UNIQ, 0));
-    hipLaunchKernelGGL(k_uniq<1024>, dim3(B.n_reads), dim3(256), 0, ctx->stream, (fsv_mz *)W.mz.p, (const uint32_t *)W.mz_off.p,
-                       (uint32_t *)W.mz_cnt.p, (uint32_t *)W.warn.p, only_changed, 0u, 1024u, mz_total);
-    FSV_HIP(ctx, hipGetLastError());
-    if (G.max_words * 16u > 1024u) {   // at most one minimizer per base: shorter reads cannot have a longer list
-        hipLaunchKernelGGL(k_uniq_walk<FSV_UQ_MAX>, dim3(std::min<uint32_t>(B.n_reads, 2u * (uint32_t)ctx->n_cu)), dim3(256), 0, ctx->stream, (fsv_mz *)W.mz.p, (const uint32_t *)W.mz_off.p,
-                           (uint32_t *)W.mz_cnt.p, (uint32_t *)W.warn.p, only_changed, 1024u, 0xffffffffu, mz_total, B.n_reads);
-        FSV_HIP(ctx, hipGetLastError());
-    }
+    W.kt.begin(ctx, PASS_WINDOWS, KN_UNIQ, 0);
+    FSV_LAUNCH(ctx, ctx->stream, k_uniq<1024>, dim3(B.n_reads), dim3(256), 0, W.mz.p, W.mz_off.p, W.mz_cnt.p, W.warn.p, only_changed, 0u, 1024u, mz_total);
+    if (G.max_words * 16u > 1024u)   // at most one minimizer per base: shorter reads cannot have a longer list
+        FSV_LAUNCH(ctx, ctx->stream, k_uniq_walk<FSV_UQ_MAX>, dim3(std::min<uint32_t>(B.n_reads, 2u * (uint32_t)ctx->n_cu)), dim3(256), 0, W.mz.p, W.mz_off.p,
+                   W.mz_cnt.p, W.warn.p, only_changed, 1024u, 0xffffffffu, mz_total, B.n_reads);
     W.kt.end(ctx);
     ts.stop();
     if (B.n_pairs == 0) return FSV_OK;
     Span tc(ctx, W.kt, ST_CHAIN);
     ChainArgs A;
-    A.store = store; A.word_off = (const uint32_t *)W.word_off.p; A.read_len = (const int32_t *)W.len.p;
-    A.set_start = (const uint32_t *)W.set_start.p; A.pair_base = (const uint32_t *)W.pair_base.p; A.upair_base = (const uint32_t *)W.upair_base.p;
-    A.mz = (const fsv_mz *)W.mz.p; A.mz_off = (const uint32_t *)W.mz_off.p; A.mz_cnt = (const uint32_t *)W.mz_cnt.p;
-    A.ovl = (fsv_ovl *)W.ovl.p; A.tasks = (fsv_wtask *)W.tasks.p; A.task_counter = ct + CT_TASKS; A.task_cap = task_cap;
-    A.overflow = ct + CT_OVERFLOW; A.warn = (uint32_t *)W.warn.p; A.set_cols = (uint32_t *)W.set_cols.p; A.thr_tab = (const uint8_t *)W.thr_tab.p;
-    A.n_sets = B.n_sets; A.k_score = P.k; A.min_anchors = P.min_anchors; A.min_ovlp = P.min_ovlp; A.bw = bw; A.emit_tasks = emit_tasks ? 1 : 0; A.primary_only = 0;
+    A.store = R.store; A.word_off = W.word_off.p; A.read_len = W.len.p;
+    A.set_start = W.set_start.p; A.pair_base = W.pair_base.p; A.upair_base = W.upair_base.p;
+    A.mz = W.mz.p; A.mz_off = W.mz_off.p; A.mz_cnt = W.mz_cnt.p;
+    A.ovl = W.ovl.p; A.tasks = W.tasks.p; A.task_counter = ct + CT_TASKS; A.task_cap = R.task_cap;
+    A.overflow = ct + CT_OVERFLOW; A.warn = W.warn.p; A.set_cols = W.set_cols.p; A.thr_tab = W.thr_tab.p;
+    A.n_sets = B.n_sets; A.k_score = P.k; A.min_anchors = min_anchors; A.min_ovlp = min_ovlp; A.bw = final_pass ? P.bw_final : P.bw_ec;
+    A.emit_tasks = final_pass ? 0 : 1; A.primary_only = 0;
     // LDS per pair: the anchor arrays for FSV_AMAX entries -- 12 B each in the compact layout (every read of the batch below
     // 65 536 bases), so the tile no longer has to be cut to the batch's longest list to keep several pairs per CU
-    A.upair_tab = (const uint4 *)W.upair_tab.p; A.pair_list = nullptr; A.n_list_dev = nullptr;
+    A.upair_tab = W.upair_tab.p; A.pair_list = nullptr; A.n_list_dev = nullptr;
     A.amax = wide_anchors ? FSV_AMAX_WIDE : FSV_AMAX;
     // a pair whose lists both exceed the tile is set aside and chained with the large tile afterwards (reads above ~25 kb)
     A.wide_list = nullptr; A.n_wide = nullptr;
     if (!wide_anchors) {
-        TRY(ensure(ctx, W.wide_list, (size_t)B.n_upairs * 4 + 16));
-        A.wide_list = (uint32_t *)W.wide_list.p; A.n_wide = ct + CT_WIDE;
+        TRY(ensure(ctx, W.wide_list, (size_t)B.n_upairs + 4));
+        A.wide_list = W.wide_list.p; A.n_wide = ct + CT_WIDE;
     }
     A.stamps = nullptr;
     if (getenv("FSV_CHAIN_STAMPS")) {   // diagnostic: where a k_chain wave spends its cycles (never in a measured run)
-        TRY(ensure(ctx, W.tmp, 128));
-        FSV_HIP(ctx, hipMemsetAsync(W.tmp.p, 0, 128, ctx->stream));
-        A.stamps = (unsigned long long *)W.tmp.p;
+        TRY(ensure(ctx, W.tmp, 16));
+        TRY(zero(ctx, W.tmp, 16));
+        A.stamps = W.tmp.p;
     }
     // algorithmic bytes of the launch are filled in when the batch ends (they need the counts this launch leaves on the device)
-    W.chain_rec.push_back(W.kt.begin(ctx, KN_CHAIN, 0));
+    W.kt.begin(ctx, PASS_WINDOWS, KN_CHAIN, 0);
     const uint32_t n_chunks = ((B.n_upairs + FSV_CHAIN_CH - 1) / FSV_CHAIN_CH + 7u) & ~7u;   // (xcd_block: a multiple of eight blocks)
-    if (short_reads) { TRY(lds_opt_in(ctx, k_chain_chunks<true>, chain_lds_bytes(true, A.amax))); hipLaunchKernelGGL(k_chain_chunks<true>, dim3(n_chunks), dim3(64), chain_lds_bytes(true, A.amax), ctx->stream, A, B.n_upairs); }
-    else { TRY(lds_opt_in(ctx, k_chain_chunks<false>, chain_lds_bytes(false, A.amax))); hipLaunchKernelGGL(k_chain_chunks<false>, dim3(n_chunks), dim3(64), chain_lds_bytes(false, A.amax), ctx->stream, A, B.n_upairs); }
-    FSV_HIP(ctx, hipGetLastError());
-    if (A.wide_list) {
-        ChainArgs AW = A;
-        AW.amax = short_reads ? FSV_AMAX_WIDE : FSV_AMAX_WIDE_LONG; AW.stamps = nullptr;   // (the kernel walks AW.wide_list)
-        const uint32_t gridw = std::min<uint32_t>(B.n_upairs, 2u * (uint32_t)ctx->n_cu);
-        if (short_reads) { TRY(lds_opt_in(ctx, k_chain_wide_list<true>, chain_lds_bytes(true, AW.amax))); hipLaunchKernelGGL(k_chain_wide_list<true>, dim3(gridw), dim3(64), chain_lds_bytes(true, AW.amax), ctx->stream, AW); }
-        else { TRY(lds_opt_in(ctx, k_chain_wide_list<false>, chain_lds_bytes(false, AW.amax))); hipLaunchKernelGGL(k_chain_wide_list<false>, dim3(gridw), dim3(64), chain_lds_bytes(false, AW.amax), ctx->stream, AW); }
-        FSV_HIP(ctx, hipGetLastError());
-    }
+    TRY(launch_chain(ctx, CHAIN_CHUNKS, R.short_reads, n_chunks, A, B.n_upairs));
+    if (A.wide_list) TRY(chain_wide_pairs(ctx, A, R.short_reads, B.n_upairs));
     W.kt.end(ctx);
     if (A.stamps) {
         unsigned long long h[16];
-        FSV_HIP(ctx, hipMemcpyAsync(h, W.tmp.p, 128, hipMemcpyDeviceToHost, ctx->stream));
+        TRY(download(ctx, h, W.tmp, 16));
         FSV_HIP(ctx, hipStreamSynchronize(ctx->stream));
         static const char *nm[7] = {"stage lists", "lookups", "exit: few anchors", "compaction", "chain DP", "best + walk", "tasks + records"};
-        fprintf(stderr, "[fsv] k_chain (%u pairs, tasks %d):", B.n_upairs, emit_tasks ? 1 : 0);
+        fprintf(stderr, "[fsv] k_chain (%u pairs, tasks %d):", B.n_upairs, A.emit_tasks);
         for (int i = 0; i < 7; i++) fprintf(stderr, " %s %.0f cyc x %llu;", nm[i], h[8 + i] ? (double)h[i] / h[8 + i] : 0.0, h[8 + i]);
         fprintf(stderr, "\n");
         A.stamps = nullptr;
@@ -375,8 +422,165 @@ extern "C" int fsv_assemble_batch_bound(const fsv_readsets *sets, uint64_t *seq_
     return FSV_OK;
 }
 
-// K5 + K6 on caller-supplied tasks: the same kernels fsv_assemble_batch drives, with every task treated as belonging to an
-// accepted overlap
+// A task list for K6, with its K5 results and the counter row its lists are counted in
+struct PathJob {
+    const uint32_t *store; fsv_wtask *tasks; fsv_wres *res; fsv_wpath *paths;
+    uint32_t task_cap; const uint32_t *n_tasks_dev; uint32_t *ct;   // the bound the grids are sized for; the count on the device (null: task_cap)
+    int pass, round;
+    bool wide_bands; int k_cap;
+    bool all_accepted;    // every task belongs to an accepted overlap (W.ovl then holds that one overlap)
+};
+
+// K6 for a task list: the fast paths, then the DP kernels on what is left (the lists and their counters live in the counter row J.ct).
+// Used for the window tasks of a round, the junction tasks of its second consensus pass, the junction cigars of its partition,
+// and for the caller's tasks of fsv_bpm_paths.
+static int path_stage(fsv_ctx *ctx, AsmWs &W, const PathJob &J)
+{
+    const uint32_t *store = J.store; const fsv_wtask *tasks = J.tasks; const fsv_wres *res = J.res; fsv_wpath *paths = J.paths;
+    uint32_t *ct = J.ct;
+    const uint32_t task_cap = J.task_cap, n_cu = (uint32_t)ctx->n_cu;
+    // a persistent grid: as many blocks as the device holds at once (per_cu each CU), never more than one wave per 64 tasks
+    auto persistent = [&](int per_cu) { return std::min<uint32_t>(fsv_grid_for(task_cap, 64), (uint32_t)std::max(1, per_cu) * n_cu); };
+    W.kt.begin(ctx, J.pass, KN_PATH_FAST, 0);
+    const bool fix = J.pass == PASS_WINDOWS && !J.wide_bands;      // fix_boundary: the windows' final cigars only (not the junction alignments)
+    if (fix) TRY(ensure(ctx, W.fix_list, task_cap));
+    const PathLists lists{{W.dp_list16.p, W.dp_list.p, W.dp_list_e3.p, W.dp_list2.p, W.dp_list3.p, W.dp_wide.p, W.dp_xwide.p, fix ? W.fix_list.p : nullptr},
+                          {ct + CT_DP_SB16, ct + CT_DP, ct + CT_DP_FR3, ct + CT_DP_SB, ct + CT_DP_GEN, ct + CT_DP_WIDE, ct + CT_DP_XW, fix ? ct + CT_FIX : nullptr}};
+    FSV_LAUNCH(ctx, ctx->stream, k_path_fast, dim3((fsv_grid_for(task_cap, 256) + 7u) & ~7u), dim3(256), 0, store, W.ovl.p, tasks, res, task_cap, paths, lists,
+               J.all_accepted, J.n_tasks_dev);
+    W.kt.end(ctx);
+    // what the fast paths left: distance <= 3 is walked without the DP matrix (k_path_fr), <= FSV_SB_MAXERR by the sub-band kernel,
+    // the rest by the general one
+    W.kt.begin(ctx, J.pass, KN_PATH_DP, 0);
+    // persistent grids, each block striding through its list, so the column scratch is a fixed few hundred MB whatever the number of windows
+    const bool stamps = getenv("FSV_K6_STAMPS") != nullptr;    // diagnostic: where a wave spends its cycles (never in a measured run)
+    unsigned long long h[4] = {0, 0, 0, 0};
+    uint32_t nl = 0;
+    auto read_stamps = [&](const uint32_t *cnt) -> int {   // waits for the launch: its stamps in h, its list's length in nl
+        TRY(download(ctx, h, W.tmp, 4));
+        if (cnt) FSV_HIP(ctx, hipMemcpyAsync(&nl, cnt, 4, hipMemcpyDeviceToHost, ctx->stream));
+        FSV_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        return FSV_OK;
+    };
+    if (!W.occ_sb) FSV_HIP(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&W.occ_sb, k_path_sb<false>, 64, 0));
+    const uint32_t grid = persistent(W.occ_sb);
+    TRY(ensure(ctx, W.cols_sb, (size_t)grid * FSV_SB_QUADS * 64));
+    if (stamps) {
+        TRY(ensure(ctx, W.tmp, 8));
+        TRY(zero(ctx, W.tmp, 8));
+        FSV_LAUNCH(ctx, ctx->stream, k_path_sb<true>, dim3(grid), dim3(64), 0, store, tasks, res, W.dp_list2.p, ct + CT_DP_SB, paths, W.cols_sb.p, W.tmp.p);
+        TRY(read_stamps(nullptr));
+        fprintf(stderr, "[fsv] k_path_sb round %d: %llu waves, cycles per wave: forward %.0f, walk %.0f, finish %.0f (grid %u)\n", J.round, h[3],
+                h[3] ? (double)h[0] / h[3] : 0.0, h[3] ? (double)h[1] / h[3] : 0.0, h[3] ? (double)h[2] / h[3] : 0.0, grid);
+    } else
+        FSV_LAUNCH(ctx, ctx->stream, k_path_sb<false>, dim3(grid), dim3(64), 0, store, tasks, res, W.dp_list2.p, ct + CT_DP_SB, paths, W.cols_sb.p,
+                   (unsigned long long *)nullptr);
+    // distance <= 3 (nine in ten): walked without the matrix, a launch per distance
+    auto fr = [&](auto kern, int e, const Dev<uint32_t> &list, uint32_t *cnt) -> int {
+        int &pf = W.occ_fr[e - 1];
+        if (!pf || stamps) FSV_HIP(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&pf, kern, 64, 0));
+        if (stamps) { TRY(ensure(ctx, W.tmp, 8)); TRY(zero(ctx, W.tmp, 8)); }
+        FSV_LAUNCH(ctx, ctx->stream, kern, dim3(persistent(pf)), dim3(64), 0, store, tasks, res, list.p, cnt, paths, stamps ? W.tmp.p : nullptr);
+        if (stamps) {
+            TRY(read_stamps(cnt));
+            fprintf(stderr, "[fsv] k_path_fr<%d> round %d: %u windows, %llu waves (%d per CU), cycles per wave: table %.0f, walk %.0f, finish %.0f\n", e, J.round, nl, h[3], pf,
+                    h[3] ? (double)h[0] / h[3] : 0.0, h[3] ? (double)h[1] / h[3] : 0.0, h[3] ? (double)h[2] / h[3] : 0.0);
+        }
+        return FSV_OK;
+    };
+    if (stamps) {
+        TRY(fr(k_path_fr<1, true>, 1, W.dp_list16, ct + CT_DP_SB16));
+        TRY(fr(k_path_fr<2, true>, 2, W.dp_list, ct + CT_DP));
+        TRY(fr(k_path_fr<3, true>, 3, W.dp_list_e3, ct + CT_DP_FR3));
+    } else {
+        TRY(fr(k_path_fr<1>, 1, W.dp_list16, ct + CT_DP_SB16));
+        TRY(fr(k_path_fr<2>, 2, W.dp_list, ct + CT_DP));
+        TRY(fr(k_path_fr<3>, 3, W.dp_list_e3, ct + CT_DP_FR3));
+    }
+    // the general kernel's lists are short (rescue windows, distances above 7): two blocks per CU are plenty
+    const uint32_t gridg = persistent(2), stride = gridg * 64;
+    TRY(ensure(ctx, W.cols, (size_t)stride * (FSV_WINDOW + 2) * 3));
+    FSV_LAUNCH(ctx, ctx->stream, k_path_dp<uint32_t>, dim3(gridg), dim3(64), 0, store, tasks, W.dp_list3.p, 0u, 0u, paths,
+               (uint32_t *)W.cols.p /* 32-bit columns in the same scratch */, stride, ct + CT_DP_GEN);
+    FSV_LAUNCH(ctx, ctx->stream, k_path_dp<uint64_t>, dim3(gridg), dim3(64), 0, store, tasks, W.dp_wide.p, 0u, 0u, paths, W.cols.p, stride, ct + CT_DP_WIDE);
+    if (J.wide_bands) {
+        // bands above 63 rows: every gapped window of an ONT-profile batch; 1.15 MB of column scratch per persistent block
+        if (!W.occ_wide) FSV_HIP(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&W.occ_wide, k_path_wide, 64, 0));
+        const uint32_t gridw = persistent(std::min(W.occ_wide, 12));
+        TRY(ensure(ctx, W.cols_wide, (size_t)gridw * FSV_WINDOW * 2 * FSV_WL * 64));
+        FSV_LAUNCH(ctx, ctx->stream, k_path_wide, dim3(gridw), dim3(64), 0, store, tasks, res, W.dp_xwide.p, ct + CT_DP_XW, paths, W.cols_wide.p, J.k_cap);
+    }
+    if (fix)
+        // fix_boundary (Correct.cpp:1676): the few windows whose alignment may touch the edge of its band (k_path_fast listed them)
+        FSV_LAUNCH(ctx, ctx->stream, k_fix_boundary, dim3(persistent(8)), dim3(64), 0, store, W.fix_list.p, ct + CT_FIX, J.tasks, J.res, paths, J.k_cap, ct + CT_FIXED);
+    W.kt.end(ctx);
+    return FSV_OK;
+}
+
+// The second consensus pass of a round (process_boundary, Correct.cpp:4453): see asm_kernels.h "second consensus pass".
+// Runs between the windows' consensus (cwin / cwin_len final for the first pass) and k_newlen; leaves cwin / cwin_len patched.
+static int second_pass(fsv_ctx *ctx, AsmWs &W, const Round &R)
+{
+    const fsv_asm_params &P = R.P; const Batch &B = R.B; const Geometry &G = R.G;
+    const uint32_t n_gwin = R.n_gwin, task_cap = R.task_cap;
+    uint32_t *ct2 = W.ct_of(R.row(PASS_JUNCTIONS));
+    // where window g starts in the first pass's result, and that result as a 2-bit store behind a copy of the round's reads
+    TRY(ensure(ctx, W.lb, std::max(1u, n_gwin)));
+    W.kt.begin(ctx, PASS_JUNCTIONS, KN_BND, 0);
+    FSV_LAUNCH(ctx, ctx->stream, k_newlen, dim3(fsv_grid_for(B.n_reads, 256)), dim3(256), 0, W.gwin_off.p, W.cwin_len.p, B.n_reads, W.new_len.p, W.lb.p);
+    const uint32_t a_words = G.word_off[B.n_reads];
+    std::vector<uint32_t> brel(B.n_reads + 1, 0);
+    for (uint32_t r = 0; r < B.n_reads; r++) {
+        const uint64_t nx = (uint64_t)brel[r] + (uint64_t)(G.gwin_off[r + 1] - G.gwin_off[r]) * (FSV_CW_STRIDE / 16) + 2;
+        if (nx + a_words >= (1ull << 32)) return fsv_fail(ctx, FSV_EUNSUP, "second consensus pass: store larger than 2^32 words; split the batch");
+        brel[r + 1] = (uint32_t)nx;
+    }
+    const uint32_t b_words = brel[B.n_reads];
+    TRY(ensure(ctx, W.sr_store, (size_t)a_words + b_words + 16));
+    FSV_HIP(ctx, hipMemcpyAsync(W.sr_store.p, R.store, (size_t)a_words * 4, hipMemcpyDeviceToDevice, ctx->stream));
+    TRY(upload(ctx, W.brel_off, brel));
+    uint32_t *store2 = W.sr_store.p;
+    FSV_LAUNCH(ctx, ctx->stream, k_repack, dim3(B.n_reads), dim3(256), 0, W.gwin_off.p, W.lb.p, W.cwin.p, W.brel_off.p, W.new_len.p, B.n_reads, 0, store2 + a_words,
+               W.read_dirty.p);
+    FSV_HIP(ctx, hipMemsetAsync(store2 + a_words + b_words, 0, 32, ctx->stream));
+    // junction tasks
+    TRY(ensure_each(ctx, task_cap, W.tasks2, W.res2, W.paths2, W.idx2, W.tasks3, W.res3, W.src3));
+    TRY(ensure_each(ctx, (size_t)n_gwin + 2, W.bnd_flag, W.bnd_list, W.bnd_patch));
+    TRY(ensure(ctx, W.bnd_bytes, (size_t)(n_gwin + 2) * FSV_CW_STRIDE));
+    TRY(zero(ctx, W.bnd_flag, (size_t)n_gwin + 2));
+    BndArgs A;
+    A.tasks = W.tasks.p; A.paths = W.paths.p; A.n_tasks = R.ct + CT_TASKS;
+    A.ovl_c = W.ovl_c.p; A.pair_base = W.pair_base.p; A.set_start = W.set_start.p; A.n_sets = B.n_sets; A.pair_read = W.pair_read.p;
+    A.gwin_off = W.gwin_off.p; A.lb = W.lb.p; A.cwin_len = W.cwin_len.p;
+    A.cov3 = W.cov3.p; A.read_dirty = W.read_dirty.p;
+    A.brel_off = W.brel_off.p; A.b_base = a_words; A.thr_tab = W.thr_tab.p;
+    A.tasks2 = W.tasks2.p; A.idx2 = W.idx2.p; A.n_tasks2 = ct2 + CT_TASKS;
+    A.bnd_flag = W.bnd_flag.p; A.bnd_list = W.bnd_list.p; A.n_bnd = ct2 + CT_B_LIST; A.store2 = store2;
+    FSV_LAUNCH(ctx, ctx->stream, k_bnd_tasks, dim3((fsv_grid_for(task_cap, 256) + 7u) & ~7u), dim3(256), 0, A);
+    W.kt.end(ctx);
+    W.kt.begin(ctx, PASS_JUNCTIONS, KN_BPM, 0);
+    // K5, once more with the doubled threshold for the tasks without an alignment, K6
+    TRY(fsv_bpm_windows_dev_n(ctx, store2, W.tasks2.p, task_cap, ct2 + CT_TASKS, W.res2.p, P.k_cap));
+    FSV_LAUNCH(ctx, ctx->stream, k_bnd_retry, dim3(fsv_grid_for(task_cap, 256)), dim3(256), 0, W.tasks2.p, W.res2.p, ct2 + CT_TASKS, W.tasks3.p, W.src3.p,
+               ct2 + CT_B_RETRY, P.k_cap);
+    TRY(fsv_bpm_windows_dev_n(ctx, store2, W.tasks3.p, task_cap, ct2 + CT_B_RETRY, W.res3.p, P.k_cap));
+    FSV_LAUNCH(ctx, ctx->stream, k_bnd_scatter, dim3(fsv_grid_for(task_cap, 256)), dim3(256), 0, W.res2.p, W.res3.p, W.src3.p, ct2 + CT_B_RETRY);
+    W.kt.end(ctx);
+    TRY(path_stage(ctx, W, PathJob{store2, W.tasks2.p, W.res2.p, W.paths2.p, task_cap, ct2 + CT_TASKS, ct2, PASS_JUNCTIONS, R.round, R.wide_bands, P.k_cap, false}));
+    // the junctions' consensus, handed to the windows as patches
+    const uint32_t grid_l = std::min<uint32_t>(std::max(1u, n_gwin), (uint32_t)ctx->n_cu * 16);
+    W.kt.begin(ctx, PASS_JUNCTIONS, KN_BND_CONS, 0);
+    if (R.wide_bands) FSV_LAUNCH(ctx, ctx->stream, k_bnd_consensus<FSV_EV_CAP_WIDE>, dim3(grid_l), dim3(64), 0, R.C, A, W.paths2.p, store2, W.bnd_patch.p, W.bnd_bytes.p);
+    else FSV_LAUNCH(ctx, ctx->stream, k_bnd_consensus<FSV_EV_CAP>, dim3(grid_l), dim3(64), 0, R.C, A, W.paths2.p, store2, W.bnd_patch.p, W.bnd_bytes.p);
+    FSV_LAUNCH(ctx, ctx->stream, k_bnd_apply, dim3(std::max(1u, n_gwin)), dim3(64), 0, W.gwin_read.p, W.gwin_off.p, W.bnd_patch.p, W.bnd_bytes.p, W.bnd_flag.p, n_gwin,
+               W.cwin.p, W.cwin_len.p, W.changed.p, W.warn.p);
+    W.kt.end(ctx);
+    return FSV_OK;
+}
+
+// K5 + K6 on caller-supplied tasks: the launch code fsv_assemble_batch drives (path_stage, on this context's workspace), with every
+// task treated as belonging to an accepted overlap and without fix_boundary.  Leaves the last assembly's reads and contigs alone
+// (fsv_asm_fetch_reads / fsv_align_batch may follow): the store goes into a buffer of its own.
 static int fsv_bpm_paths_impl(fsv_ctx *ctx, const uint32_t *store, size_t store_words, const fsv_wtask *tasks, uint32_t n_tasks,
                              fsv_wres *res, fsv_wpath *paths)
 {
@@ -389,61 +593,26 @@ static int fsv_bpm_paths_impl(fsv_ctx *ctx, const uint32_t *store, size_t store_
     }
     const int k_cap = kmax > FSV_K_MAX ? kmax : FSV_K_MAX;     // a threshold above 31 anywhere: K5 of the whole list through the wide kernel
     FSV_HIP(ctx, hipSetDevice(ctx->device));
-    DevBuf d_store, d_tasks, d_res, d_paths, d_ovl, d_list, d_list2, d_list3, d_list16, d_list_e3, d_wide, d_xwide, d_cnt, d_cols, d_cols_sb, d_cols_wide;
-    {
-        std::vector<fsv_wtask> t(tasks, tasks + n_tasks);
-        for (auto &x : t) x.ovl = 0;
-        fsv_ovl o; memset(&o, 0, sizeof(o)); o.valid = 1; o.is_match = 1;
-        TRY(ensure(ctx, d_store, store_words * 4 + 64));
-        FSV_HIP(ctx, hipMemsetAsync(d_store.p, 0, store_words * 4 + 64, ctx->stream));
-        FSV_HIP(ctx, hipMemcpyAsync(d_store.p, store, store_words * 4, hipMemcpyHostToDevice, ctx->stream));
-        TRY(upload(ctx, d_tasks, t));
-        TRY(upload(ctx, d_ovl, std::vector<fsv_ovl>{o}));
-        TRY(ensure(ctx, d_res, (size_t)n_tasks * sizeof(fsv_wres)));
-        TRY(ensure(ctx, d_paths, (size_t)n_tasks * sizeof(fsv_wpath)));
-        for (DevBuf *b : {&d_list, &d_list2, &d_list3, &d_list16, &d_list_e3, &d_wide, &d_xwide}) TRY(ensure(ctx, *b, (size_t)n_tasks * 4));
-        TRY(ensure(ctx, d_cnt, CT_SLOT * 4));
-        uint32_t *ct = (uint32_t *)d_cnt.p;
-        FSV_HIP(ctx, hipMemsetAsync(d_cnt.p, 0, CT_SLOT * 4, ctx->stream));
-        FSV_HIP(ctx, hipMemsetAsync(d_paths.p, 0, (size_t)n_tasks * sizeof(fsv_wpath), ctx->stream));
-        // the same launches as a correction round of fsv_assemble_batch (device-side list lengths, no host round trip in between)
-        TRY(fsv_bpm_windows_dev_n(ctx, (const uint32_t *)d_store.p, (const fsv_wtask *)d_tasks.p, n_tasks, nullptr, (fsv_wres *)d_res.p, k_cap));
-        const PathLists lists{{(uint32_t *)d_list16.p, (uint32_t *)d_list.p, (uint32_t *)d_list_e3.p, (uint32_t *)d_list2.p, (uint32_t *)d_list3.p, (uint32_t *)d_wide.p, (uint32_t *)d_xwide.p},
-                              {ct + CT_DP_SB16, ct + CT_DP, ct + CT_DP_FR3, ct + CT_DP_SB, ct + CT_DP_GEN, ct + CT_DP_WIDE, ct + CT_DP_XW}};
-        hipLaunchKernelGGL(k_path_fast, dim3((fsv_grid_for(n_tasks, 256) + 7u) & ~7u), dim3(256), 0, ctx->stream, (const uint32_t *)d_store.p, (const fsv_ovl *)d_ovl.p,
-                           (const fsv_wtask *)d_tasks.p, (const fsv_wres *)d_res.p, n_tasks, (fsv_wpath *)d_paths.p, lists, true, (const uint32_t *)nullptr);
-        FSV_HIP(ctx, hipGetLastError());
-        const uint32_t grid = std::min<uint32_t>(fsv_grid_for(n_tasks, 64), 8u * (uint32_t)ctx->n_cu);
-        TRY(ensure(ctx, d_cols_sb, (size_t)grid * FSV_SB_QUADS * 64 * sizeof(uint4)));
-        hipLaunchKernelGGL(k_path_sb<false>, dim3(grid), dim3(64), 0, ctx->stream, (const uint32_t *)d_store.p, (const fsv_wtask *)d_tasks.p, (const fsv_wres *)d_res.p,
-                           (const uint32_t *)d_list2.p, (const uint32_t *)(ct + CT_DP_SB), (fsv_wpath *)d_paths.p, (uint4 *)d_cols_sb.p, (unsigned long long *)nullptr);
-        FSV_HIP(ctx, hipGetLastError());
-        hipLaunchKernelGGL(k_path_fr<1>, dim3(grid), dim3(64), 0, ctx->stream, (const uint32_t *)d_store.p, (const fsv_wtask *)d_tasks.p, (const fsv_wres *)d_res.p,
-                           (const uint32_t *)d_list16.p, (const uint32_t *)(ct + CT_DP_SB16), (fsv_wpath *)d_paths.p);
-        hipLaunchKernelGGL(k_path_fr<2>, dim3(grid), dim3(64), 0, ctx->stream, (const uint32_t *)d_store.p, (const fsv_wtask *)d_tasks.p, (const fsv_wres *)d_res.p,
-                           (const uint32_t *)d_list.p, (const uint32_t *)(ct + CT_DP), (fsv_wpath *)d_paths.p);
-        hipLaunchKernelGGL(k_path_fr<3>, dim3(grid), dim3(64), 0, ctx->stream, (const uint32_t *)d_store.p, (const fsv_wtask *)d_tasks.p, (const fsv_wres *)d_res.p,
-                           (const uint32_t *)d_list_e3.p, (const uint32_t *)(ct + CT_DP_FR3), (fsv_wpath *)d_paths.p);
-        FSV_HIP(ctx, hipGetLastError());
-        const uint32_t gridg = std::min<uint32_t>(fsv_grid_for(n_tasks, 64), 2u * (uint32_t)ctx->n_cu);
-        TRY(ensure(ctx, d_cols, (size_t)gridg * 64 * (FSV_WINDOW + 2) * 3 * 8));
-        hipLaunchKernelGGL(k_path_dp<uint32_t>, dim3(gridg), dim3(64), 0, ctx->stream, (const uint32_t *)d_store.p, (const fsv_wtask *)d_tasks.p,
-                           (const uint32_t *)d_list3.p, 0u, 0u, (fsv_wpath *)d_paths.p, (uint32_t *)d_cols.p, gridg * 64, (const uint32_t *)(ct + CT_DP_GEN));
-        FSV_HIP(ctx, hipGetLastError());
-        hipLaunchKernelGGL(k_path_dp<uint64_t>, dim3(gridg), dim3(64), 0, ctx->stream, (const uint32_t *)d_store.p, (const fsv_wtask *)d_tasks.p,
-                           (const uint32_t *)d_wide.p, 0u, 0u, (fsv_wpath *)d_paths.p, (uint64_t *)d_cols.p, gridg * 64, (const uint32_t *)(ct + CT_DP_WIDE));
-        FSV_HIP(ctx, hipGetLastError());
-        if (kmax > FSV_K_MAX) {
-            const uint32_t gridw = std::min<uint32_t>(fsv_grid_for(n_tasks, 64), 4u * (uint32_t)ctx->n_cu);
-            TRY(ensure(ctx, d_cols_wide, (size_t)gridw * FSV_WINDOW * 2 * FSV_WL * 64 * 4));
-            hipLaunchKernelGGL(k_path_wide, dim3(gridw), dim3(64), 0, ctx->stream, (const uint32_t *)d_store.p, (const fsv_wtask *)d_tasks.p, (const fsv_wres *)d_res.p,
-                               (const uint32_t *)d_xwide.p, (const uint32_t *)(ct + CT_DP_XW), (fsv_wpath *)d_paths.p, (uint32_t *)d_cols_wide.p, k_cap);
-            FSV_HIP(ctx, hipGetLastError());
-        }
-        FSV_HIP(ctx, hipMemcpyAsync(res, d_res.p, (size_t)n_tasks * sizeof(fsv_wres), hipMemcpyDeviceToHost, ctx->stream));
-        FSV_HIP(ctx, hipMemcpyAsync(paths, d_paths.p, (size_t)n_tasks * sizeof(fsv_wpath), hipMemcpyDeviceToHost, ctx->stream));
-        FSV_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    }
+    AsmWs &W = *ws_get(ctx);
+    W.kt.reset();       // (path_stage times its launches: no record of them is left for a later batch's statistics)
+    std::vector<fsv_wtask> t(tasks, tasks + n_tasks);
+    for (auto &x : t) x.ovl = 0;
+    fsv_ovl o; memset(&o, 0, sizeof(o)); o.valid = 1; o.is_match = 1;
+    Dev<uint32_t> d_store;
+    TRY(ensure(ctx, d_store, store_words + 16));
+    TRY(zero(ctx, d_store, store_words + 16));
+    FSV_HIP(ctx, hipMemcpyAsync(d_store.p, store, store_words * 4, hipMemcpyHostToDevice, ctx->stream));
+    TRY(upload(ctx, W.tasks, t));
+    TRY(upload(ctx, W.ovl, std::vector<fsv_ovl>{o}));
+    TRY(ensure_each(ctx, n_tasks, W.res, W.paths, W.dp_list, W.dp_list2, W.dp_list3, W.dp_list16, W.dp_list_e3, W.dp_wide, W.dp_xwide));
+    TRY(ensure(ctx, W.counters, CT_SLOT));
+    TRY(zero(ctx, W.counters, CT_SLOT));
+    TRY(zero(ctx, W.paths, n_tasks));
+    TRY(fsv_bpm_windows_dev_n(ctx, d_store.p, W.tasks.p, n_tasks, nullptr, W.res.p, k_cap));
+    TRY(path_stage(ctx, W, PathJob{d_store.p, W.tasks.p, W.res.p, W.paths.p, n_tasks, nullptr, W.counters.p, PASS_NONE, 0, kmax > FSV_K_MAX, k_cap, true}));
+    TRY(download(ctx, res, W.res, n_tasks));
+    TRY(download(ctx, paths, W.paths, n_tasks));
+    FSV_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return FSV_OK;
 }
 
@@ -454,213 +623,22 @@ extern "C" int fsv_asm_last_stats(const fsv_ctx *ctx, fsv_asm_stats *out)
     return FSV_OK;
 }
 
-// one chunk of read sets through the whole assembly (what fsv_assemble_batch was before it learnt to split a batch)
-// K6 for a task list: the fast paths, then the DP kernels on what is left (the lists and their counters live in the counter row ct).
-// Used for the window tasks of a round and, with second_round, for the junction tasks of its second consensus pass.
-static int path_stage(fsv_ctx *ctx, AsmWs &W, const uint32_t *store, const fsv_wtask *tasks, const fsv_wres *res, fsv_wpath *paths, uint32_t task_cap,
-                      const uint32_t *n_tasks_dev, uint32_t *ct, int round, bool wide_bands, const fsv_asm_params &P, int pass_kind)
-{
-    // pass_kind 0: the round's window tasks, 1: the junction tasks of its second consensus pass, 2: the junction cigars of the partition
-    { const size_t rec_ = W.kt.begin(ctx, KN_PATH_FAST, 0); (pass_kind == 0 ? W.fast_rec : pass_kind == 1 ? W.fast2_rec : W.bc_fast_rec).push_back(rec_); }
-    const bool fix = pass_kind == 0 && !wide_bands;      // fix_boundary: the windows' final cigars only (not the junction alignments)
-    if (fix) TRY(ensure(ctx, W.fix_list, (size_t)task_cap * 4));
-    const PathLists lists{{(uint32_t *)W.dp_list16.p, (uint32_t *)W.dp_list.p, (uint32_t *)W.dp_list_e3.p, (uint32_t *)W.dp_list2.p, (uint32_t *)W.dp_list3.p, (uint32_t *)W.dp_wide.p, (uint32_t *)W.dp_xwide.p,
-                           fix ? (uint32_t *)W.fix_list.p : (uint32_t *)nullptr},
-                          {ct + CT_DP_SB16, ct + CT_DP, ct + CT_DP_FR3, ct + CT_DP_SB, ct + CT_DP_GEN, ct + CT_DP_WIDE, ct + CT_DP_XW, fix ? ct + CT_FIX : (uint32_t *)nullptr}};
-    hipLaunchKernelGGL(k_path_fast, dim3((fsv_grid_for(task_cap, 256) + 7u) & ~7u), dim3(256), 0, ctx->stream, store, (const fsv_ovl *)W.ovl.p,
-                       tasks, res, task_cap, paths, lists, false, n_tasks_dev);
-    FSV_HIP(ctx, hipGetLastError());
-    W.kt.end(ctx);
-    // what the fast paths left: distance <= 3 is walked without the DP matrix (k_path_fr), <= FSV_SB_MAXERR by the sub-band kernel,
-    // the rest by the general one
-    { const size_t rec_ = W.kt.begin(ctx, KN_PATH_DP, 0); (pass_kind == 0 ? W.dp_rec : pass_kind == 1 ? W.dp2_rec : W.bc_dp_rec).push_back(rec_); }
-    // persistent grids: as many blocks as the device holds at once, each striding through its list, so the column scratch
-    // is a fixed few hundred MB whatever the number of windows
-    {
-        if (!W.occ_sb) FSV_HIP(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&W.occ_sb, k_path_sb<false>, 64, 0));
-        const int per_cu = W.occ_sb;
-        const uint32_t grid = std::min<uint32_t>(fsv_grid_for(task_cap, 64), (uint32_t)std::max(1, per_cu) * (uint32_t)ctx->n_cu);
-        TRY(ensure(ctx, W.cols_sb, (size_t)grid * FSV_SB_QUADS * 64 * sizeof(uint4)));
-        if (getenv("FSV_K6_STAMPS")) {   // diagnostic: where a k_path_sb wave spends its cycles (never in a measured run)
-            DevBuf &sb = W.tmp;
-            TRY(ensure(ctx, sb, 64));
-            FSV_HIP(ctx, hipMemsetAsync(sb.p, 0, 64, ctx->stream));
-            hipLaunchKernelGGL(k_path_sb<true>, dim3(grid), dim3(64), 0, ctx->stream, store, tasks, res,
-                               (const uint32_t *)W.dp_list2.p, (const uint32_t *)(ct + CT_DP_SB), paths, (uint4 *)W.cols_sb.p, (unsigned long long *)sb.p);
-            unsigned long long h[4] = {0, 0, 0, 0};
-            FSV_HIP(ctx, hipMemcpyAsync(h, sb.p, 32, hipMemcpyDeviceToHost, ctx->stream));
-            FSV_HIP(ctx, hipStreamSynchronize(ctx->stream));
-            fprintf(stderr, "[fsv] k_path_sb round %d: %llu waves, cycles per wave: forward %.0f, walk %.0f, finish %.0f (grid %u)\n", round, h[3],
-                    h[3] ? (double)h[0] / h[3] : 0.0, h[3] ? (double)h[1] / h[3] : 0.0, h[3] ? (double)h[2] / h[3] : 0.0, grid);
-        } else
-        hipLaunchKernelGGL(k_path_sb<false>, dim3(grid), dim3(64), 0, ctx->stream, store, tasks, res,
-                           (const uint32_t *)W.dp_list2.p, (const uint32_t *)(ct + CT_DP_SB), paths, (uint4 *)W.cols_sb.p, (unsigned long long *)nullptr);
-        FSV_HIP(ctx, hipGetLastError());
-        // distance <= 3 (nine in ten): walked without the matrix, a launch per distance
-        {
-            const bool stamps = getenv("FSV_K6_STAMPS") != nullptr;    // diagnostic, never in a measured run
-            auto fr = [&](auto kern, int e, const DevBuf &list, uint32_t *cnt) -> int {
-                int &pf = W.occ_fr[e - 1];
-                if (!pf || stamps) FSV_HIP(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&pf, kern, 64, 0));
-                const uint32_t gridf = std::min<uint32_t>(fsv_grid_for(task_cap, 64), (uint32_t)std::max(1, pf) * (uint32_t)ctx->n_cu);
-                if (stamps) { TRY(ensure(ctx, W.tmp, 64)); FSV_HIP(ctx, hipMemsetAsync(W.tmp.p, 0, 64, ctx->stream)); }
-                hipLaunchKernelGGL(kern, dim3(gridf), dim3(64), 0, ctx->stream, store, tasks, res, (const uint32_t *)list.p, (const uint32_t *)cnt, paths,
-                                   (unsigned long long *)(stamps ? W.tmp.p : nullptr));
-                FSV_HIP(ctx, hipGetLastError());
-                if (stamps) {
-                    unsigned long long h[4] = {0, 0, 0, 0};
-                    uint32_t nl = 0;
-                    FSV_HIP(ctx, hipMemcpyAsync(h, W.tmp.p, 32, hipMemcpyDeviceToHost, ctx->stream));
-                    FSV_HIP(ctx, hipMemcpyAsync(&nl, cnt, 4, hipMemcpyDeviceToHost, ctx->stream));
-                    FSV_HIP(ctx, hipStreamSynchronize(ctx->stream));
-                    fprintf(stderr, "[fsv] k_path_fr<%d> round %d: %u windows, %llu waves (%d per CU), cycles per wave: table %.0f, walk %.0f, finish %.0f\n", e, round, nl, h[3], pf,
-                            h[3] ? (double)h[0] / h[3] : 0.0, h[3] ? (double)h[1] / h[3] : 0.0, h[3] ? (double)h[2] / h[3] : 0.0);
-                }
-                return FSV_OK;
-            };
-            if (stamps) {
-                TRY(fr(k_path_fr<1, true>, 1, W.dp_list16, ct + CT_DP_SB16));
-                TRY(fr(k_path_fr<2, true>, 2, W.dp_list, ct + CT_DP));
-                TRY(fr(k_path_fr<3, true>, 3, W.dp_list_e3, ct + CT_DP_FR3));
-            } else {
-                TRY(fr(k_path_fr<1>, 1, W.dp_list16, ct + CT_DP_SB16));
-                TRY(fr(k_path_fr<2>, 2, W.dp_list, ct + CT_DP));
-                TRY(fr(k_path_fr<3>, 3, W.dp_list_e3, ct + CT_DP_FR3));
-            }
-        }
-        // the general kernel's lists are short (rescue windows, distances above 7): two blocks per CU are plenty
-        const uint32_t gridg = std::min<uint32_t>(fsv_grid_for(task_cap, 64), 2u * (uint32_t)ctx->n_cu), stride = gridg * 64;
-        TRY(ensure(ctx, W.cols, (size_t)stride * (FSV_WINDOW + 2) * 3 * sizeof(uint64_t)));
-        hipLaunchKernelGGL(k_path_dp<uint32_t>, dim3(gridg), dim3(64), 0, ctx->stream, store, tasks,
-                           (const uint32_t *)W.dp_list3.p, 0u, 0u, paths, (uint32_t *)W.cols.p, stride, (const uint32_t *)(ct + CT_DP_GEN));
-        FSV_HIP(ctx, hipGetLastError());
-        hipLaunchKernelGGL(k_path_dp<uint64_t>, dim3(gridg), dim3(64), 0, ctx->stream, store, tasks,
-                           (const uint32_t *)W.dp_wide.p, 0u, 0u, paths, (uint64_t *)W.cols.p, stride, (const uint32_t *)(ct + CT_DP_WIDE));
-        FSV_HIP(ctx, hipGetLastError());
-        if (wide_bands) {
-            // bands above 63 rows: every gapped window of an ONT-profile batch; 1.15 MB of column scratch per persistent block
-            if (!W.occ_wide) FSV_HIP(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&W.occ_wide, k_path_wide, 64, 0));
-            const int pc = W.occ_wide;
-            const uint32_t gridw = std::min<uint32_t>(fsv_grid_for(task_cap, 64), (uint32_t)std::max(1, std::min(pc, 12)) * (uint32_t)ctx->n_cu);
-            TRY(ensure(ctx, W.cols_wide, (size_t)gridw * FSV_WINDOW * 2 * FSV_WL * 64 * 4));
-            hipLaunchKernelGGL(k_path_wide, dim3(gridw), dim3(64), 0, ctx->stream, store, tasks, res,
-                               (const uint32_t *)W.dp_xwide.p, (const uint32_t *)(ct + CT_DP_XW), paths, (uint32_t *)W.cols_wide.p, P.k_cap);
-            FSV_HIP(ctx, hipGetLastError());
-        }
-    }
-    if (fix) {
-        // fix_boundary (Correct.cpp:1676): the few windows whose alignment may touch the edge of its band (k_path_fast listed them)
-        const uint32_t gridf = std::min<uint32_t>(fsv_grid_for(task_cap, 64), 8u * (uint32_t)ctx->n_cu);
-        hipLaunchKernelGGL(k_fix_boundary, dim3(gridf), dim3(64), 0, ctx->stream, store, (const uint32_t *)W.fix_list.p, (const uint32_t *)(ct + CT_FIX),
-                           const_cast<fsv_wtask *>(tasks), const_cast<fsv_wres *>(res), paths, P.k_cap, ct + CT_FIXED);
-        FSV_HIP(ctx, hipGetLastError());
-    }
-    W.kt.end(ctx);
-    return FSV_OK;
-}
+// ---- one chunk of read sets through the whole assembly, stage by stage ---------------------------------------------------------
+// Every launch of a round is sized from what the host knows when the round starts (read lengths, the window-task bound); counts the
+// kernels produce stay in the round's counter row.  One synchronisation per round is left: the corrected reads' lengths, which the
+// host turns into the next round's geometry -- the round's counters ride along with it (finish_round).
 
-// The second consensus pass of a round (process_boundary, Correct.cpp:4453): see asm_kernels.h "second consensus pass".
-// Runs between the windows' consensus (cwin / cwin_len final for the first pass) and k_newlen; leaves cwin / cwin_len patched.
-static int second_pass(fsv_ctx *ctx, AsmWs &W, const Batch &B, const Geometry &G, const uint32_t *store, const fsv_asm_params &P, const ConsArgs &C,
-                       uint32_t n_gwin, uint32_t task_cap, const uint32_t *n_tasks_dev, uint32_t *ct2, int round, bool wide_bands)
+// the batch's tables on the device, the geometry of round 0, zeroed counters
+static int prepare_batch(fsv_ctx *ctx, AsmWs &W, const fsv_readsets *sets, Round &R)
 {
-    // where window g starts in the first pass's result, and that result as a 2-bit store behind a copy of the round's reads
-    TRY(ensure(ctx, W.lb, (size_t)std::max(1u, n_gwin) * 4));
-    W.bnd_rec.push_back(W.kt.begin(ctx, KN_BND, 0));
-    hipLaunchKernelGGL(k_newlen, dim3(fsv_grid_for(B.n_reads, 256)), dim3(256), 0, ctx->stream, (const uint32_t *)W.gwin_off.p,
-                       (const uint16_t *)W.cwin_len.p, B.n_reads, (int32_t *)W.new_len.p, (uint32_t *)W.lb.p);
-    FSV_HIP(ctx, hipGetLastError());
-    const uint32_t a_words = G.word_off[B.n_reads];
-    std::vector<uint32_t> brel(B.n_reads + 1, 0);
-    for (uint32_t r = 0; r < B.n_reads; r++) {
-        const uint64_t nx = (uint64_t)brel[r] + (uint64_t)(G.gwin_off[r + 1] - G.gwin_off[r]) * (FSV_CW_STRIDE / 16) + 2;
-        if (nx + a_words >= (1ull << 32)) return fsv_fail(ctx, FSV_EUNSUP, "second consensus pass: store larger than 2^32 words; split the batch");
-        brel[r + 1] = (uint32_t)nx;
-    }
-    const uint32_t b_words = brel[B.n_reads];
-    TRY(ensure(ctx, W.sr_store, ((size_t)a_words + b_words + 16) * 4));
-    FSV_HIP(ctx, hipMemcpyAsync(W.sr_store.p, store, (size_t)a_words * 4, hipMemcpyDeviceToDevice, ctx->stream));
-    TRY(upload(ctx, W.brel_off, brel));
-    uint32_t *store2 = (uint32_t *)W.sr_store.p;
-    hipLaunchKernelGGL(k_repack, dim3(B.n_reads), dim3(256), 0, ctx->stream, (const uint32_t *)W.gwin_off.p, (const uint32_t *)W.lb.p,
-                       (const uint8_t *)W.cwin.p, (const uint32_t *)W.brel_off.p, (const int32_t *)W.new_len.p, B.n_reads, 0, store2 + a_words,
-                       (const uint32_t *)W.read_dirty.p);
-    FSV_HIP(ctx, hipGetLastError());
-    FSV_HIP(ctx, hipMemsetAsync(store2 + a_words + b_words, 0, 32, ctx->stream));
-    // junction tasks
-    TRY(ensure(ctx, W.tasks2, (size_t)task_cap * sizeof(fsv_wtask)));
-    TRY(ensure(ctx, W.res2, (size_t)task_cap * sizeof(fsv_wres)));
-    TRY(ensure(ctx, W.paths2, (size_t)task_cap * sizeof(fsv_wpath)));
-    TRY(ensure(ctx, W.idx2, (size_t)task_cap * 4));
-    TRY(ensure(ctx, W.tasks3, (size_t)task_cap * sizeof(fsv_wtask)));
-    TRY(ensure(ctx, W.res3, (size_t)task_cap * sizeof(fsv_wres)));
-    TRY(ensure(ctx, W.src3, (size_t)task_cap * 4));
-    TRY(ensure(ctx, W.bnd_flag, (size_t)(n_gwin + 2) * 4));
-    TRY(ensure(ctx, W.bnd_list, (size_t)(n_gwin + 2) * 4));
-    TRY(ensure(ctx, W.bnd_patch, (size_t)(n_gwin + 2) * sizeof(BndPatch)));
-    TRY(ensure(ctx, W.bnd_bytes, (size_t)(n_gwin + 2) * FSV_CW_STRIDE));
-    FSV_HIP(ctx, hipMemsetAsync(W.bnd_flag.p, 0, (size_t)(n_gwin + 2) * 4, ctx->stream));
-    BndArgs A;
-    A.tasks = (const fsv_wtask *)W.tasks.p; A.paths = (const fsv_wpath *)W.paths.p; A.n_tasks = n_tasks_dev;
-    A.ovl_c = (const uint4 *)W.ovl_c.p; A.pair_base = (const uint32_t *)W.pair_base.p; A.set_start = (const uint32_t *)W.set_start.p; A.n_sets = B.n_sets; A.pair_read = (const uint32_t *)W.pair_read.p;
-    A.gwin_off = (const uint32_t *)W.gwin_off.p; A.lb = (const uint32_t *)W.lb.p; A.cwin_len = (const uint16_t *)W.cwin_len.p;
-    A.cov3 = (const uint8_t *)W.cov3.p; A.read_dirty = (const uint32_t *)W.read_dirty.p;
-    A.brel_off = (const uint32_t *)W.brel_off.p; A.b_base = a_words; A.thr_tab = (const uint8_t *)W.thr_tab.p;
-    A.tasks2 = (fsv_wtask *)W.tasks2.p; A.idx2 = (int32_t *)W.idx2.p; A.n_tasks2 = ct2 + CT_TASKS;
-    A.bnd_flag = (uint32_t *)W.bnd_flag.p; A.bnd_list = (uint32_t *)W.bnd_list.p; A.n_bnd = ct2 + CT_B_LIST; A.store2 = store2;
-    hipLaunchKernelGGL(k_bnd_tasks, dim3((fsv_grid_for(task_cap, 256) + 7u) & ~7u), dim3(256), 0, ctx->stream, A);
-    FSV_HIP(ctx, hipGetLastError());
-    W.kt.end(ctx);
-    W.bpm2_rec.push_back(W.kt.begin(ctx, KN_BPM, 0));
-    // K5, once more with the doubled threshold for the tasks without an alignment, K6
-    TRY(fsv_bpm_windows_dev_n(ctx, store2, (const fsv_wtask *)W.tasks2.p, task_cap, ct2 + CT_TASKS, (fsv_wres *)W.res2.p, P.k_cap));
-    hipLaunchKernelGGL(k_bnd_retry, dim3(fsv_grid_for(task_cap, 256)), dim3(256), 0, ctx->stream, (fsv_wtask *)W.tasks2.p, (const fsv_wres *)W.res2.p,
-                       (const uint32_t *)(ct2 + CT_TASKS), (fsv_wtask *)W.tasks3.p, (uint32_t *)W.src3.p, ct2 + CT_B_RETRY, P.k_cap);
-    FSV_HIP(ctx, hipGetLastError());
-    TRY(fsv_bpm_windows_dev_n(ctx, store2, (const fsv_wtask *)W.tasks3.p, task_cap, ct2 + CT_B_RETRY, (fsv_wres *)W.res3.p, P.k_cap));
-    hipLaunchKernelGGL(k_bnd_scatter, dim3(fsv_grid_for(task_cap, 256)), dim3(256), 0, ctx->stream, (fsv_wres *)W.res2.p, (const fsv_wres *)W.res3.p,
-                       (const uint32_t *)W.src3.p, (const uint32_t *)(ct2 + CT_B_RETRY));
-    FSV_HIP(ctx, hipGetLastError());
-    W.kt.end(ctx);
-    TRY(path_stage(ctx, W, store2, (const fsv_wtask *)W.tasks2.p, (const fsv_wres *)W.res2.p, (fsv_wpath *)W.paths2.p, task_cap, (const uint32_t *)(ct2 + CT_TASKS), ct2,
-                   round, wide_bands, P, 1));
-    // the junctions' consensus, handed to the windows as patches
-    const uint32_t grid_l = std::min<uint32_t>(std::max(1u, n_gwin), (uint32_t)ctx->n_cu * 16);
-    W.bndc_rec.push_back(W.kt.begin(ctx, KN_BND_CONS, 0));
-    if (wide_bands) hipLaunchKernelGGL(k_bnd_consensus<FSV_EV_CAP_WIDE>, dim3(grid_l), dim3(64), 0, ctx->stream, C, A, (const fsv_wpath *)W.paths2.p, (const uint32_t *)store2,
-                                       (BndPatch *)W.bnd_patch.p, (uint8_t *)W.bnd_bytes.p);
-    else hipLaunchKernelGGL(k_bnd_consensus<FSV_EV_CAP>, dim3(grid_l), dim3(64), 0, ctx->stream, C, A, (const fsv_wpath *)W.paths2.p, (const uint32_t *)store2,
-                            (BndPatch *)W.bnd_patch.p, (uint8_t *)W.bnd_bytes.p);
-    FSV_HIP(ctx, hipGetLastError());
-    hipLaunchKernelGGL(k_bnd_apply, dim3(std::max(1u, n_gwin)), dim3(64), 0, ctx->stream, (const uint32_t *)W.gwin_read.p, (const uint32_t *)W.gwin_off.p,
-                       (const BndPatch *)W.bnd_patch.p, (const uint8_t *)W.bnd_bytes.p, (const uint32_t *)W.bnd_flag.p, n_gwin, (uint8_t *)W.cwin.p,
-                       (uint16_t *)W.cwin_len.p, (uint32_t *)W.changed.p, (uint32_t *)W.warn.p);
-    FSV_HIP(ctx, hipGetLastError());
-    W.kt.end(ctx);
-    return FSV_OK;
-}
-
-static int assemble_chunk(fsv_ctx *ctx, const fsv_readsets *sets, const fsv_asm_params &P, fsv_contigs *out)
-{
-    AsmWs &W = *ws_get(ctx);
-    memset(&W.stats, 0, sizeof(W.stats));
-    W.kt.reset();
-    W.sk_rec.clear(); W.uq_rec.clear(); W.chain_rec.clear(); W.bpm_rec.clear(); W.rescue_rec.clear(); W.fast_rec.clear(); W.dp_rec.clear(); W.cons_rec.clear();
-    W.bnd_rec.clear(); W.bpm2_rec.clear(); W.fast2_rec.clear(); W.dp2_rec.clear(); W.bndc_rec.clear(); W.bc_bpm_rec.clear(); W.bc_fast_rec.clear(); W.bc_dp_rec.clear();
-    const auto t_enter = std::chrono::steady_clock::now();
-
-    Batch B;
+    // (set_start spans [0, n_reads] and is monotone: fsv_assemble_batch_impl has checked)
+    const fsv_asm_params &P = R.P; Batch &B = R.B;
     B.n_reads = sets->n_reads; B.n_sets = sets->n_sets;
-    out->n_contigs = 0;
-    out->off[0] = 0;
-    for (uint32_t s = 0; s < B.n_sets; s++) out->set_status[s] = 0;
-    if (B.n_reads == 0 || B.n_sets == 0) return FSV_OK;
+    R.set_flags = sets->set_flags;   // (FSV_SET_UNPHASED only picks the layout: the haplotype partition runs for every read of every set, as in hifiasm)
     B.set_start.assign(sets->set_start, sets->set_start + B.n_sets + 1);
-    if (B.set_start[0] != 0 || B.set_start[B.n_sets] != B.n_reads) return fsv_fail(ctx, FSV_EINVAL, "set_start must span [0, n_reads]");
     B.read_set.resize(B.n_reads); B.pair_base.resize(B.n_sets + 1); B.upair_base.resize(B.n_sets + 1);
     uint64_t np = 0;
     for (uint32_t s = 0; s < B.n_sets; s++) {
-        if (B.set_start[s + 1] < B.set_start[s]) return fsv_fail(ctx, FSV_EINVAL, "set_start not monotone");
         uint64_t ns = B.set_start[s + 1] - B.set_start[s];
         B.pair_base[s] = (uint32_t)np;
         B.upair_base[s] = (uint32_t)(np / 2);
@@ -670,7 +648,8 @@ static int assemble_chunk(fsv_ctx *ctx, const fsv_readsets *sets, const fsv_asm_
     if (np >= (1ull << 31)) return fsv_fail(ctx, FSV_EUNSUP, "too many read pairs in one batch; split it");
     B.pair_base[B.n_sets] = (uint32_t)np; B.n_pairs = (uint32_t)np;
     B.upair_base[B.n_sets] = (uint32_t)(np / 2); B.n_upairs = (uint32_t)(np / 2);
-    std::vector<int32_t> len(sets->read_len, sets->read_len + B.n_reads);
+    std::vector<int32_t> &len = R.len;
+    len.assign(sets->read_len, sets->read_len + B.n_reads);
     for (uint32_t r = 0; r < B.n_reads; r++) if (len[r] < 1 || len[r] >= (1 << 24)) return fsv_fail(ctx, FSV_EUNSUP, "read length must be in [1, 2^24)");
 
     std::vector<uint8_t> thr(FSV_WINDOW + 1);
@@ -681,368 +660,366 @@ static int assemble_chunk(fsv_ctx *ctx, const fsv_readsets *sets, const fsv_asm_
     TRY(upload(ctx, W.pair_base, B.pair_base));
     TRY(upload(ctx, W.upair_base, B.upair_base));
     if (B.n_upairs) {
-        TRY(ensure(ctx, W.upair_tab, (size_t)B.n_upairs * sizeof(uint4)));
-        TRY(ensure(ctx, W.pair_read, (size_t)B.n_pairs * 4));
-        hipLaunchKernelGGL(k_pair_tab, dim3((B.n_upairs + 255) / 256), dim3(256), 0, ctx->stream, (const uint32_t *)W.set_start.p,
-                           (const uint32_t *)W.pair_base.p, (const uint32_t *)W.upair_base.p, B.n_sets, B.n_upairs, (uint4 *)W.upair_tab.p, (uint32_t *)W.pair_read.p);
-        FSV_HIP(ctx, hipGetLastError());
+        TRY(ensure(ctx, W.upair_tab, B.n_upairs));
+        TRY(ensure(ctx, W.pair_read, B.n_pairs));
+        FSV_LAUNCH(ctx, ctx->stream, k_pair_tab, dim3((B.n_upairs + 255) / 256), dim3(256), 0, W.set_start.p, W.pair_base.p, W.upair_base.p, B.n_sets, B.n_upairs,
+                   W.upair_tab.p, W.pair_read.p);
     }
-    TRY(ensure(ctx, W.warn, (size_t)B.n_reads * 4));
-    FSV_HIP(ctx, hipMemsetAsync(W.warn.p, 0, (size_t)B.n_reads * 4, ctx->stream));
-    // set_flags (FSV_SET_UNPHASED) no longer changes anything here: the haplotype partition runs for every read of every set, as in hifiasm
+    TRY(ensure(ctx, W.warn, B.n_reads));
+    TRY(zero(ctx, W.warn, B.n_reads));
 
     // minimizer slots stay where they are for the whole call (a read grows by a few bases at most when it is corrected): the
     // final pass can then keep the lists of reads the last round did not change
-    std::vector<uint32_t> mz_fixed(B.n_reads + 1, 0);
+    R.mz_fixed.assign(B.n_reads + 1, 0);
     {
         uint64_t m = 0;
-        for (uint32_t r = 0; r < B.n_reads; r++) { mz_fixed[r] = (uint32_t)m; m += mz_slots((int64_t)len[r] + len[r] / 8 + 64, P.w); }
+        for (uint32_t r = 0; r < B.n_reads; r++) { R.mz_fixed[r] = (uint32_t)m; m += mz_slots((int64_t)len[r] + len[r] / 8 + 64, P.w); }
         if (m >= (1ull << 32)) return fsv_fail(ctx, FSV_EUNSUP, "batch too large for 32-bit offsets; split it");
-        mz_fixed[B.n_reads] = (uint32_t)m;
+        R.mz_fixed[B.n_reads] = (uint32_t)m;
     }
-    Geometry G;
-    TRY(make_geometry(ctx, B, len, G, P.w, &mz_fixed));
+    TRY(make_geometry(ctx, B, len, R.G, P.w, &R.mz_fixed));
     // round 0 reads the caller's store through the caller's word offsets
-    std::vector<uint32_t> woff0(B.n_reads + 1);
     for (uint32_t r = 0; r <= B.n_reads; r++) {
         if (sets->word_off[r] >= (1ull << 32)) return fsv_fail(ctx, FSV_EUNSUP, "store larger than 2^32 words; split the batch");
-        woff0[r] = (uint32_t)sets->word_off[r];
+        R.G.word_off[r] = (uint32_t)sets->word_off[r];
     }
-    G.word_off = woff0;
-    const uint32_t *store = sets->store_dev;
-    uint64_t reads_in_bytes = 0;
-    const bool wide_bands = P.k_cap > FSV_K_MAX;   // the error model allows thresholds above hifiasm's 31: wide-band K5 / K6 / rescue
-    bool short_reads = true;     // every read below 65 536 bases: k_chain's compact LDS layout
-    for (uint32_t r = 0; r < B.n_reads; r++) { reads_in_bytes += (uint64_t)(len[r] + 3) / 4; if (len[r] >= 65536) short_reads = false; }
+    R.store = sets->store_dev;
+    R.wide_bands = P.k_cap > FSV_K_MAX;
+    for (uint32_t r = 0; r < B.n_reads; r++) { R.reads_in_bytes += (uint64_t)(len[r] + 3) / 4; if (len[r] >= 65536) R.short_reads = false; }
     // rows 0 .. n_rounds: the rounds and the final pass; rows n_rounds + 1 ..: the second consensus pass of every round; rows
-    // 2 n_rounds + 2 ..: the junction cigars of every round's partition
-    TRY(ensure(ctx, W.counters, (size_t)(3 * P.n_rounds + 2) * CT_SLOT * 4));
-    FSV_HIP(ctx, hipMemsetAsync(W.counters.p, 0, (size_t)(3 * P.n_rounds + 2) * CT_SLOT * 4, ctx->stream));
-    TRY(ensure(ctx, W.set_cols, (size_t)B.n_reads * 4));       // K5 columns per set, summed over the rounds (statistics)
-    FSV_HIP(ctx, hipMemsetAsync(W.set_cols.p, 0, (size_t)B.n_reads * 4, ctx->stream));
+    // 2 n_rounds + 2 ..: the junction cigars of every round's partition (Round::row)
+    const size_t n_ct = (size_t)(3 * P.n_rounds + 2) * CT_SLOT;
+    TRY(ensure(ctx, W.counters, n_ct));
+    TRY(zero(ctx, W.counters, n_ct));
+    R.h_ct.assign(n_ct, 0u);
+    TRY(ensure(ctx, W.set_cols, B.n_reads));       // K5 columns per set, summed over the rounds (statistics)
+    TRY(zero(ctx, W.set_cols, B.n_reads));
+    return FSV_OK;
+}
 
-    // every launch of a round is sized from what the host knows when the round starts (read lengths, the window-task bound);
-    // counts the kernels produce stay in the round's counter slot.  One synchronisation per round is left: the corrected reads'
-    // lengths, which the host turns into the next round's geometry -- the round's counters ride along with it.
-    auto ct_of = [&](int slot) { return (uint32_t *)W.counters.p + (size_t)slot * CT_SLOT; };
-    std::vector<uint32_t> h_ct((size_t)(3 * P.n_rounds + 2) * CT_SLOT, 0u);   // rows as on the device: rounds, final pass, the rounds' second passes
-    for (int round = 0; round < P.n_rounds; round++) {
-        uint32_t *ct = ct_of(round);
-        TRY(upload(ctx, W.word_off, G.word_off));
-        TRY(upload(ctx, W.len, len));
-        TRY(upload(ctx, W.mz_off, G.mz_off));
-        TRY(upload(ctx, W.gwin_off, G.gwin_off));
-        TRY(upload(ctx, W.gwin_read, G.gwin_read));
-        if (G.task_bound >= (1ull << 31)) return fsv_fail(ctx, FSV_EUNSUP, "window task bound exceeds 2^31; split the batch");
-        const uint32_t task_cap = (uint32_t)std::max<uint64_t>(G.task_bound, 1);
-        TRY(ensure(ctx, W.tasks, (size_t)task_cap * sizeof(fsv_wtask)));
-        TRY(ensure(ctx, W.res, (size_t)task_cap * sizeof(fsv_wres)));
-        TRY(ensure(ctx, W.paths, (size_t)task_cap * sizeof(fsv_wpath)));
-        TRY(ensure(ctx, W.dp_list, (size_t)task_cap * 4));
-        TRY(ensure(ctx, W.dp_list_e3, (size_t)task_cap * 4));
-        TRY(ensure(ctx, W.dp_list2, (size_t)task_cap * 4));
-        TRY(ensure(ctx, W.dp_list3, (size_t)task_cap * 4));
-        TRY(ensure(ctx, W.dp_list16, (size_t)task_cap * 4));
-        TRY(ensure(ctx, W.dp_wide, (size_t)task_cap * 4));
-        TRY(ensure(ctx, W.dp_xwide, wide_bands ? (size_t)task_cap * 4 : 64));
-        // ONT-profile batches: dense seeds and 4 096-anchor tiles for the first round only (noisy reads share few minimizers, but nothing bounds
-        // them); from the second round on the reads are accurate and the sparser seeds keep a pair below 1 024 anchors
-        const int w_round = (round > 0 && P.w_later > 0) ? P.w_later : P.w;
-        TRY(overlap_stage(ctx, W, B, G, store, P, P.bw_ec, true, task_cap, ct, short_reads, wide_bands && w_round == P.w, w_round));
-        W.stats.n_pairs += B.n_pairs;
-        if (B.n_pairs) {
-            Span tv(ctx, W.kt, ST_VERIFY);
-            W.bpm_rec.push_back(W.kt.begin(ctx, KN_BPM, 0));
-            TRY(fsv_bpm_windows_dev_n(ctx, store, (const fsv_wtask *)W.tasks.p, task_cap, ct + CT_TASKS, (fsv_wres *)W.res.p, P.k_cap));
-            W.kt.end(ctx);
-            W.rescue_rec.push_back(W.kt.begin(ctx, KN_RESCUE, (uint64_t)B.n_pairs * sizeof(fsv_ovl) * 2));
-            if (wide_bands)
-                hipLaunchKernelGGL(k_rescue_accept<true>, dim3(fsv_grid_for(B.n_pairs, 64)), dim3(64), 0, ctx->stream, store, (fsv_ovl *)W.ovl.p,
-                                   B.n_pairs, (fsv_wtask *)W.tasks.p, (fsv_wres *)W.res.p, (unsigned long long *)(ct + CT_COLS_LO),
-                                   (uint4 *)W.ovl_c.p, P.k_cap, P.accept_err_pm, (uint32_t *)nullptr, (uint32_t *)nullptr);
-            else {
-                // the right-extension pass and the verdict in one kernel; an overlap with an unmatched window LEFT of a matched one is set
-                // aside for the left-extension pass (k_left_rescue: it needs the matched window's path first), which then gives its verdict
-                TRY(ensure(ctx, W.left_list, (size_t)B.n_pairs * 4 + 16));
-                hipLaunchKernelGGL(k_rescue_accept<false>, dim3(fsv_grid_for(B.n_pairs, 64)), dim3(64), 0, ctx->stream, store, (fsv_ovl *)W.ovl.p,
-                                   B.n_pairs, (fsv_wtask *)W.tasks.p, (fsv_wres *)W.res.p, (unsigned long long *)(ct + CT_COLS_LO),
-                                   (uint4 *)W.ovl_c.p, P.k_cap, P.accept_err_pm, (uint32_t *)W.left_list.p, ct + CT_LEFT);
-                FSV_HIP(ctx, hipGetLastError());
-                const uint32_t gridl = std::min<uint32_t>(std::max(1u, B.n_pairs), 8u * (uint32_t)ctx->n_cu);
-                hipLaunchKernelGGL(k_left_rescue, dim3(gridl), dim3(64), 0, ctx->stream, store, (fsv_ovl *)W.ovl.p, (const uint32_t *)W.left_list.p,
-                                   (const uint32_t *)(ct + CT_LEFT), (fsv_wtask *)W.tasks.p, (fsv_wres *)W.res.p, (fsv_wpath *)W.paths.p, (uint64_t *)nullptr,
-                                   (uint4 *)W.ovl_c.p, P.k_cap, P.accept_err_pm);
-            }
-            FSV_HIP(ctx, hipGetLastError());
-            W.kt.end(ctx);
-            tv.stop();
-            Span tp(ctx, W.kt, ST_PATH);
-            TRY(path_stage(ctx, W, store, (const fsv_wtask *)W.tasks.p, (const fsv_wres *)W.res.p, (fsv_wpath *)W.paths.p, task_cap, (const uint32_t *)(ct + CT_TASKS), ct, round, wide_bands, P, 0));
-            tp.stop();
-        }
-        // consensus -> corrected windows -> new read store
-        Span tcs(ctx, W.kt, ST_CONSENSUS);
-        const uint32_t n_gwin = G.gwin_off[B.n_reads];
-        TRY(ensure(ctx, W.cwin, (size_t)n_gwin * FSV_CW_STRIDE));
-        TRY(ensure(ctx, W.cwin_len, (size_t)n_gwin * 2));
-        TRY(ensure(ctx, W.new_len, (size_t)B.n_reads * 4));
-        if (!B.n_pairs) FSV_HIP(ctx, hipMemsetAsync(W.ovl_c.p, 0, sizeof(uint4), ctx->stream));
-        TRY(ensure(ctx, W.gwin_tab, (size_t)std::max(1u, n_gwin) * sizeof(uint4)));
-        hipLaunchKernelGGL(k_gwin_tab, dim3(fsv_grid_for(n_gwin, 256)), dim3(256), 0, ctx->stream, (const uint32_t *)W.gwin_read.p, (const uint32_t *)W.gwin_off.p,
-                           (const uint32_t *)W.read_set.p, (const uint32_t *)W.set_start.p, (const uint32_t *)W.pair_base.p, n_gwin, (uint4 *)W.gwin_tab.p);
-        FSV_HIP(ctx, hipGetLastError());
-        ConsArgs C;
-        C.store = store; C.word_off = (const uint32_t *)W.word_off.p; C.read_len = (const int32_t *)W.len.p;
-        C.read_set = (const uint32_t *)W.read_set.p; C.set_start = (const uint32_t *)W.set_start.p; C.pair_base = (const uint32_t *)W.pair_base.p;
-        C.gwin_off = (const uint32_t *)W.gwin_off.p; C.gwin_read = (const uint32_t *)W.gwin_read.p; C.ovl_c = (const uint4 *)W.ovl_c.p;
-        C.gwin_tab = (const uint4 *)W.gwin_tab.p; C.tasks = (const fsv_wtask *)W.tasks.p;
-        C.paths = (const fsv_wpath *)W.paths.p; C.cwin = (uint8_t *)W.cwin.p; C.cwin_len = (uint16_t *)W.cwin_len.p; C.warn = (uint32_t *)W.warn.p;
-        C.n_reads = B.n_reads;
-        TRY(ensure(ctx, W.changed, (size_t)B.n_reads * 4));
-        FSV_HIP(ctx, hipMemsetAsync(W.changed.p, 0, (size_t)B.n_reads * 4, ctx->stream));
-        C.changed = (uint32_t *)W.changed.p;
-        C.read_dirty = nullptr;
-        C.junction_vote = P.second_round ? 0 : 1;
-        C.ins_dag = P.ins_dag ? 1 : 0;
-        C.cov3 = nullptr;
-        if (P.second_round && B.n_pairs) { TRY(ensure(ctx, W.cov3, (size_t)std::max(1u, n_gwin))); C.cov3 = (uint8_t *)W.cov3.p; }
-        if (B.n_pairs) {
-            TRY(ensure(ctx, W.read_dirty, (size_t)B.n_reads * 4));
-            hipLaunchKernelGGL(k_read_dirty, dim3(B.n_reads), dim3(64), 0, ctx->stream, (const uint4 *)W.ovl_c.p, (const fsv_wpath *)W.paths.p,
-                               (const uint32_t *)W.read_set.p, (const uint32_t *)W.set_start.p, (const uint32_t *)W.pair_base.p, B.n_reads, (uint32_t *)W.read_dirty.p);
-            FSV_HIP(ctx, hipGetLastError());
-            C.read_dirty = (const uint32_t *)W.read_dirty.p;
-        }
-        const bool partition = B.n_pairs && P.partition;
-        SiteArgs SA{};
-        SiteLists SL{};
-        if (partition) {
-            const size_t vec_cap = (size_t)B.n_pairs * 64 + (1u << 20);
-            TRY(ensure(ctx, W.site_cnt, (size_t)std::max(1u, n_gwin) * 4));
-            const size_t rec_cap = (size_t)n_gwin * 4 + 65536;
-            TRY(ensure(ctx, W.site_rec, rec_cap * sizeof(uint2)));
-            TRY(ensure(ctx, W.site_off, (size_t)std::max(1u, n_gwin) * 4));
-            TRY(ensure(ctx, W.site_vec, vec_cap));
-            TRY(ensure(ctx, W.site_cursor, 16));
-            TRY(ensure(ctx, W.redo, (size_t)B.n_reads * 4));
-            TRY(ensure(ctx, W.site_lists, (size_t)std::max(1u, n_gwin) * 8));
-            FSV_HIP(ctx, hipMemsetAsync(W.site_cursor.p, 0, 16, ctx->stream));
-            FSV_HIP(ctx, hipMemsetAsync(W.redo.p, 0, (size_t)B.n_reads * 4, ctx->stream));
-            SA.site_cnt = (uint32_t *)W.site_cnt.p; SA.site_rec = (uint2 *)W.site_rec.p; SA.vec = (int8_t *)W.site_vec.p;
-            SA.site_off = (uint32_t *)W.site_off.p; SA.rec_cursor = (uint32_t *)W.site_cursor.p + 3; SA.rec_cap = (uint32_t)std::min<size_t>(rec_cap, 0xfffffff0u);
-            SA.vec_cursor = (uint32_t *)W.site_cursor.p; SA.vec_cap = (uint32_t)std::min<size_t>(vec_cap, 0xfffffff0u);
-            SA.read_sites = (uint32_t *)W.redo.p;
-            SL.site_cnt = SA.site_cnt; SL.win_list = (uint32_t *)W.site_lists.p; SL.redo_list = SL.win_list + std::max(1u, n_gwin);
-            SL.win_n = (uint32_t *)W.site_cursor.p + 1;
-        }
-        if (partition && P.junction_cigars) {
-            // calculate_boundary_cigars (Correct.cpp:2310): junction tasks -> K5 -> K6 -> which of the new cigars the partition uses
-            uint32_t *ct3 = ct_of(2 * P.n_rounds + 2 + round);
-            TRY(ensure(ctx, W.tasks2, (size_t)task_cap * sizeof(fsv_wtask)));
-            TRY(ensure(ctx, W.res2, (size_t)task_cap * sizeof(fsv_wres)));
-            TRY(ensure(ctx, W.paths2, (size_t)task_cap * sizeof(fsv_wpath)));
-            TRY(ensure(ctx, W.bc_idx, (size_t)task_cap * 4));
-            TRY(ensure(ctx, W.bc_rec, (size_t)task_cap * sizeof(uint4)));
-            TRY(ensure(ctx, W.bc_win, (size_t)(n_gwin + 2) * 12));
-            hipLaunchKernelGGL(k_bcwin_init, dim3(fsv_grid_for(n_gwin + 2, 256)), dim3(256), 0, ctx->stream, (int32_t *)W.bc_win.p, n_gwin + 2);
-            FSV_HIP(ctx, hipGetLastError());
-            BcigArgs BA;
-            BA.tasks = (const fsv_wtask *)W.tasks.p; BA.paths = (const fsv_wpath *)W.paths.p; BA.n_tasks = ct + CT_TASKS;
-            BA.pair_read = (const uint32_t *)W.pair_read.p; BA.read_dirty = (const uint32_t *)W.read_dirty.p; BA.gwin_off = (const uint32_t *)W.gwin_off.p;
-            BA.thr_tab = (const uint8_t *)W.thr_tab.p; BA.k_cap = P.k_cap;
-            BA.tasks2 = (fsv_wtask *)W.tasks2.p; BA.bc_idx = (int32_t *)W.bc_idx.p; BA.n_tasks2 = ct3 + CT_TASKS;
-            BA.n_same = ct3 + CT_B_RETRY; BA.n_used = ct3 + CT_B_LIST;
-            BA.res2 = (const fsv_wres *)W.res2.p; BA.paths2 = (const fsv_wpath *)W.paths2.p; BA.bc_rec = (uint4 *)W.bc_rec.p; BA.bc_win = (int32_t *)W.bc_win.p;
-            W.kt.begin(ctx, KN_PARTITION, 0);
-            hipLaunchKernelGGL(k_bcig_tasks, dim3((fsv_grid_for(task_cap, 256) + 7u) & ~7u), dim3(256), 0, ctx->stream, BA);
-            FSV_HIP(ctx, hipGetLastError());
-            W.kt.end(ctx);
-            W.bc_bpm_rec.push_back(W.kt.begin(ctx, KN_BPM, 0));
-            TRY(fsv_bpm_windows_dev_n(ctx, store, (const fsv_wtask *)W.tasks2.p, task_cap, ct3 + CT_TASKS, (fsv_wres *)W.res2.p, P.k_cap));
-            W.kt.end(ctx);
-            TRY(path_stage(ctx, W, store, (const fsv_wtask *)W.tasks2.p, (const fsv_wres *)W.res2.p, (fsv_wpath *)W.paths2.p, task_cap, (const uint32_t *)(ct3 + CT_TASKS), ct3,
-                           round, wide_bands, P, 2));
-            W.kt.begin(ctx, KN_PARTITION, 0);
-            hipLaunchKernelGGL(k_bcig_accept, dim3(fsv_grid_for(task_cap, 256)), dim3(256), 0, ctx->stream, BA);
-            FSV_HIP(ctx, hipGetLastError());
-            W.kt.end(ctx);
-            SA.bc_idx = (const int32_t *)W.bc_idx.p; SA.bc_rec = (const uint4 *)W.bc_rec.p; SA.bc_paths = (const fsv_wpath *)W.paths2.p;
-            SL.bc_win = (const int32_t *)W.bc_win.p;
-        }
-        // consensus of every window; with the haplotype partition (K7) on, the windows that hold a candidate site are listed on the
-        // way, k_snp_sites / k_hap_partition take the overlaps with the other allele out (is_match 2 / 4: out of the consensus and,
-        // through that, out of what the final pass accepts as verified), and the reads that lost an overlap get their windows redone
-        W.cons_rec.push_back(W.kt.begin(ctx, KN_CONSENSUS, (uint64_t)n_gwin * (96 + 448)));
-        if (wide_bands) {
-            if (partition) hipLaunchKernelGGL((k_consensus<FSV_EV_CAP_WIDE, 1>), dim3((n_gwin + 7u) & ~7u), dim3(64), 0, ctx->stream, C, n_gwin, SL);
-            else hipLaunchKernelGGL((k_consensus<FSV_EV_CAP_WIDE, 0>), dim3((n_gwin + 7u) & ~7u), dim3(64), 0, ctx->stream, C, n_gwin, SL);
-        } else {
-            if (partition) hipLaunchKernelGGL((k_consensus<FSV_EV_CAP, 1>), dim3((n_gwin + 7u) & ~7u), dim3(64), 0, ctx->stream, C, n_gwin, SL);
-            else hipLaunchKernelGGL((k_consensus<FSV_EV_CAP, 0>), dim3((n_gwin + 7u) & ~7u), dim3(64), 0, ctx->stream, C, n_gwin, SL);
-        }
-        FSV_HIP(ctx, hipGetLastError());
-        W.kt.end(ctx);
-        if (partition) {
-            const uint32_t grid_l = std::min<uint32_t>(std::max(1u, n_gwin), (uint32_t)ctx->n_cu * 16);
-            W.kt.begin(ctx, KN_PARTITION, (uint64_t)B.n_reads * 4);
-            hipLaunchKernelGGL(k_snp_sites, dim3(grid_l), dim3(64), 0, ctx->stream, C, SA, SL);
-            FSV_HIP(ctx, hipGetLastError());
-            hipLaunchKernelGGL(k_hap_partition, dim3(B.n_reads), dim3(64), 0, ctx->stream, C, SA, (fsv_ovl *)W.ovl.p, (uint4 *)W.ovl_c.p, SL);
-            FSV_HIP(ctx, hipGetLastError());
-            if (wide_bands) hipLaunchKernelGGL(k_consensus_redo<FSV_EV_CAP_WIDE>, dim3(grid_l), dim3(64), 0, ctx->stream, C, SL);
-            else hipLaunchKernelGGL(k_consensus_redo<FSV_EV_CAP>, dim3(grid_l), dim3(64), 0, ctx->stream, C, SL);
-            FSV_HIP(ctx, hipGetLastError());
-            W.kt.end(ctx);
-        }
-        if (P.second_round && B.n_pairs)
-            TRY(second_pass(ctx, W, B, G, store, P, C, n_gwin, task_cap, (const uint32_t *)(ct + CT_TASKS), ct_of(P.n_rounds + 1 + round), round, wide_bands));
-        TRY(ensure(ctx, W.lb, (size_t)std::max(1u, n_gwin) * 4));
-        hipLaunchKernelGGL(k_newlen, dim3(fsv_grid_for(B.n_reads, 256)), dim3(256), 0, ctx->stream, (const uint32_t *)W.gwin_off.p,
-                           (const uint16_t *)W.cwin_len.p, B.n_reads, (int32_t *)W.new_len.p, (uint32_t *)W.lb.p);
-        FSV_HIP(ctx, hipGetLastError());
-        // the round's one synchronisation: new read lengths (+ this round's counters)
-        std::vector<int32_t> nlen(B.n_reads);
-        FSV_HIP(ctx, hipMemcpyAsync(nlen.data(), W.new_len.p, (size_t)B.n_reads * 4, hipMemcpyDeviceToHost, ctx->stream));
-        FSV_HIP(ctx, hipMemcpyAsync(h_ct.data() + (size_t)round * CT_SLOT, ct, CT_SLOT * 4, hipMemcpyDeviceToHost, ctx->stream));
-        FSV_HIP(ctx, hipMemcpyAsync(h_ct.data() + (size_t)(P.n_rounds + 1 + round) * CT_SLOT, ct_of(P.n_rounds + 1 + round), CT_SLOT * 4, hipMemcpyDeviceToHost, ctx->stream));
-        FSV_HIP(ctx, hipMemcpyAsync(h_ct.data() + (size_t)(2 * P.n_rounds + 2 + round) * CT_SLOT, ct_of(2 * P.n_rounds + 2 + round), CT_SLOT * 4, hipMemcpyDeviceToHost, ctx->stream));
-        FSV_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        if (h_ct[(size_t)round * CT_SLOT + CT_OVERFLOW]) return fsv_fail(ctx, FSV_ECAP, "internal window task buffer overflow");
-        Geometry G2;
-        TRY(make_geometry(ctx, B, nlen, G2, P.w, &mz_fixed));
-        DevBuf &dst = W.store[round & 1];
-        const uint32_t total_words = G2.word_off[B.n_reads];
-        TRY(ensure(ctx, dst, ((size_t)total_words + 8) * 4));
-        // k_repack needs the new offsets/lengths while the old ones are still in use by nothing else: stage them in mz_cnt/new_len
-        TRY(upload(ctx, W.unpack_off, G2.word_off));
-        W.kt.begin(ctx, KN_REPACK, (uint64_t)n_gwin * 384 + (uint64_t)total_words * 4);
-        hipLaunchKernelGGL(k_repack, dim3(B.n_reads), dim3(256), 0, ctx->stream, (const uint32_t *)W.gwin_off.p,
-                           (const uint32_t *)W.lb.p, (const uint8_t *)W.cwin.p, (const uint32_t *)W.unpack_off.p,
-                           (const int32_t *)W.new_len.p, B.n_reads, round + 1 < P.n_rounds ? 1 : 0, (uint32_t *)dst.p);
-        FSV_HIP(ctx, hipGetLastError());
-        W.kt.end(ctx);
-        FSV_HIP(ctx, hipMemsetAsync((uint8_t *)dst.p + (size_t)total_words * 4, 0, 32, ctx->stream));
-        tcs.stop();
-        store = (const uint32_t *)dst.p;
-        len = nlen;
-        for (int32_t l : len) if (l >= 65536) short_reads = false;
-        G = G2;
+// the round's geometry on the device, room for its window tasks
+static int begin_round(fsv_ctx *ctx, AsmWs &W, Round &R)
+{
+    R.ct = W.ct_of(R.row(PASS_WINDOWS));
+    TRY(upload(ctx, W.word_off, R.G.word_off));
+    TRY(upload(ctx, W.len, R.len));
+    TRY(upload(ctx, W.mz_off, R.G.mz_off));
+    TRY(upload(ctx, W.gwin_off, R.G.gwin_off));
+    TRY(upload(ctx, W.gwin_read, R.G.gwin_read));
+    if (R.G.task_bound >= (1ull << 31)) return fsv_fail(ctx, FSV_EUNSUP, "window task bound exceeds 2^31; split the batch");
+    const uint32_t task_cap = R.task_cap = (uint32_t)std::max<uint64_t>(R.G.task_bound, 1);
+    R.n_gwin = R.G.gwin_off[R.B.n_reads];
+    TRY(ensure_each(ctx, task_cap, W.tasks, W.res, W.paths, W.dp_list, W.dp_list_e3, W.dp_list2, W.dp_list3, W.dp_list16, W.dp_wide));
+    TRY(ensure(ctx, W.dp_xwide, R.wide_bands ? task_cap : 16));
+    return FSV_OK;
+}
+
+// K5 on the window tasks, the rescue of unmatched windows and the verdict on every overlap, then K6 on the same tasks
+static int verify_stage(fsv_ctx *ctx, AsmWs &W, const Round &R)
+{
+    const fsv_asm_params &P = R.P; const Batch &B = R.B;
+    uint32_t *ct = R.ct;
+    unsigned long long *cols = (unsigned long long *)(ct + CT_COLS_LO);   // a 64-bit sum in two counter words
+    Span tv(ctx, W.kt, ST_VERIFY);
+    W.kt.begin(ctx, PASS_WINDOWS, KN_BPM, 0);
+    TRY(fsv_bpm_windows_dev_n(ctx, R.store, W.tasks.p, R.task_cap, ct + CT_TASKS, W.res.p, P.k_cap));
+    W.kt.end(ctx);
+    W.kt.begin(ctx, PASS_WINDOWS, KN_RESCUE, (uint64_t)B.n_pairs * sizeof(fsv_ovl) * 2);
+    if (R.wide_bands)
+        FSV_LAUNCH(ctx, ctx->stream, k_rescue_accept<true>, dim3(fsv_grid_for(B.n_pairs, 64)), dim3(64), 0, R.store, W.ovl.p, B.n_pairs, W.tasks.p, W.res.p, cols,
+                   W.ovl_c.p, P.k_cap, P.accept_err_pm, (uint32_t *)nullptr, (uint32_t *)nullptr);
+    else {
+        // the right-extension pass and the verdict in one kernel; an overlap with an unmatched window LEFT of a matched one is set
+        // aside for the left-extension pass (k_left_rescue: it needs the matched window's path first), which then gives its verdict
+        TRY(ensure(ctx, W.left_list, (size_t)B.n_pairs + 4));
+        FSV_LAUNCH(ctx, ctx->stream, k_rescue_accept<false>, dim3(fsv_grid_for(B.n_pairs, 64)), dim3(64), 0, R.store, W.ovl.p, B.n_pairs, W.tasks.p, W.res.p, cols,
+                   W.ovl_c.p, P.k_cap, P.accept_err_pm, W.left_list.p, ct + CT_LEFT);
+        const uint32_t gridl = std::min<uint32_t>(std::max(1u, B.n_pairs), 8u * (uint32_t)ctx->n_cu);
+        FSV_LAUNCH(ctx, ctx->stream, k_left_rescue, dim3(gridl), dim3(64), 0, R.store, W.ovl.p, W.left_list.p, ct + CT_LEFT, W.tasks.p, W.res.p, W.paths.p,
+                   (uint64_t *)nullptr, W.ovl_c.p, P.k_cap, P.accept_err_pm);
     }
+    W.kt.end(ctx);
+    tv.stop();
+    Span tp(ctx, W.kt, ST_PATH);
+    TRY(path_stage(ctx, W, PathJob{R.store, W.tasks.p, W.res.p, W.paths.p, R.task_cap, R.ct + CT_TASKS, R.ct, PASS_WINDOWS, R.round, R.wide_bands, R.P.k_cap, false}));
+    tp.stop();
+    return FSV_OK;
+}
 
-    // final overlaps on the corrected reads
-    Span tf(ctx, W.kt, ST_FINAL);
-    uint32_t *ctf = ct_of(P.n_rounds);
-    auto tr0 = std::chrono::steady_clock::now();
-    auto trace = [&](const char *what) { if (getenv("FSV_TRACE")) { (void)hipStreamSynchronize(ctx->stream); auto t = std::chrono::steady_clock::now(); fprintf(stderr, "[fsv] final %-14s %.2f ms\n", what, std::chrono::duration<double, std::milli>(t - tr0).count()); tr0 = t; } };
-    TRY(upload(ctx, W.word_off, G.word_off));
-    TRY(upload(ctx, W.len, len));
-    TRY(upload(ctx, W.mz_off, G.mz_off));
-    TRY(ensure(ctx, W.tasks, 64));
+// room for the corrected windows, the per-window table, the consensus kernels' arguments (R.C), the reads whose overlaps changed
+static int consensus_setup(fsv_ctx *ctx, AsmWs &W, Round &R)
+{
+    const fsv_asm_params &P = R.P; const Batch &B = R.B;
+    const uint32_t n_gwin = R.n_gwin;
+    TRY(ensure(ctx, W.cwin, (size_t)n_gwin * FSV_CW_STRIDE));
+    TRY(ensure(ctx, W.cwin_len, n_gwin));
+    TRY(ensure(ctx, W.new_len, B.n_reads));
+    if (!B.n_pairs) TRY(zero(ctx, W.ovl_c, 1));
+    TRY(ensure(ctx, W.gwin_tab, std::max(1u, n_gwin)));
+    FSV_LAUNCH(ctx, ctx->stream, k_gwin_tab, dim3(fsv_grid_for(n_gwin, 256)), dim3(256), 0, W.gwin_read.p, W.gwin_off.p, W.read_set.p, W.set_start.p, W.pair_base.p, n_gwin,
+               W.gwin_tab.p);
+    ConsArgs &C = R.C;
+    C.store = R.store; C.word_off = W.word_off.p; C.read_len = W.len.p;
+    C.read_set = W.read_set.p; C.set_start = W.set_start.p; C.pair_base = W.pair_base.p;
+    C.gwin_off = W.gwin_off.p; C.gwin_read = W.gwin_read.p; C.ovl_c = W.ovl_c.p;
+    C.gwin_tab = W.gwin_tab.p; C.tasks = W.tasks.p;
+    C.paths = W.paths.p; C.cwin = W.cwin.p; C.cwin_len = W.cwin_len.p; C.warn = W.warn.p;
+    C.n_reads = B.n_reads;
+    TRY(ensure(ctx, W.changed, B.n_reads));
+    TRY(zero(ctx, W.changed, B.n_reads));
+    C.changed = W.changed.p;
+    C.read_dirty = nullptr;
+    C.junction_vote = P.second_round ? 0 : 1;
+    C.ins_dag = P.ins_dag ? 1 : 0;
+    C.cov3 = nullptr;
+    if (P.second_round && B.n_pairs) { TRY(ensure(ctx, W.cov3, std::max(1u, n_gwin))); C.cov3 = W.cov3.p; }
+    if (B.n_pairs) {
+        TRY(ensure(ctx, W.read_dirty, B.n_reads));
+        FSV_LAUNCH(ctx, ctx->stream, k_read_dirty, dim3(B.n_reads), dim3(64), 0, W.ovl_c.p, W.paths.p, W.read_set.p, W.set_start.p, W.pair_base.p, B.n_reads, W.read_dirty.p);
+        C.read_dirty = W.read_dirty.p;
+    }
+    return FSV_OK;
+}
+
+// the haplotype partition's (K7) site records, vectors and window lists
+static int partition_setup(fsv_ctx *ctx, AsmWs &W, const Round &R, SiteArgs &SA, SiteLists &SL)
+{
+    const Batch &B = R.B;
+    const uint32_t n_gwin = R.n_gwin;
+    const size_t vec_cap = (size_t)B.n_pairs * 64 + (1u << 20);
+    TRY(ensure(ctx, W.site_cnt, std::max(1u, n_gwin)));
+    const size_t rec_cap = (size_t)n_gwin * 4 + 65536;
+    TRY(ensure(ctx, W.site_rec, rec_cap));
+    TRY(ensure(ctx, W.site_off, std::max(1u, n_gwin)));
+    TRY(ensure(ctx, W.site_vec, vec_cap));
+    TRY(ensure(ctx, W.site_cursor, 4));
+    TRY(ensure(ctx, W.redo, B.n_reads));
+    TRY(ensure(ctx, W.site_lists, (size_t)std::max(1u, n_gwin) * 2));
+    TRY(zero(ctx, W.site_cursor, 4));
+    TRY(zero(ctx, W.redo, B.n_reads));
+    SA.site_cnt = W.site_cnt.p; SA.site_rec = W.site_rec.p; SA.vec = W.site_vec.p;
+    SA.site_off = W.site_off.p; SA.rec_cursor = W.site_cursor.p + 3; SA.rec_cap = (uint32_t)std::min<size_t>(rec_cap, 0xfffffff0u);
+    SA.vec_cursor = W.site_cursor.p; SA.vec_cap = (uint32_t)std::min<size_t>(vec_cap, 0xfffffff0u);
+    SA.read_sites = W.redo.p;
+    SL.site_cnt = SA.site_cnt; SL.win_list = W.site_lists.p; SL.redo_list = SL.win_list + std::max(1u, n_gwin);
+    SL.win_n = W.site_cursor.p + 1;
+    return FSV_OK;
+}
+
+// calculate_boundary_cigars (Correct.cpp:2310): junction tasks -> K5 -> K6 -> which of the new cigars the partition uses
+static int junction_cigars(fsv_ctx *ctx, AsmWs &W, const Round &R, SiteArgs &SA, SiteLists &SL)
+{
+    const fsv_asm_params &P = R.P;
+    const uint32_t n_gwin = R.n_gwin, task_cap = R.task_cap;
+    uint32_t *ct3 = W.ct_of(R.row(PASS_BCIG));
+    TRY(ensure_each(ctx, task_cap, W.tasks2, W.res2, W.paths2, W.bc_idx, W.bc_rec));
+    TRY(ensure(ctx, W.bc_win, (size_t)(n_gwin + 2) * 3));
+    FSV_LAUNCH(ctx, ctx->stream, k_bcwin_init, dim3(fsv_grid_for(n_gwin + 2, 256)), dim3(256), 0, W.bc_win.p, n_gwin + 2);
+    BcigArgs BA;
+    BA.tasks = W.tasks.p; BA.paths = W.paths.p; BA.n_tasks = R.ct + CT_TASKS;
+    BA.pair_read = W.pair_read.p; BA.read_dirty = W.read_dirty.p; BA.gwin_off = W.gwin_off.p;
+    BA.thr_tab = W.thr_tab.p; BA.k_cap = P.k_cap;
+    BA.tasks2 = W.tasks2.p; BA.bc_idx = W.bc_idx.p; BA.n_tasks2 = ct3 + CT_TASKS;
+    BA.n_same = ct3 + CT_B_RETRY; BA.n_used = ct3 + CT_B_LIST;
+    BA.res2 = W.res2.p; BA.paths2 = W.paths2.p; BA.bc_rec = W.bc_rec.p; BA.bc_win = W.bc_win.p;
+    W.kt.begin(ctx, KN_PARTITION, 0);
+    FSV_LAUNCH(ctx, ctx->stream, k_bcig_tasks, dim3((fsv_grid_for(task_cap, 256) + 7u) & ~7u), dim3(256), 0, BA);
+    W.kt.end(ctx);
+    W.kt.begin(ctx, PASS_BCIG, KN_BPM, 0);
+    TRY(fsv_bpm_windows_dev_n(ctx, R.store, W.tasks2.p, task_cap, ct3 + CT_TASKS, W.res2.p, P.k_cap));
+    W.kt.end(ctx);
+    TRY(path_stage(ctx, W, PathJob{R.store, W.tasks2.p, W.res2.p, W.paths2.p, task_cap, ct3 + CT_TASKS, ct3, PASS_BCIG, R.round, R.wide_bands, P.k_cap, false}));
+    W.kt.begin(ctx, KN_PARTITION, 0);
+    FSV_LAUNCH(ctx, ctx->stream, k_bcig_accept, dim3(fsv_grid_for(task_cap, 256)), dim3(256), 0, BA);
+    W.kt.end(ctx);
+    SA.bc_idx = W.bc_idx.p; SA.bc_rec = W.bc_rec.p; SA.bc_paths = W.paths2.p;
+    SL.bc_win = W.bc_win.p;
+    return FSV_OK;
+}
+
+// consensus of every window; with the haplotype partition (K7) on, the windows that hold a candidate site are listed on the
+// way, k_snp_sites / k_hap_partition take the overlaps with the other allele out (is_match 2 / 4: out of the consensus and,
+// through that, out of what the final pass accepts as verified), and the reads that lost an overlap get their windows redone
+static int consensus_stage(fsv_ctx *ctx, AsmWs &W, Round &R)
+{
+    const fsv_asm_params &P = R.P; const Batch &B = R.B;
+    const uint32_t n_gwin = R.n_gwin;
+    TRY(consensus_setup(ctx, W, R));
+    const ConsArgs &C = R.C;
+    const bool partition = B.n_pairs && P.partition;
+    SiteArgs SA{};
+    SiteLists SL{};
+    if (partition) TRY(partition_setup(ctx, W, R, SA, SL));
+    if (partition && P.junction_cigars) TRY(junction_cigars(ctx, W, R, SA, SL));
+    const dim3 grid_w((n_gwin + 7u) & ~7u);
+    W.kt.begin(ctx, PASS_WINDOWS, KN_CONSENSUS, (uint64_t)n_gwin * (96 + 448));
+    if (R.wide_bands) {
+        if (partition) FSV_LAUNCH(ctx, ctx->stream, (k_consensus<FSV_EV_CAP_WIDE, 1>), grid_w, dim3(64), 0, C, n_gwin, SL);
+        else FSV_LAUNCH(ctx, ctx->stream, (k_consensus<FSV_EV_CAP_WIDE, 0>), grid_w, dim3(64), 0, C, n_gwin, SL);
+    } else {
+        if (partition) FSV_LAUNCH(ctx, ctx->stream, (k_consensus<FSV_EV_CAP, 1>), grid_w, dim3(64), 0, C, n_gwin, SL);
+        else FSV_LAUNCH(ctx, ctx->stream, (k_consensus<FSV_EV_CAP, 0>), grid_w, dim3(64), 0, C, n_gwin, SL);
+    }
+    W.kt.end(ctx);
+    if (partition) {
+        const uint32_t grid_l = std::min<uint32_t>(std::max(1u, n_gwin), (uint32_t)ctx->n_cu * 16);
+        W.kt.begin(ctx, KN_PARTITION, (uint64_t)B.n_reads * 4);
+        FSV_LAUNCH(ctx, ctx->stream, k_snp_sites, dim3(grid_l), dim3(64), 0, C, SA, SL);
+        FSV_LAUNCH(ctx, ctx->stream, k_hap_partition, dim3(B.n_reads), dim3(64), 0, C, SA, W.ovl.p, W.ovl_c.p, SL);
+        if (R.wide_bands) FSV_LAUNCH(ctx, ctx->stream, k_consensus_redo<FSV_EV_CAP_WIDE>, dim3(grid_l), dim3(64), 0, C, SL);
+        else FSV_LAUNCH(ctx, ctx->stream, k_consensus_redo<FSV_EV_CAP>, dim3(grid_l), dim3(64), 0, C, SL);
+        W.kt.end(ctx);
+    }
+    return FSV_OK;
+}
+
+// new read lengths -> the round's one synchronisation (the round's counters ride along) -> the next geometry -> the corrected reads
+// repacked into the other store
+static int finish_round(fsv_ctx *ctx, AsmWs &W, Round &R)
+{
+    const fsv_asm_params &P = R.P; const Batch &B = R.B;
+    const uint32_t n_gwin = R.n_gwin;
+    TRY(ensure(ctx, W.lb, std::max(1u, n_gwin)));
+    FSV_LAUNCH(ctx, ctx->stream, k_newlen, dim3(fsv_grid_for(B.n_reads, 256)), dim3(256), 0, W.gwin_off.p, W.cwin_len.p, B.n_reads, W.new_len.p, W.lb.p);
+    std::vector<int32_t> nlen(B.n_reads);
+    TRY(download(ctx, nlen.data(), W.new_len, B.n_reads));
+    for (int pass = 0; pass < PASS_COUNT; pass++)
+        FSV_HIP(ctx, hipMemcpyAsync(R.h_ct.data() + (size_t)R.row(pass) * CT_SLOT, W.ct_of(R.row(pass)), CT_SLOT * 4, hipMemcpyDeviceToHost, ctx->stream));
+    FSV_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (R.h_ct[(size_t)R.round * CT_SLOT + CT_OVERFLOW]) return fsv_fail(ctx, FSV_ECAP, "internal window task buffer overflow");
+    Geometry G2;
+    TRY(make_geometry(ctx, B, nlen, G2, P.w, &R.mz_fixed));
+    Dev<uint32_t> &dst = W.store[R.round & 1];
+    const uint32_t total_words = G2.word_off[B.n_reads];
+    TRY(ensure(ctx, dst, (size_t)total_words + 8));
+    // k_repack needs the new offsets while the old ones are still in use: they go up in a buffer of their own
+    TRY(upload(ctx, W.unpack_off, G2.word_off));
+    W.kt.begin(ctx, KN_REPACK, (uint64_t)n_gwin * 384 + (uint64_t)total_words * 4);
+    FSV_LAUNCH(ctx, ctx->stream, k_repack, dim3(B.n_reads), dim3(256), 0, W.gwin_off.p, W.lb.p, W.cwin.p, W.unpack_off.p, W.new_len.p, B.n_reads,
+               R.round + 1 < P.n_rounds ? 1 : 0, dst.p);
+    W.kt.end(ctx);
+    FSV_HIP(ctx, hipMemsetAsync(dst.p + total_words, 0, 32, ctx->stream));
+    R.store = dst.p;
+    R.len = nlen;
+    for (int32_t l : R.len) if (l >= 65536) R.short_reads = false;
+    R.G = G2;
+    return FSV_OK;
+}
+
+// What the final pass hands from the hit gather to the layout, the contigs and the statistics
+struct SetLayout { std::vector<std::vector<Piece>> contigs; bool fallback = false; };
+struct Final {
+    std::vector<uint32_t> hit_first, hwarn, h_setcols;   // hits of set s: [hit_first[s], hit_first[s + 1]); per-read warnings; K5 columns per set
+    const fsv_hit *hraw = nullptr;                        // the hits, grouped by set (pinned host memory)
+    bool any_inexact = false;                             // some set's layout compares bases: W.h_store holds its reads
+    std::vector<SetLayout> lay;
+    uint64_t used = 0;                                    // contig bases written
+    // FSV_TRACE: the host's view of the final pass, step by step (each line waits for the stream)
+    fsv_ctx *ctx; std::chrono::steady_clock::time_point tr0 = std::chrono::steady_clock::now();
+    void trace(const char *what) { if (getenv("FSV_TRACE")) { (void)hipStreamSynchronize(ctx->stream); auto t = std::chrono::steady_clock::now(); fprintf(stderr, "[fsv] final %-14s %.2f ms\n", what, std::chrono::duration<double, std::milli>(t - tr0).count()); tr0 = t; } }
+};
+
+// final overlaps on the corrected reads: the exact ones (k_exact), and the inexact ones the last correction round had verified
+static int final_overlaps(fsv_ctx *ctx, AsmWs &W, Round &R, Final &F)
+{
+    const fsv_asm_params &P = R.P; const Batch &B = R.B;
+    R.ct = W.ct_of(P.n_rounds); R.task_cap = 0;      // (the final pass emits no window tasks)
+    TRY(upload(ctx, W.word_off, R.G.word_off));
+    TRY(upload(ctx, W.len, R.len));
+    TRY(upload(ctx, W.mz_off, R.G.mz_off));
+    TRY(ensure(ctx, W.tasks, 2));
     // what the last correction round verified (coordinates on the reads as they were before that round) -- the final pass
     // accepts inexact overlaps against it; the slots are about to be overwritten
     const bool have_prev = P.n_rounds > 0 && B.n_pairs > 0;
     if (have_prev) {
-        TRY(ensure(ctx, W.ovl_prev, (size_t)B.n_pairs * sizeof(fsv_ovl)));
+        TRY(ensure(ctx, W.ovl_prev, B.n_pairs));
         FSV_HIP(ctx, hipMemcpyAsync(W.ovl_prev.p, W.ovl.p, (size_t)B.n_pairs * sizeof(fsv_ovl), hipMemcpyDeviceToDevice, ctx->stream));
     }
-    // reads the last round left untouched keep that round's minimizer lists (the last round does not reverse-complement)
-    const int w_final = P.w_later > 0 ? P.w_later : P.w;
-    // (the final pass keeps the lists of unchanged reads only when the last round sketched with the same window)
-    const bool keep_lists = P.n_rounds > 0 && (P.n_rounds > 1 || w_final == P.w);
-    // hifiasm's final pass keeps every pair that shares a minimizer on a strand, however short the overlap (the graph sorts them out)
-    fsv_asm_params Pf = P;
-    if (P.min_anchors_final > 0) Pf.min_anchors = P.min_anchors_final;
-    if (P.min_ovlp_final > 0) Pf.min_ovlp = P.min_ovlp_final;
-    TRY(overlap_stage(ctx, W, B, G, store, Pf, P.bw_final, false, 0, ctf, short_reads, wide_bands && w_final == P.w, w_final, keep_lists ? (const uint32_t *)W.changed.p : nullptr));
-    trace("overlaps");
-    const fsv_hit *hraw = nullptr;
-    std::vector<uint32_t> hit_first(B.n_sets + 1, 0);
-    std::vector<uint32_t> hwarn(B.n_reads), h_setcols(B.n_reads, 0u);
-    if (B.n_pairs) {
-        TRY(ensure(ctx, W.hits, (size_t)B.n_pairs * sizeof(fsv_hit)));
-        TRY(ensure(ctx, W.set_hits, (size_t)(2 * B.n_sets + 2) * 4));
-        FSV_HIP(ctx, hipMemsetAsync(W.set_hits.p, 0, (size_t)B.n_sets * 4, ctx->stream));
-        W.kt.begin(ctx, KN_EXACT, (uint64_t)B.n_pairs * sizeof(fsv_ovl) + W.stats.n_pairs * 0);
-        TRY(ensure(ctx, W.exact_flag, (size_t)B.n_upairs + 16));
-        hipLaunchKernelGGL(k_exact, dim3(B.n_upairs), dim3(64), 0, ctx->stream, store, (const uint32_t *)W.word_off.p, (const int32_t *)W.len.p,
-                           (const uint32_t *)W.read_set.p, (const uint32_t *)W.pair_base.p, (const uint4 *)W.upair_tab.p, (const fsv_ovl *)W.ovl.p,
-                           (fsv_hit *)W.hits.p, (uint32_t *)W.set_hits.p, (uint8_t *)W.exact_flag.p);
-        FSV_HIP(ctx, hipGetLastError());
-        W.kt.end(ctx);
-        if (have_prev) {
-            // pairs without an exact overlap that the last correction round had verified: gapped re-chain, accept per direction.
-            // The list's length stays on the device: the re-chain is launched over every pair slot and the blocks beyond the list
-            // return at once (a few hundred pairs are listed out of hundreds of thousands; the empty blocks cost ~40 us)
-            TRY(ensure(ctx, W.inexact_list, (size_t)B.n_upairs * 4 + 16));
-            uint32_t *n_list_dev = ctf + CT_INEXACT;
-            hipLaunchKernelGGL(k_inexact_list, dim3(fsv_grid_for(B.n_upairs, 256)), dim3(256), 0, ctx->stream, (const uint4 *)W.upair_tab.p,
-                               (const uint8_t *)W.exact_flag.p, (const fsv_ovl *)W.ovl_prev.p, B.n_upairs, (uint32_t *)W.inexact_list.p, n_list_dev);
-            FSV_HIP(ctx, hipGetLastError());
-            ChainArgs A2 = W.last_chain;
-            A2.bw = P.bw_rechain; A2.emit_tasks = 0; A2.pair_list = (const uint32_t *)W.inexact_list.p; A2.n_list_dev = n_list_dev;
-            // Either direction of a listed pair is chained from its own side, as hifiasm does: with an indel budget the chain DP depends
-            // on the end it starts from (the budget is a rate over the span chained so far; on the reverse strand the two sides start
-            // from opposite ends), and the mirror image of one side's chain can be off by the bases of an indel near a read end.
-            A2.primary_only = 1;
-            TRY(ensure(ctx, W.upair_tab_sw, (size_t)std::max(1u, B.n_upairs) * sizeof(uint4)));
-            hipLaunchKernelGGL(k_pair_tab_swap, dim3(fsv_grid_for(B.n_upairs, 256)), dim3(256), 0, ctx->stream, (const uint4 *)W.upair_tab.p, B.n_upairs, (uint4 *)W.upair_tab_sw.p);
-            FSV_HIP(ctx, hipGetLastError());
-            // timed like the other k_chain launches (a profiler counts it too)
-            W.kt.begin(ctx, KN_CHAIN, 0);
-            for (int side = 0; side < 2; side++) {
-                if (side == 1) A2.upair_tab = (const uint4 *)W.upair_tab_sw.p;
-                if (A2.wide_list) FSV_HIP(ctx, hipMemsetAsync(A2.n_wide, 0, 4, ctx->stream));   // (the final pass's own wide pairs are done)
-                if (short_reads) { TRY(lds_opt_in(ctx, k_chain<true>, chain_lds_bytes(true, A2.amax))); hipLaunchKernelGGL(k_chain<true>, dim3(B.n_upairs), dim3(64), chain_lds_bytes(true, A2.amax), ctx->stream, A2); }
-                else { TRY(lds_opt_in(ctx, k_chain<false>, chain_lds_bytes(false, A2.amax))); hipLaunchKernelGGL(k_chain<false>, dim3(B.n_upairs), dim3(64), chain_lds_bytes(false, A2.amax), ctx->stream, A2); }
-                FSV_HIP(ctx, hipGetLastError());
-                if (A2.wide_list) {
-                    ChainArgs AW = A2;
-                    AW.amax = short_reads ? FSV_AMAX_WIDE : FSV_AMAX_WIDE_LONG; AW.pair_list = nullptr; AW.n_list_dev = nullptr;
-                    const uint32_t gridw = std::min<uint32_t>(B.n_upairs, 2u * (uint32_t)ctx->n_cu);
-                    if (short_reads) { TRY(lds_opt_in(ctx, k_chain_wide_list<true>, chain_lds_bytes(true, AW.amax))); hipLaunchKernelGGL(k_chain_wide_list<true>, dim3(gridw), dim3(64), chain_lds_bytes(true, AW.amax), ctx->stream, AW); }
-                    else { TRY(lds_opt_in(ctx, k_chain_wide_list<false>, chain_lds_bytes(false, AW.amax))); hipLaunchKernelGGL(k_chain_wide_list<false>, dim3(gridw), dim3(64), chain_lds_bytes(false, AW.amax), ctx->stream, AW); }
-                    FSV_HIP(ctx, hipGetLastError());
-                }
-            }
-            W.kt.end(ctx);
-            hipLaunchKernelGGL(k_accept_inexact, dim3(fsv_grid_for(2ull * B.n_upairs, 256)), dim3(256), 0, ctx->stream, (const uint4 *)W.upair_tab.p,
-                               (const uint32_t *)W.inexact_list.p, 0u, (const fsv_ovl *)W.ovl.p, (const fsv_ovl *)W.ovl_prev.p,
-                               (const uint32_t *)W.read_set.p, (const uint32_t *)W.pair_base.p, (fsv_hit *)W.hits.p, (uint32_t *)W.set_hits.p,
-                               (const uint32_t *)n_list_dev);
-            FSV_HIP(ctx, hipGetLastError());
-        }
-        // per-set counts -> offsets; the segments are packed on the device and come back in one copy, already grouped by set.
-        // The order inside a set depends on atomics and does not matter: the layout's containment marks and "longest arc,
-        // smallest target on ties" choices are order-independent.  The warnings and the batch's counters ride along.
-        FSV_HIP(ctx, hipMemcpyAsync(hit_first.data() + 1, W.set_hits.p, (size_t)B.n_sets * 4, hipMemcpyDeviceToHost, ctx->stream));
+    TRY(overlap_stage(ctx, W, R, true));
+    F.trace("overlaps");
+    if (!B.n_pairs) return FSV_OK;
+    TRY(ensure(ctx, W.hits, B.n_pairs));
+    TRY(ensure(ctx, W.set_hits, (size_t)2 * B.n_sets + 2));
+    TRY(zero(ctx, W.set_hits, B.n_sets));
+    W.kt.begin(ctx, KN_EXACT, (uint64_t)B.n_pairs * sizeof(fsv_ovl));
+    TRY(ensure(ctx, W.exact_flag, (size_t)B.n_upairs + 16));
+    FSV_LAUNCH(ctx, ctx->stream, k_exact, dim3(B.n_upairs), dim3(64), 0, R.store, W.word_off.p, W.len.p, W.read_set.p, W.pair_base.p, W.upair_tab.p, W.ovl.p,
+               W.hits.p, W.set_hits.p, W.exact_flag.p);
+    W.kt.end(ctx);
+    if (!have_prev) return FSV_OK;
+    // pairs without an exact overlap that the last correction round had verified: gapped re-chain, accept per direction.
+    // The list's length stays on the device: the re-chain is launched over every pair slot and the blocks beyond the list
+    // return at once (a few hundred pairs are listed out of hundreds of thousands; the empty blocks cost ~40 us)
+    TRY(ensure(ctx, W.inexact_list, (size_t)B.n_upairs + 4));
+    uint32_t *n_list_dev = R.ct + CT_INEXACT;
+    FSV_LAUNCH(ctx, ctx->stream, k_inexact_list, dim3(fsv_grid_for(B.n_upairs, 256)), dim3(256), 0, W.upair_tab.p, W.exact_flag.p, W.ovl_prev.p, B.n_upairs,
+               W.inexact_list.p, n_list_dev);
+    ChainArgs A2 = W.last_chain;
+    A2.bw = P.bw_rechain; A2.emit_tasks = 0; A2.pair_list = W.inexact_list.p; A2.n_list_dev = n_list_dev;
+    // Either direction of a listed pair is chained from its own side, as hifiasm does: with an indel budget the chain DP depends
+    // on the end it starts from (the budget is a rate over the span chained so far; on the reverse strand the two sides start
+    // from opposite ends), and the mirror image of one side's chain can be off by the bases of an indel near a read end.
+    A2.primary_only = 1;
+    TRY(ensure(ctx, W.upair_tab_sw, std::max(1u, B.n_upairs)));
+    FSV_LAUNCH(ctx, ctx->stream, k_pair_tab_swap, dim3(fsv_grid_for(B.n_upairs, 256)), dim3(256), 0, W.upair_tab.p, B.n_upairs, W.upair_tab_sw.p);
+    // timed like the other k_chain launches (a profiler counts it too)
+    W.kt.begin(ctx, KN_CHAIN, 0);
+    for (int side = 0; side < 2; side++) {
+        if (side == 1) A2.upair_tab = W.upair_tab_sw.p;
+        if (A2.wide_list) FSV_HIP(ctx, hipMemsetAsync(A2.n_wide, 0, 4, ctx->stream));   // (the final pass's own wide pairs are done)
+        TRY(launch_chain(ctx, CHAIN_PAIRS, R.short_reads, B.n_upairs, A2, B.n_upairs));
+        if (A2.wide_list) TRY(chain_wide_pairs(ctx, A2, R.short_reads, B.n_upairs));
     }
-    FSV_HIP(ctx, hipMemcpyAsync(hwarn.data(), W.warn.p, (size_t)B.n_reads * 4, hipMemcpyDeviceToHost, ctx->stream));
-    FSV_HIP(ctx, hipMemcpyAsync(h_setcols.data(), W.set_cols.p, (size_t)B.n_reads * 4, hipMemcpyDeviceToHost, ctx->stream));
-    FSV_HIP(ctx, hipMemcpyAsync(h_ct.data() + (size_t)P.n_rounds * CT_SLOT, ctf, CT_SLOT * 4, hipMemcpyDeviceToHost, ctx->stream));
+    W.kt.end(ctx);
+    FSV_LAUNCH(ctx, ctx->stream, k_accept_inexact, dim3(fsv_grid_for(2ull * B.n_upairs, 256)), dim3(256), 0, W.upair_tab.p, W.inexact_list.p, 0u, W.ovl.p, W.ovl_prev.p,
+               W.read_set.p, W.pair_base.p, W.hits.p, W.set_hits.p, n_list_dev);
+    return FSV_OK;
+}
+
+// per-set counts -> offsets; the segments are packed on the device and come back in one copy, already grouped by set.
+// The order inside a set depends on atomics and does not matter: the layout's containment marks and "longest arc,
+// smallest target on ties" choices are order-independent.  The warnings and the batch's counters ride along.
+static int gather_hits(fsv_ctx *ctx, AsmWs &W, Round &R, Final &F)
+{
+    const Batch &B = R.B;
+    F.hit_first.assign(B.n_sets + 1, 0);
+    F.hwarn.resize(B.n_reads); F.h_setcols.assign(B.n_reads, 0u);
+    if (B.n_pairs) TRY(download(ctx, F.hit_first.data() + 1, W.set_hits, B.n_sets));
+    TRY(download(ctx, F.hwarn.data(), W.warn, B.n_reads));
+    TRY(download(ctx, F.h_setcols.data(), W.set_cols, B.n_reads));
+    FSV_HIP(ctx, hipMemcpyAsync(R.h_ct.data() + (size_t)R.P.n_rounds * CT_SLOT, R.ct, CT_SLOT * 4, hipMemcpyDeviceToHost, ctx->stream));
     FSV_HIP(ctx, hipStreamSynchronize(ctx->stream));
     if (B.n_pairs) {
-        for (uint32_t s2 = 0; s2 < B.n_sets; s2++) hit_first[s2 + 1] += hit_first[s2];
+        std::vector<uint32_t> &hit_first = F.hit_first;
+        for (uint32_t s = 0; s < B.n_sets; s++) hit_first[s + 1] += hit_first[s];
         const uint32_t nh = hit_first[B.n_sets];
         if ((size_t)nh * sizeof(fsv_hit) > W.h_pin_cap) {
             if (W.h_pin) FSV_HIP(ctx, hipHostFree(W.h_pin));
             W.h_pin = nullptr; W.h_pin_cap = (size_t)nh * sizeof(fsv_hit) * 5 / 4 + 4096;
             FSV_HIP(ctx, hipHostMalloc(&W.h_pin, W.h_pin_cap, hipHostMallocDefault));
         }
-        hraw = (const fsv_hit *)W.h_pin;
+        F.hraw = (const fsv_hit *)W.h_pin;
         if (nh) {
-            uint32_t *first_dev = (uint32_t *)W.set_hits.p + B.n_sets;
-            TRY(ensure(ctx, W.hits_packed, (size_t)nh * sizeof(fsv_hit)));
+            uint32_t *first_dev = W.set_hits.p + B.n_sets;   // the offsets go behind the counts
+            TRY(ensure(ctx, W.hits_packed, nh));
             FSV_HIP(ctx, hipMemcpyAsync(first_dev, hit_first.data(), (size_t)(B.n_sets + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
-            hipLaunchKernelGGL(k_hits_compact, dim3(B.n_sets), dim3(256), 0, ctx->stream, (const fsv_hit *)W.hits.p, (const uint32_t *)W.pair_base.p,
-                               (const uint32_t *)first_dev, (fsv_hit *)W.hits_packed.p);
-            FSV_HIP(ctx, hipGetLastError());
-            FSV_HIP(ctx, hipMemcpyAsync(W.h_pin, W.hits_packed.p, (size_t)nh * sizeof(fsv_hit), hipMemcpyDeviceToHost, ctx->stream));
+            FSV_LAUNCH(ctx, ctx->stream, k_hits_compact, dim3(B.n_sets), dim3(256), 0, W.hits.p, W.pair_base.p, first_dev, W.hits_packed.p);
+            TRY(download(ctx, (fsv_hit *)W.h_pin, W.hits_packed, nh));
             FSV_HIP(ctx, hipStreamSynchronize(ctx->stream));
         }
         W.stats.n_exact_overlaps = nh;
     }
-    trace("exact+gather");
+    F.trace("exact+gather");
+    return FSV_OK;
+}
 
+// layout per set on the host.  The sets are independent: they are laid out on a few host threads
+static int layout_sets(fsv_ctx *ctx, AsmWs &W, const Round &R, Final &F)
+{
+    const fsv_asm_params &P = R.P; const Batch &B = R.B; const Geometry &G = R.G;
+    const std::vector<int32_t> &len = R.len;
+    const std::vector<uint32_t> &hit_first = F.hit_first;
+    const fsv_hit *hraw = F.hraw;
     // the unitig polishing compares reads base for base where they are joined by an inexact overlap (low coverage only): the
     // corrected reads then come to the host too, 2 bits a base (24 MB for 256 regions)
     // (only the reads of the sets that hold an inexact overlap: a handful of sets, ~200 KB each.  Since the correction rounds keep
@@ -1058,74 +1035,78 @@ static int assemble_chunk(fsv_ctx *ctx, const fsv_readsets *sets, const fsv_asm_
             if (!any_inexact && h_store.size() < (size_t)G.word_off[B.n_reads] + 1) h_store.resize((size_t)G.word_off[B.n_reads] + 1);
             any_inexact = true;
             const uint32_t w0 = G.word_off[B.set_start[s2]], w1 = G.word_off[B.set_start[s2 + 1]];
-            if (w1 > w0) FSV_HIP(ctx, hipMemcpyAsync(h_store.data() + w0, store + w0, (size_t)(w1 - w0) * 4, hipMemcpyDeviceToHost, ctx->stream));
+            if (w1 > w0) FSV_HIP(ctx, hipMemcpyAsync(h_store.data() + w0, R.store + w0, (size_t)(w1 - w0) * 4, hipMemcpyDeviceToHost, ctx->stream));
         }
         if (any_inexact) FSV_HIP(ctx, hipStreamSynchronize(ctx->stream));
     }
-    const uint8_t *set_flags = sets->set_flags;
-    // layout per set (host), then stitch on the device
+    F.any_inexact = any_inexact;
+    const uint8_t *set_flags = R.set_flags;
+    std::vector<SetLayout> &lay = F.lay;
+    lay.resize(B.n_sets);
+    const uint32_t nthr = std::max(1u, std::min({8u, std::thread::hardware_concurrency(), B.n_sets / 16 + 1}));
+    std::atomic<uint32_t> next{0};
+    // a worker never lets an exception out (it would end the process): the first failure is kept and returned after the join
+    std::atomic<int> rc_work{FSV_OK};
+    auto work = [&]() {
+        try {
+        for (uint32_t s = next.fetch_add(1); s < B.n_sets && rc_work.load() == FSV_OK; s = next.fetch_add(1)) {
+            const uint32_t r0 = B.set_start[s], ns = B.set_start[s + 1] - r0;
+            if (ns == 0) continue;
+            const uint32_t nh_s = hit_first[s + 1] - hit_first[s];
+            const bool unphased = set_flags && (set_flags[s] & FSV_SET_UNPHASED);
+            if (P.graph_layout && !unphased) {
+                // the layout as hifiasm makes it (layout.h)
+                fsv_layout::ReadBases rb; rb.words = any_inexact ? h_store.data() : nullptr; rb.word_off = G.word_off.data() + r0; rb.len = len.data() + r0;
+                fsv_layout::Graph g(len.data() + r0, (int)ns, rb);
+                std::vector<fsv_layout::Hit> hs(nh_s);
+                for (uint32_t i = 0; i < nh_s; i++) {
+                    const fsv_hit &h = hraw[hit_first[s] + i];
+                    const int tl = len[r0 + h.t];
+                    fsv_layout::Hit &x = hs[i];
+                    x.qn = (int32_t)h.q; x.tn = (int32_t)h.t; x.qs = h.x_s; x.qe = h.x_e + 1; x.rev = (uint8_t)h.rev; x.el = (uint8_t)(h.slot >> 31); x.del = 0;
+                    if (h.rev) { x.ts = tl - h.y_e - 1; x.te = tl - h.y_s; } else { x.ts = h.y_s; x.te = h.y_e + 1; }
+                }
+                g.set_hits(std::move(hs));
+                g.build();
+                std::vector<std::vector<fsv_layout::PieceOut>> cs;
+                g.unitigs(P.min_contig_reads, cs);
+                for (auto &c : cs) { std::vector<Piece> pc; for (auto &e : c) pc.push_back(Piece{e.read, e.rev, e.len}); lay[s].contigs.push_back(std::move(pc)); }
+                lay[s].fallback = cs.empty();
+                continue;
+            }
+            layout_set(len.data() + r0, ns, hraw + hit_first[s], nh_s, P.min_contig_reads, lay[s].contigs, lay[s].fallback);
+        }
+        } catch (const std::bad_alloc &) { int ok = FSV_OK; rc_work.compare_exchange_strong(ok, FSV_ENOMEM); }
+        catch (...) { int ok = FSV_OK; rc_work.compare_exchange_strong(ok, FSV_EINTERNAL); }
+    };
+    // joined on every way out of this scope, an exception from emplace_back (a thread that cannot start) included: no joinable
+    // std::thread is ever destroyed
+    struct Joiner { std::vector<std::thread> thr; ~Joiner() { for (auto &t : thr) if (t.joinable()) t.join(); } };
+    {
+        Joiner j;
+        j.thr.reserve(nthr);
+        for (uint32_t t = 1; t < nthr; t++) j.thr.emplace_back(work);
+        work();
+    }
+    if (rc_work.load() != FSV_OK) return fsv_fail(ctx, rc_work.load(), rc_work.load() == FSV_ENOMEM ? "out of host memory (layout)" : "exception in the layout of a read set");
+    return FSV_OK;
+}
+
+// the contigs in set order: their pieces, stitched on the device (k_stitch) and copied back; the sets' status words
+static int emit_contigs(fsv_ctx *ctx, AsmWs &W, const Round &R, Final &F, fsv_contigs *out)
+{
+    const Batch &B = R.B;
     std::vector<fsv_piece> pieces;
     uint64_t used = 0;
     uint32_t nc = 0;
     int rc_out = FSV_OK;
-    // the sets are independent: lay them out on a few host threads, then emit the contigs in set order
-    struct SetLayout { std::vector<std::vector<Piece>> contigs; bool fallback = false; };
-    std::vector<SetLayout> lay(B.n_sets);
-    {
-        const uint32_t nthr = std::max(1u, std::min({8u, std::thread::hardware_concurrency(), B.n_sets / 16 + 1}));
-        std::atomic<uint32_t> next{0};
-        // a worker never lets an exception out (it would end the process): the first failure is kept and returned after the join
-        std::atomic<int> rc_work{FSV_OK};
-        auto work = [&]() {
-            try {
-            for (uint32_t s = next.fetch_add(1); s < B.n_sets && rc_work.load() == FSV_OK; s = next.fetch_add(1)) {
-                const uint32_t r0 = B.set_start[s], ns = B.set_start[s + 1] - r0;
-                if (ns == 0) continue;
-                const uint32_t nh_s = hit_first[s + 1] - hit_first[s];
-                const bool unphased = set_flags && (set_flags[s] & FSV_SET_UNPHASED);
-                if (P.graph_layout && !unphased) {
-                    // the layout as hifiasm makes it (layout.h)
-                    fsv_layout::ReadBases rb; rb.words = any_inexact ? h_store.data() : nullptr; rb.word_off = G.word_off.data() + r0; rb.len = len.data() + r0;
-                    fsv_layout::Graph g(len.data() + r0, (int)ns, rb);
-                    std::vector<fsv_layout::Hit> hs(nh_s);
-                    for (uint32_t i = 0; i < nh_s; i++) {
-                        const fsv_hit &h = hraw[hit_first[s] + i];
-                        const int tl = len[r0 + h.t];
-                        fsv_layout::Hit &x = hs[i];
-                        x.qn = (int32_t)h.q; x.tn = (int32_t)h.t; x.qs = h.x_s; x.qe = h.x_e + 1; x.rev = (uint8_t)h.rev; x.el = (uint8_t)(h.slot >> 31); x.del = 0;
-                        if (h.rev) { x.ts = tl - h.y_e - 1; x.te = tl - h.y_s; } else { x.ts = h.y_s; x.te = h.y_e + 1; }
-                    }
-                    g.set_hits(std::move(hs));
-                    g.build();
-                    std::vector<std::vector<fsv_layout::PieceOut>> cs;
-                    g.unitigs(P.min_contig_reads, cs);
-                    for (auto &c : cs) { std::vector<Piece> pc; for (auto &e : c) pc.push_back(Piece{e.read, e.rev, e.len}); lay[s].contigs.push_back(std::move(pc)); }
-                    lay[s].fallback = cs.empty();
-                    continue;
-                }
-                layout_set(len.data() + r0, ns, hraw + hit_first[s], nh_s, P.min_contig_reads, lay[s].contigs, lay[s].fallback);
-            }
-            } catch (const std::bad_alloc &) { int ok = FSV_OK; rc_work.compare_exchange_strong(ok, FSV_ENOMEM); }
-            catch (...) { int ok = FSV_OK; rc_work.compare_exchange_strong(ok, FSV_EINTERNAL); }
-        };
-        // joined on every way out of this scope, an exception from emplace_back (a thread that cannot start) included: no joinable
-        // std::thread is ever destroyed
-        struct Joiner { std::vector<std::thread> thr; ~Joiner() { for (auto &t : thr) if (t.joinable()) t.join(); } };
-        {
-            Joiner j;
-            j.thr.reserve(nthr);
-            for (uint32_t t = 1; t < nthr; t++) j.thr.emplace_back(work);
-            work();
-        }
-        if (rc_work.load() != FSV_OK) return fsv_fail(ctx, rc_work.load(), rc_work.load() == FSV_ENOMEM ? "out of host memory (layout)" : "exception in the layout of a read set");
-    }
     for (uint32_t s = 0; s < B.n_sets && rc_out == FSV_OK; s++) {
         const uint32_t r0 = B.set_start[s], ns = B.set_start[s + 1] - r0;
         int32_t st = 0;
-        for (uint32_t r = r0; r < r0 + ns; r++) st |= (int32_t)(hwarn[r] & (FSV_W_MZ_TRUNC | FSV_W_ANCHOR_TRUNC | FSV_W_INS_EVENTS | FSV_W_WINDOW_KEPT | FSV_W_INTERNAL | FSV_W_SITES));
+        for (uint32_t r = r0; r < r0 + ns; r++) st |= (int32_t)(F.hwarn[r] & (FSV_W_MZ_TRUNC | FSV_W_ANCHOR_TRUNC | FSV_W_INS_EVENTS | FSV_W_WINDOW_KEPT | FSV_W_INTERNAL | FSV_W_SITES));
         if (ns == 0) { out->set_status[s] = st; continue; }
-        if (lay[s].fallback) st |= FSV_W_NO_LAYOUT;
-        for (auto &c : lay[s].contigs) {
+        if (F.lay[s].fallback) st |= FSV_W_NO_LAYOUT;
+        for (auto &c : F.lay[s].contigs) {
             uint64_t clen = 0;
             for (auto &pc : c) clen += pc.len;
             if (nc >= out->contig_cap || used + clen > out->seq_cap) { rc_out = fsv_fail(ctx, FSV_ECAP, "contig output buffers too small (use fsv_assemble_batch_bound)"); break; }
@@ -1135,7 +1116,7 @@ static int assemble_chunk(fsv_ctx *ctx, const fsv_readsets *sets, const fsv_asm_
         }
         out->set_status[s] = st;
     }
-    trace("layout");
+    F.trace("layout");
     if (rc_out != FSV_OK) return rc_out;
     out->n_contigs = nc;
     ctx->last_contigs_dev = nullptr;
@@ -1144,18 +1125,26 @@ static int assemble_chunk(fsv_ctx *ctx, const fsv_readsets *sets, const fsv_asm_
         TRY(upload(ctx, W.pieces, pieces));
         TRY(ensure(ctx, W.contig_out, used + 16));
         W.kt.begin(ctx, KN_STITCH, used + used / 4);    // 2-bit bases in, ASCII out
-        hipLaunchKernelGGL(k_stitch, dim3((uint32_t)pieces.size()), dim3(256), 0, ctx->stream, store, (const uint32_t *)W.word_off.p,
-                           (const int32_t *)W.len.p, (const fsv_piece *)W.pieces.p, (char *)W.contig_out.p);
-        FSV_HIP(ctx, hipGetLastError());
+        FSV_LAUNCH(ctx, ctx->stream, k_stitch, dim3((uint32_t)pieces.size()), dim3(256), 0, R.store, W.word_off.p, W.len.p, W.pieces.p, W.contig_out.p);
         W.kt.end(ctx);
-        ctx->last_contigs_dev = (const char *)W.contig_out.p;
-        FSV_HIP(ctx, hipMemcpyAsync(out->seq, W.contig_out.p, used, hipMemcpyDeviceToHost, ctx->stream));
+        ctx->last_contigs_dev = W.contig_out.p;
+        TRY(download(ctx, out->seq, W.contig_out, used));
         FSV_HIP(ctx, hipStreamSynchronize(ctx->stream));
     }
-    trace("stitch+d2h");
-    tf.stop();
-    W.h_word_off = G.word_off; W.h_len = len; W.cur_store = store; W.n_reads = B.n_reads;
-    // statistics out of the counter slots (one per correction round, one for the final pass)
+    F.trace("stitch+d2h");
+    F.used = used;
+    return FSV_OK;
+}
+
+// statistics out of the counter rows (Round::row), and the byte counts of the launches that had to wait for them
+static void fill_stats(AsmWs &W, const Round &R, const Final &F)
+{
+    const fsv_asm_params &P = R.P; const Batch &B = R.B;
+    const std::vector<uint32_t> &h_ct = R.h_ct;
+    KTimes &kt = W.kt;
+    auto set = [&](int pass, int k, size_t round, uint64_t bytes) { if (uint64_t *b = kt.bytes_of(pass, k, round)) *b = bytes; };
+    auto add = [&](int pass, int k, size_t round, uint64_t bytes) { if (uint64_t *b = kt.bytes_of(pass, k, round)) *b += bytes; };
+    auto n_dp_of = [](const uint32_t *c) { return (uint64_t)c[CT_DP_SB] + c[CT_DP_SB16] + c[CT_DP] + c[CT_DP_FR3] + c[CT_DP_GEN] + c[CT_DP_WIDE] + c[CT_DP_XW]; };
     uint64_t mz_total[17] = {0}, n_windows2 = 0;
     for (int sl = 0; sl <= P.n_rounds; sl++) {
         const uint32_t *c = h_ct.data() + (size_t)sl * CT_SLOT;
@@ -1163,65 +1152,63 @@ static int assemble_chunk(fsv_ctx *ctx, const fsv_readsets *sets, const fsv_asm_
         if (sl == P.n_rounds) { W.stats.n_inexact_candidates = c[CT_INEXACT]; break; }
         W.stats.n_windows += c[CT_TASKS];
         W.stats.dp_columns += (uint64_t)c[CT_COLS_LO] | (uint64_t)c[CT_COLS_HI] << 32;      // rescue re-runs (k_rescue_accept)
-        W.stats.n_path_dp += (uint64_t)c[CT_DP_SB] + c[CT_DP_SB16] + c[CT_DP] + c[CT_DP_FR3] + c[CT_DP_GEN] + c[CT_DP_WIDE] + c[CT_DP_XW];
+        W.stats.n_path_dp += n_dp_of(c);
         W.stats.n_path_fr += (uint64_t)c[CT_DP_SB16] + c[CT_DP] + c[CT_DP_FR3];
         // algorithmic bytes of the round's launches, now that the counts are known: a window task is
         // 94 + 102 B of 2-bit operands + 16 B of result; a K6 window leaves a 128 B path record instead;
         // k_chain reads every unique-minimizer list once (two sorted copies, 16 B entries) and writes the overlap slots and
         // the 32 B task records; the consensus reads the path records and writes its corrected windows
-        const uint64_t nt = c[CT_TASKS], n_dp = (uint64_t)c[CT_DP_SB] + c[CT_DP_SB16] + c[CT_DP] + c[CT_DP_FR3] + c[CT_DP_GEN] + c[CT_DP_WIDE] + c[CT_DP_XW];
-        if ((size_t)sl < W.bpm_rec.size()) W.kt.recs[W.bpm_rec[sl]].bytes = nt * 212ull;
-        if ((size_t)sl < W.rescue_rec.size()) W.kt.recs[W.rescue_rec[sl]].bytes += nt * 16ull;
-        if ((size_t)sl < W.fast_rec.size()) W.kt.recs[W.fast_rec[sl]].bytes = nt * (16ull + 196ull) + (nt - n_dp) * 128ull;
-        if ((size_t)sl < W.dp_rec.size()) W.kt.recs[W.dp_rec[sl]].bytes = n_dp * (196ull + 128ull);
-        if ((size_t)sl < W.cons_rec.size()) W.kt.recs[W.cons_rec[sl]].bytes += nt * 128ull;
-        // the round's second consensus pass (its counters sit n_rounds + 1 rows further): the junction tasks are window tasks like
-        // the first pass's; k_bnd_tasks reads every first-pass task and path record and writes the junction tasks; the junctions'
-        // consensus reads their path records and writes a patch per junction
-        if ((size_t)sl < W.bc_bpm_rec.size()) {      // the junction cigars of the round's partition: window tasks like the others
-            const uint32_t *c3 = h_ct.data() + (size_t)(2 * P.n_rounds + 2 + sl) * CT_SLOT;
-            const uint64_t n3 = c3[CT_TASKS], n_dp3 = (uint64_t)c3[CT_DP_SB] + c3[CT_DP_SB16] + c3[CT_DP] + c3[CT_DP_FR3] + c3[CT_DP_GEN] + c3[CT_DP_WIDE] + c3[CT_DP_XW];
+        const uint64_t nt = c[CT_TASKS], n_dp = n_dp_of(c);
+        set(PASS_WINDOWS, KN_BPM, sl, nt * 212ull);
+        add(PASS_WINDOWS, KN_RESCUE, sl, nt * 16ull);
+        set(PASS_WINDOWS, KN_PATH_FAST, sl, nt * (16ull + 196ull) + (nt - n_dp) * 128ull);
+        set(PASS_WINDOWS, KN_PATH_DP, sl, n_dp * (196ull + 128ull));
+        add(PASS_WINDOWS, KN_CONSENSUS, sl, nt * 128ull);
+        if (kt.bytes_of(PASS_BCIG, KN_BPM, sl)) {      // the junction cigars of the round's partition: window tasks like the others
+            const uint32_t *c3 = h_ct.data() + (size_t)(PASS_BCIG * (P.n_rounds + 1) + sl) * CT_SLOT;
+            const uint64_t n3 = c3[CT_TASKS], n_dp3 = n_dp_of(c3);
             n_windows2 += n3;
             W.stats.n_junction_cigars += n3;
             W.stats.n_junction_used += c3[CT_B_LIST];
             if (getenv("FSV_BCIG_DEBUG")) fprintf(stderr, "[fsv] round %d: %u overlaps set aside for the left-extension pass; fix_boundary: %u candidates, %u windows moved\n", sl, c[CT_LEFT], c[CT_FIX], c[CT_FIXED]);
             if (getenv("FSV_BCIG_DEBUG")) fprintf(stderr, "[fsv] round %d: %llu junction cigars, %u accepted but showing what the window cigars show, %u used\n", sl, (unsigned long long)n3, c3[CT_B_RETRY], c3[CT_B_LIST]);
-            W.kt.recs[W.bc_bpm_rec[sl]].bytes = n3 * 212ull;
-            if ((size_t)sl < W.bc_fast_rec.size()) W.kt.recs[W.bc_fast_rec[sl]].bytes = n3 * (16ull + 196ull) + (n3 - n_dp3) * 128ull;
-            if ((size_t)sl < W.bc_dp_rec.size()) W.kt.recs[W.bc_dp_rec[sl]].bytes = n_dp3 * (196ull + 128ull);
+            set(PASS_BCIG, KN_BPM, sl, n3 * 212ull);
+            set(PASS_BCIG, KN_PATH_FAST, sl, n3 * (16ull + 196ull) + (n3 - n_dp3) * 128ull);
+            set(PASS_BCIG, KN_PATH_DP, sl, n_dp3 * (196ull + 128ull));
         }
-        if ((size_t)sl < W.bnd_rec.size()) {
-            const uint32_t *c2 = h_ct.data() + (size_t)(P.n_rounds + 1 + sl) * CT_SLOT;
-            const uint64_t n2 = c2[CT_TASKS], n3 = c2[CT_B_RETRY], n_dp2 = (uint64_t)c2[CT_DP_SB] + c2[CT_DP_SB16] + c2[CT_DP] + c2[CT_DP_FR3] + c2[CT_DP_GEN] + c2[CT_DP_WIDE] + c2[CT_DP_XW];
+        // the round's second consensus pass: the junction tasks are window tasks like the first pass's; k_bnd_tasks reads every
+        // first-pass task and path record and writes the junction tasks; the junctions' consensus reads their path records and
+        // writes a patch per junction
+        if (kt.bytes_of(PASS_JUNCTIONS, KN_BND, sl)) {
+            const uint32_t *c2 = h_ct.data() + (size_t)(PASS_JUNCTIONS * (P.n_rounds + 1) + sl) * CT_SLOT;
+            const uint64_t n2 = c2[CT_TASKS], n3 = c2[CT_B_RETRY], n_dp2 = n_dp_of(c2);
             n_windows2 += n2 + n3;
-            W.kt.recs[W.bnd_rec[sl]].bytes = nt * (sizeof(fsv_wtask) + 128ull) + n2 * sizeof(fsv_wtask);
-            if ((size_t)sl < W.bpm2_rec.size()) W.kt.recs[W.bpm2_rec[sl]].bytes = (n2 + n3) * 212ull;
-            if ((size_t)sl < W.fast2_rec.size()) W.kt.recs[W.fast2_rec[sl]].bytes = n2 * (16ull + 196ull) + (n2 - n_dp2) * 128ull;
-            if ((size_t)sl < W.dp2_rec.size()) W.kt.recs[W.dp2_rec[sl]].bytes = n_dp2 * (196ull + 128ull);
-            if ((size_t)sl < W.bndc_rec.size()) W.kt.recs[W.bndc_rec[sl]].bytes = n2 * 128ull + (uint64_t)c2[CT_B_LIST] * (sizeof(BndPatch) + 2ull * FSV_BND_HALF);
+            set(PASS_JUNCTIONS, KN_BND, sl, nt * (sizeof(fsv_wtask) + 128ull) + n2 * sizeof(fsv_wtask));
+            set(PASS_JUNCTIONS, KN_BPM, sl, (n2 + n3) * 212ull);
+            set(PASS_JUNCTIONS, KN_PATH_FAST, sl, n2 * (16ull + 196ull) + (n2 - n_dp2) * 128ull);
+            set(PASS_JUNCTIONS, KN_PATH_DP, sl, n_dp2 * (196ull + 128ull));
+            set(PASS_JUNCTIONS, KN_BND_CONS, sl, n2 * 128ull + (uint64_t)c2[CT_B_LIST] * (sizeof(BndPatch) + 2ull * FSV_BND_HALF));
         }
     }
     // the sketch reads the packed bases of the reads it sketches and writes 16 B per minimizer it produces ("len/4
     // in + 16 B / minimizer out"); k_uniq reads those and writes the unique ones twice (sorted by hash, sorted by position).
     // Round 2 charged 16 B per slot of CAPACITY (one per base) -- seven times what the counters saw.
-    for (size_t i = 0; i < W.sk_rec.size() && i <= (size_t)P.n_rounds; i++) {
+    // (overlap_stage runs once per round and once more for the final pass: its record i belongs to counter row i)
+    for (size_t i = 0; i <= (size_t)P.n_rounds; i++) {
         const uint32_t *c = h_ct.data() + i * CT_SLOT;
         const uint64_t raw = (uint64_t)c[CT_MZRAW_LO] | (uint64_t)c[CT_MZRAW_HI] << 32, bases = (uint64_t)c[CT_BASES_LO] | (uint64_t)c[CT_BASES_HI] << 32;
-        W.kt.recs[W.sk_rec[i]].bytes = bases / 4 + raw * sizeof(fsv_mz);
-        if (i < W.uq_rec.size()) W.kt.recs[W.uq_rec[i]].bytes = raw * sizeof(fsv_mz) + mz_total[i] * 2 * sizeof(fsv_mz);
+        set(PASS_WINDOWS, KN_SKETCH, i, bases / 4 + raw * sizeof(fsv_mz));
+        set(PASS_WINDOWS, KN_UNIQ, i, raw * sizeof(fsv_mz) + mz_total[i] * 2 * sizeof(fsv_mz));
+        set(PASS_WINDOWS, KN_CHAIN, i, mz_total[i] * 32ull + (uint64_t)B.n_pairs * sizeof(fsv_ovl) + (i < (size_t)P.n_rounds ? (uint64_t)c[CT_TASKS] * sizeof(fsv_wtask) : 0ull));
     }
-    for (size_t i = 0; i < W.chain_rec.size(); i++) {
-        const uint32_t *c = h_ct.data() + i * CT_SLOT;
-        W.kt.recs[W.chain_rec[i]].bytes = mz_total[i] * 32ull + (uint64_t)B.n_pairs * sizeof(fsv_ovl) + (i < (size_t)P.n_rounds ? (uint64_t)c[CT_TASKS] * sizeof(fsv_wtask) : 0ull);
-    }
-    for (uint32_t s2 = 0; s2 < B.n_sets; s2++) if (B.set_start[s2] < B.n_reads && B.set_start[s2 + 1] > B.set_start[s2]) W.stats.dp_columns += h_setcols[B.set_start[s2]];   // K5 windows
+    for (uint32_t s2 = 0; s2 < B.n_sets; s2++) if (B.set_start[s2] < B.n_reads && B.set_start[s2 + 1] > B.set_start[s2]) W.stats.dp_columns += F.h_setcols[B.set_start[s2]];   // K5 windows
     // algorithmic bytes: 2-bit operands + result of every DP task, reads in once per pass, contigs out
-    W.stats.algo_bytes = (W.stats.n_windows + n_windows2) * 212ull + reads_in_bytes * (uint64_t)(P.n_rounds + 1) + used;
-    W.stats.ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_enter).count();
+    W.stats.algo_bytes = (W.stats.n_windows + n_windows2) * 212ull + R.reads_in_bytes * (uint64_t)(P.n_rounds + 1) + F.used;
+    W.stats.ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - R.t_enter).count();
     // resolve the per-kernel event timings
     W.stats.n_kernels = KN_COUNT;
     for (int k = 0; k < KN_COUNT; k++) { memset(&W.stats.kernels[k], 0, sizeof(fsv_kernel_stat)); strncpy(W.stats.kernels[k].name, kn_names[k], 23); }
-    for (auto &r : W.kt.recs) {
+    for (auto &r : kt.recs) {
         float ms = 0;
         const bool ok = hipEventElapsedTime(&ms, r.a, r.b) == hipSuccess;
         if (r.k >= KN_COUNT) {   // a stage
@@ -1234,6 +1221,41 @@ static int assemble_chunk(fsv_ctx *ctx, const fsv_readsets *sets, const fsv_asm_
         W.stats.kernels[r.k].launches++;
         W.stats.kernels[r.k].algo_bytes += r.bytes;
     }
+}
+
+static int assemble_chunk(fsv_ctx *ctx, const fsv_readsets *sets, const fsv_asm_params &P, fsv_contigs *out)
+{
+    AsmWs &W = *ws_get(ctx);
+    memset(&W.stats, 0, sizeof(W.stats));
+    W.kt.reset();
+    Round R(P);
+    out->n_contigs = 0;
+    out->off[0] = 0;
+    for (uint32_t s = 0; s < sets->n_sets; s++) out->set_status[s] = 0;
+    if (sets->n_reads == 0 || sets->n_sets == 0) return FSV_OK;
+    TRY(prepare_batch(ctx, W, sets, R));
+    for (R.round = 0; R.round < P.n_rounds; R.round++) {
+        TRY(begin_round(ctx, W, R));
+        TRY(overlap_stage(ctx, W, R, false));
+        W.stats.n_pairs += R.B.n_pairs;
+        if (R.B.n_pairs) TRY(verify_stage(ctx, W, R));
+        // consensus -> corrected windows -> new read store
+        Span tcs(ctx, W.kt, ST_CONSENSUS);
+        TRY(consensus_stage(ctx, W, R));
+        if (P.second_round && R.B.n_pairs) TRY(second_pass(ctx, W, R));
+        TRY(finish_round(ctx, W, R));
+        tcs.stop();
+    }
+    Span tf(ctx, W.kt, ST_FINAL);
+    Final F;
+    F.ctx = ctx;
+    TRY(final_overlaps(ctx, W, R, F));
+    TRY(gather_hits(ctx, W, R, F));
+    TRY(layout_sets(ctx, W, R, F));
+    TRY(emit_contigs(ctx, W, R, F, out));
+    tf.stop();
+    W.h_word_off = R.G.word_off; W.h_len = R.len; W.cur_store = R.store; W.n_reads = R.B.n_reads;
+    fill_stats(W, R, F);
     return FSV_OK;
 }
 
@@ -1275,8 +1297,8 @@ static int fsv_assemble_batch_impl(fsv_ctx *ctx, const fsv_readsets *sets, const
     const char *env = getenv("FSV_ASM_BUDGET_GB");
     double budget = 0.4 * (double)ctx->hbm_bytes;
     {
-        size_t free_b = 0, total_b = 0, own = 0;
-        for (const DevBuf *b : W.all()) own += b->cap;
+        size_t free_b = 0, total_b = 0;
+        const size_t own = W.held();
         if (hipMemGetInfo(&free_b, &total_b) == hipSuccess)
             budget = std::min(budget, 0.9 * ((double)free_b / (double)std::max(1, fsv_live_contexts(ctx->device)) + (double)own));
     }
@@ -1322,13 +1344,13 @@ static int fsv_assemble_batch_impl(fsv_ctx *ctx, const fsv_readsets *sets, const
         const uint64_t bytes = part.n_contigs ? out->off[nc + part.n_contigs] - used : 0;
         if (bytes) {
             if (W.contig_all.cap < used + bytes + 16) {
-                DevBuf bigger;
+                Dev<char> bigger;
                 TRY(ensure(ctx, bigger, std::max<uint64_t>((used + bytes) * 2, 1u << 20)));
                 if (used) FSV_HIP(ctx, hipMemcpyAsync(bigger.p, W.contig_all.p, used, hipMemcpyDeviceToDevice, ctx->stream));
                 FSV_HIP(ctx, hipStreamSynchronize(ctx->stream));
                 W.contig_all.swap(bigger);      // (the old allocation goes with `bigger`)
             }
-            FSV_HIP(ctx, hipMemcpyAsync((char *)W.contig_all.p + used, W.contig_out.p, bytes, hipMemcpyDeviceToDevice, ctx->stream));
+            FSV_HIP(ctx, hipMemcpyAsync(W.contig_all.p + used, W.contig_out.p, bytes, hipMemcpyDeviceToDevice, ctx->stream));
         }
         used += bytes; nc += part.n_contigs;
         // statistics: sums over the chunks
@@ -1348,7 +1370,7 @@ static int fsv_assemble_batch_impl(fsv_ctx *ctx, const fsv_readsets *sets, const
     out->n_contigs = nc;
     W.stats = total;
     W.n_reads = 0; W.cur_store = nullptr;        // fsv_asm_fetch_reads serves single-pass batches only
-    ctx->last_contigs_dev = nc ? (const char *)W.contig_all.p : nullptr;
+    ctx->last_contigs_dev = nc ? W.contig_all.p : nullptr;
     ctx->last_contig_off.assign(out->off, out->off + nc + 1);
     return FSV_OK;
 }
@@ -1362,17 +1384,13 @@ static int fsv_asm_fetch_reads_impl(fsv_ctx *ctx, char *seq, uint64_t seq_cap, u
     std::vector<uint64_t> o(n_reads + 1, 0);
     for (uint32_t r = 0; r < n_reads; r++) o[r + 1] = o[r] + (uint64_t)W.h_len[r];
     if (o[n_reads] > seq_cap) return FSV_ECAP;
-    DevBuf d_off, d_out;
-    int rc = upload(ctx, d_off, o);
-    if (rc == FSV_OK) rc = ensure(ctx, d_out, o[n_reads] + 16);
-    if (rc == FSV_OK) {
-        hipLaunchKernelGGL(k_unpack_reads, dim3(n_reads), dim3(256), 0, ctx->stream, W.cur_store, (const uint32_t *)W.word_off.p,
-                           (const int32_t *)W.len.p, (const uint64_t *)d_off.p, (char *)d_out.p);
-        if (hipGetLastError() != hipSuccess) rc = FSV_EHIP;
-    }
-    if (rc == FSV_OK) rc = fsv_d2h(ctx, seq, d_out.p, o[n_reads]);
     memcpy(off, o.data(), (n_reads + 1) * sizeof(uint64_t));
-    return rc;
+    Dev<uint64_t> d_off;
+    Dev<char> d_out;
+    TRY(upload(ctx, d_off, o));
+    TRY(ensure(ctx, d_out, o[n_reads] + 16));
+    FSV_LAUNCH(ctx, ctx->stream, k_unpack_reads, dim3(n_reads), dim3(256), 0, W.cur_store, W.word_off.p, W.len.p, d_off.p, d_out.p);
+    return fsv_d2h(ctx, seq, d_out.p, o[n_reads]);
 }
 
 static int fsv_sketch_reads_impl(fsv_ctx *ctx, const fsv_readsets *sets, int32_t w, int32_t k, int32_t hpc, int32_t variant, fsv_mz *out_mz,
@@ -1396,42 +1414,20 @@ static int fsv_sketch_reads_impl(fsv_ctx *ctx, const fsv_readsets *sets, int32_t
     TRY(upload(ctx, W.word_off, G.word_off));
     TRY(upload(ctx, W.len, len));
     TRY(upload(ctx, W.mz_off, G.mz_off));
-    TRY(ensure(ctx, W.warn, (size_t)B.n_reads * 4));
-    FSV_HIP(ctx, hipMemsetAsync(W.warn.p, 0, (size_t)B.n_reads * 4, ctx->stream));
-    fsv_asm_params P;
-    fsv_asm_default_params(&P);
-    P.w = w; P.k = (variant == 1) ? (k | 0) : k; P.hpc = hpc;
-    // overlap_stage picks the kernel by the parity of k; to force the replay kernel for an odd k, run its launch here
-    TRY(ensure(ctx, W.mz, (size_t)G.mz_off[B.n_reads] * sizeof(fsv_mz)));
-    TRY(ensure(ctx, W.mz_cnt, (size_t)B.n_reads * 4));
-    FSV_HIP(ctx, hipMemsetAsync(W.mz_cnt.p, 0, (size_t)B.n_reads * 4, ctx->stream));
-    if ((k & 1) && variant != 1) {
-        const size_t total_words = G.word_off[B.n_reads];
-        TRY(ensure(ctx, W.sk_ends, (total_words * 16 + 64) * 4));
-        TRY(ensure(ctx, W.sk_low, (total_words + B.n_reads + 8) * 4));
-        TRY(ensure(ctx, W.sk_high, (total_words + B.n_reads + 8) * 4));
-        FSV_HIP(ctx, hipMemsetAsync(W.sk_low.p, 0, (total_words + B.n_reads + 8) * 4, ctx->stream));
-        FSV_HIP(ctx, hipMemsetAsync(W.sk_high.p, 0, (total_words + B.n_reads + 8) * 4, ctx->stream));
-        hipLaunchKernelGGL(k_sketch_fast, dim3(B.n_reads), dim3(256), 0, ctx->stream, sets->store_dev, (const uint32_t *)W.word_off.p,
-                           (const int32_t *)W.len.p, (const uint32_t *)W.mz_off.p, (fsv_mz *)W.mz.p, (uint32_t *)W.mz_cnt.p, B.n_reads, w, k, hpc,
-                           (uint32_t *)W.warn.p, (const uint8_t *)nullptr, (uint32_t *)W.sk_ends.p, (uint32_t *)W.sk_low.p, (uint32_t *)W.sk_high.p,
-                           (const uint32_t *)nullptr);
-    } else {
-        const uint32_t lds_words = std::min<uint32_t>(G.max_words, 8192u);
-        FSV_HIP(ctx, hipFuncSetAttribute((const void *)k_sketch, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sketch_lds_bytes(w, lds_words)));
-        hipLaunchKernelGGL(k_sketch, dim3(B.n_reads), dim3(64), sketch_lds_bytes(w, lds_words), ctx->stream, sets->store_dev,
-                           (const uint32_t *)W.word_off.p, (const int32_t *)W.len.p, (const uint32_t *)W.mz_off.p, (fsv_mz *)W.mz.p,
-                           (uint32_t *)W.mz_cnt.p, B.n_reads, w, k, hpc, (uint32_t *)W.warn.p, (const uint8_t *)nullptr, w, lds_words);
-    }
-    FSV_HIP(ctx, hipGetLastError());
+    TRY(ensure(ctx, W.warn, B.n_reads));
+    TRY(zero(ctx, W.warn, B.n_reads));
+    TRY(ensure(ctx, W.mz, G.mz_off[B.n_reads]));
+    TRY(ensure(ctx, W.mz_cnt, B.n_reads));
+    // variant 1: the replay kernel for an odd k as well (by itself the launch picks the kernel by the parity of k)
+    TRY(launch_sketch(ctx, W, SketchJob{sets->store_dev, B.n_reads, G.word_off[B.n_reads], G.max_words, w, k, hpc, nullptr, w, variant == 1, nullptr}));
     std::vector<uint32_t> cnt(B.n_reads);
-    FSV_HIP(ctx, hipMemcpyAsync(cnt.data(), W.mz_cnt.p, (size_t)B.n_reads * 4, hipMemcpyDeviceToHost, ctx->stream));
+    TRY(download(ctx, cnt.data(), W.mz_cnt, B.n_reads));
     FSV_HIP(ctx, hipStreamSynchronize(ctx->stream));
     uint64_t tot = 0;
     for (uint32_t r = 0; r < B.n_reads; r++) {
         const uint32_t c = std::min<uint32_t>(cnt[r], G.mz_off[r + 1] - G.mz_off[r]);
         if (tot + c > out_cap) return fsv_fail(ctx, FSV_ECAP, "out_mz too small");
-        FSV_HIP(ctx, hipMemcpyAsync(out_mz + tot, (const fsv_mz *)W.mz.p + G.mz_off[r], (size_t)c * sizeof(fsv_mz), hipMemcpyDeviceToHost, ctx->stream));
+        FSV_HIP(ctx, hipMemcpyAsync(out_mz + tot, W.mz.p + G.mz_off[r], (size_t)c * sizeof(fsv_mz), hipMemcpyDeviceToHost, ctx->stream));
         tot += c;
         out_off[r + 1] = tot;
     }

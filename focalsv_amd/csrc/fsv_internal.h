@@ -90,36 +90,48 @@ static inline unsigned fsv_grid_for(uint64_t n, unsigned block) { return (unsign
 #define TRY(x) do { int rc_ = (x); if (rc_ != FSV_OK) return rc_; } while (0)
 
 // ---- device buffers -------------------------------------------------------------------
-// A device allocation that only grows.  It owns its memory: the destructor frees it, so deleting a workspace frees its buffers.
-struct DevBuf {
-    void *p = nullptr;
+// A device allocation of elements of type T that only grows.  It owns its memory: the destructor frees it, so deleting a
+// workspace frees its buffers.  cap is in bytes (what the chunking budget adds up); every count below is in elements.
+template <class T> struct Dev {
+    T *p = nullptr;
     size_t cap = 0;
-    DevBuf() = default;
-    DevBuf(const DevBuf &) = delete;
-    DevBuf &operator=(const DevBuf &) = delete;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    void swap(DevBuf &o) { void *tp = p; p = o.p; o.p = tp; const size_t tc = cap; cap = o.cap; o.cap = tc; }
+    Dev() = default;
+    Dev(const Dev &) = delete;
+    Dev &operator=(const Dev &) = delete;
+    ~Dev() { if (p) (void)hipFree(p); }
+    void swap(Dev &o) { T *tp = p; p = o.p; o.p = tp; const size_t tc = cap; cap = o.cap; o.cap = tc; }
 };
 
-// room for `bytes` (an eighth more, so that a slowly growing batch does not reallocate every call).  What the buffer held is
-// lost when it grows; the stream is drained before the old allocation goes.
-static inline int ensure(fsv_ctx *ctx, DevBuf &b, size_t bytes)
+// room for n elements (an eighth more bytes, so that a slowly growing batch does not reallocate every call).  What the buffer
+// held is lost when it grows; the stream is drained before the old allocation goes.
+template <class T> int ensure(fsv_ctx *ctx, Dev<T> &b, size_t n)
 {
+    const size_t bytes = n * sizeof(T);
     if (bytes <= b.cap && b.p) return FSV_OK;
     if (b.p) { FSV_HIP(ctx, hipStreamSynchronize(ctx->stream)); FSV_HIP(ctx, hipFree(b.p)); b.p = nullptr; b.cap = 0; }
     const size_t want = bytes + bytes / 8 + 256;
-    FSV_HIP(ctx, hipMalloc(&b.p, want));
+    FSV_HIP(ctx, hipMalloc((void **)&b.p, want));
     b.cap = want;
     return FSV_OK;
 }
 
 // (an empty vector still leaves a valid pointer behind: kernels are handed b.p whatever the count)
-template <class T> int upload(fsv_ctx *ctx, DevBuf &b, const std::vector<T> &v)
+template <class T> int upload(fsv_ctx *ctx, Dev<T> &b, const std::vector<T> &v)
 {
-    TRY(ensure(ctx, b, (v.empty() ? 1 : v.size()) * sizeof(T)));
+    TRY(ensure(ctx, b, v.empty() ? 1 : v.size()));
     if (!v.empty()) FSV_HIP(ctx, hipMemcpyAsync(b.p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, ctx->stream));
     return FSV_OK;
 }
+
+// the first n elements zeroed / copied to the host, on the context's stream
+template <class T> int zero(fsv_ctx *ctx, Dev<T> &b, size_t n) { FSV_HIP(ctx, hipMemsetAsync(b.p, 0, n * sizeof(T), ctx->stream)); return FSV_OK; }
+template <class T> int download(fsv_ctx *ctx, T *host, const Dev<T> &b, size_t n) { FSV_HIP(ctx, hipMemcpyAsync(host, b.p, n * sizeof(T), hipMemcpyDeviceToHost, ctx->stream)); return FSV_OK; }
+// room for n elements in each of several buffers, in the order given
+template <class... Ts> int ensure_each(fsv_ctx *ctx, size_t n, Dev<Ts> &...b) { int rc = FSV_OK; (void)(((rc = ensure(ctx, b, n)) == FSV_OK) && ...); return rc; }
+
+// a kernel launch on a stream; every launch is checked on its own
+#define FSV_LAUNCH(ctx, stream, kern, grid, block, lds, ...) \
+    do { hipLaunchKernelGGL(kern, grid, block, lds, stream, __VA_ARGS__); FSV_HIP(ctx, hipGetLastError()); } while (0)
 
 // K5 with the task count left on the device (k5_bpm.hip): n_tasks sizes the grid, *n_dev is the count the kernel uses
 // k_cap: the largest threshold of the batch's error model (31 = hifiasm's; above it every window goes through the wide-band kernel)

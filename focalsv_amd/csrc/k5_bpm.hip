@@ -98,12 +98,9 @@ int fsv_bpm_windows_dev_n(fsv_ctx *ctx, const uint32_t *store_dev, const fsv_wta
     if (k_cap > FSV_K_WIDE) return fsv_fail(ctx, FSV_EUNSUP, "window thresholds above 95 (bands above 191 rows) are not built");
     FSV_HIP(ctx, hipSetDevice(ctx->device));
     if (k_cap > FSV_K_MAX)
-        hipLaunchKernelGGL(k5_bpm_wide_kernel, dim3(fsv_grid_for(n_tasks, 256)), dim3(256), 0, ctx->stream, store_dev, tasks_dev,
-                           n_tasks, res_dev, n_dev, k_cap);
+        FSV_LAUNCH(ctx, ctx->stream, k5_bpm_wide_kernel, dim3(fsv_grid_for(n_tasks, 256)), dim3(256), 0, store_dev, tasks_dev, n_tasks, res_dev, n_dev, k_cap);
     else
-    hipLaunchKernelGGL(k5_bpm_kernel, dim3((fsv_grid_for(n_tasks, 256) + 7u) & ~7u), dim3(256), 0, ctx->stream, store_dev, tasks_dev,
-                       n_tasks, res_dev, n_dev);
-    FSV_HIP(ctx, hipGetLastError());
+    FSV_LAUNCH(ctx, ctx->stream, k5_bpm_kernel, dim3((fsv_grid_for(n_tasks, 256) + 7u) & ~7u), dim3(256), 0, store_dev, tasks_dev, n_tasks, res_dev, n_dev);
     return FSV_OK;
 }
 

@@ -514,4 +514,36 @@ __global__ __launch_bounds__(256) void k_sketch_fast(const uint32_t *__restrict_
     }
 }
 
+// ------------------------------------------------------------------------------------------------ host: the sketch launch
+// Sketches n_reads reads of `store` into W.mz / W.mz_cnt (W: a workspace with word_off, len, mz_off, mz, mz_cnt, warn uploaded or
+// sized, and the scratch buffers sk_ends / sk_low / sk_high).  Odd k: the position-parallel kernel; even k, or replay: k_sketch.
+struct SketchJob {
+    const uint32_t *store; uint32_t n_reads; size_t total_words; uint32_t max_words;   // store words of all reads / of the longest one (the replay kernel's LDS tile)
+    int w, k, hpc; const uint8_t *wper; int w_max;        // a window per read (or null) and the largest of them
+    bool replay;                                          // k_sketch for an odd k as well
+    const uint32_t *only_changed;                         // odd k: reads with a zero here keep their list and their count
+};
+template <class Ws> int launch_sketch(fsv_ctx *ctx, Ws &W, const SketchJob &J)
+{
+    const bool fast = (J.k & 1) && !J.replay;
+    if (!(fast && J.only_changed)) TRY(zero(ctx, W.mz_cnt, J.n_reads));   // (with only_changed the kernel zeroes the counts of the others itself)
+    if (fast) {
+        // per-read scratch for run ends (4 B / base) and two bit planes, planes zeroed per launch
+        const size_t plane = J.total_words + J.n_reads + 8;
+        TRY(ensure(ctx, W.sk_ends, J.total_words * 16 + 64));
+        TRY(ensure_each(ctx, plane, W.sk_low, W.sk_high));
+        TRY(zero(ctx, W.sk_low, plane));
+        TRY(zero(ctx, W.sk_high, plane));
+        FSV_LAUNCH(ctx, ctx->stream, k_sketch_fast, dim3(J.n_reads), dim3(256), 0, J.store, W.word_off.p, W.len.p, W.mz_off.p, W.mz.p, W.mz_cnt.p,
+                   J.n_reads, J.w, J.k, J.hpc, W.warn.p, J.wper, W.sk_ends.p, W.sk_low.p, W.sk_high.p, J.only_changed);
+    } else {
+        const uint32_t lds_words = J.max_words < 8192u ? J.max_words : 8192u;
+        const size_t lds = sketch_lds_bytes(J.w_max, lds_words);
+        FSV_HIP(ctx, hipFuncSetAttribute((const void *)k_sketch, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        FSV_LAUNCH(ctx, ctx->stream, k_sketch, dim3(J.n_reads), dim3(64), lds, J.store, W.word_off.p, W.len.p, W.mz_off.p, W.mz.p, W.mz_cnt.p,
+                   J.n_reads, J.w, J.k, J.hpc, W.warn.p, J.wper, J.w_max, lds_words);
+    }
+    return FSV_OK;
+}
+
 } // namespace
