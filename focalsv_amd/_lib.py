@@ -342,14 +342,15 @@ class Context:
         self._last_contig_bytes = int(off[n])
         return ContigBatch(seq, off[: n + 1].copy()), cset[:n].copy(), cnr[:n].copy(), status[:rs.n_sets].copy()
 
-    def sketch_reads(self, store_dev, word_off, read_len, w=51, k=51, hpc=1, variant=0):
-        """K1 exposed: per read, its minimizers in position order -> list of structured arrays (hash, pos, rev, span)"""
+    def sketch_reads(self, store_dev, word_off, read_len, w=51, k=51, hpc=1, variant=0, out_cap=None):
+        """K1 exposed: per read, its minimizers in position order -> list of structured arrays (hash, pos, rev, span).
+        out_cap: entries of the output buffer (default: one per base and some, which always suffices)"""
         word_off = np.ascontiguousarray(word_off, dtype=np.uint64)
         read_len = np.ascontiguousarray(read_len, dtype=np.int32)
         ss = np.asarray([0, len(read_len)], dtype=np.uint32)
         rs = ReadSets(C.c_void_p(store_dev), _ptr(word_off).value, _ptr(read_len).value, _ptr(ss).value, len(read_len), 1)
-        cap = int(read_len.sum()) + 64 * len(read_len) + 64
-        out = np.zeros(cap, dtype=MZ_DTYPE)
+        cap = int(read_len.sum()) + 64 * len(read_len) + 64 if out_cap is None else int(out_cap)
+        out = np.zeros(max(cap, 1), dtype=MZ_DTYPE)
         off = np.zeros(len(read_len) + 1, dtype=np.uint64)
         self.check(self._lib.fsv_sketch_reads(self._h, C.byref(rs), w, k, hpc, variant, _ptr(out), cap, _ptr(off)), "fsv_sketch_reads")
         return [out[int(off[i]):int(off[i + 1])].copy() for i in range(len(read_len))]

@@ -1397,7 +1397,10 @@ static int fsv_sketch_reads_impl(fsv_ctx *ctx, const fsv_readsets *sets, int32_t
                                 uint64_t out_cap, uint64_t *out_off)
 {
     if (!ctx || !sets || !sets->store_dev || !sets->word_off || !sets->read_len || !out_mz || !out_off) return FSV_EINVAL;
-    if (k < 1 || k > 63 || w < 1 || w > 64) return fsv_fail(ctx, FSV_EINVAL, "k <= 63, w <= 64");
+    if (k < 1 || k > 63 || w < 1) return fsv_fail(ctx, FSV_EINVAL, "1 <= k <= 63, 1 <= w");
+    // the position-parallel kernel's LDS tile holds w <= 255 (as the aligner uses it); the replay kernel keeps w deque slots per lane
+    if ((k & 1) && variant != 1) { if (w > 255) return fsv_fail(ctx, FSV_EINVAL, "w <= 255 (position-parallel kernel: odd k, variant 0)"); }
+    else if (w > 64) return fsv_fail(ctx, FSV_EINVAL, "w <= 64 (replay kernel: even k, or variant 1)");
     FSV_HIP(ctx, hipSetDevice(ctx->device));
     AsmWs &W = *ws_get(ctx);
     W.kt.reset();

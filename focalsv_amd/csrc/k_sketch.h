@@ -35,8 +35,8 @@ __device__ __forceinline__ uint64_t mix64(uint64_t key)
 // is emitted the moment it joins the deque's front run.  The one irregular step is the first full window (l == w+k-1):
 // copies of the previous partial window's minimum are emitted and that minimum itself is dropped silently if the
 // incoming k-mer ties or beats it (sketch.cpp:101-106 run before 116-118 with l < w+k); replicated literally below.
-// Dynamic LDS: [w x 64 hashes][read words][w x 64 pos|span][w x 64 time|flag|rev][(k+1) x 64 run lengths].
-__host__ __device__ inline size_t sketch_lds_bytes(int w, uint32_t read_words) { return (size_t)read_words * 4 + (size_t)w * 64 * 14 + 64 * 64 + 16; }
+// Dynamic LDS: [w x 64 hashes][read words][w x 64 pos|span][w x 64 time|flag|rev][64 x 64 run lengths, 16 bits each].
+__host__ __device__ inline size_t sketch_lds_bytes(int w, uint32_t read_words) { return (size_t)read_words * 4 + (size_t)w * 64 * 14 + 64 * 64 * 2 + 16; }
 
 struct WordCache { // sequential base access through one cached 16-base word
     const uint32_t *p; uint32_t w; int idx;
@@ -62,7 +62,7 @@ __global__ __launch_bounds__(64) void k_sketch(const uint32_t *__restrict__ stor
     uint32_t *s_words = (uint32_t *)(d_hash + (size_t)w_max * 64);      // [lds_words]
     uint32_t *d_ps = s_words + lds_words;                               // [w_max][64]   pos << 8 | span
     uint16_t *d_tf = (uint16_t *)(d_ps + (size_t)w_max * 64);           // [w_max][64]   (time & 0x3fff) << 2 | rev << 1 | emitted
-    uint8_t *q_run = (uint8_t *)(d_tf + (size_t)w_max * 64);            // [64][64]      saturating run lengths
+    uint16_t *q_run = d_tf + (size_t)w_max * 64;                        // [64][64]      run lengths, saturating at 256
 #define D_HASH(j) d_hash[(j) * 64 + lane]
 #define D_PS(j) d_ps[(j) * 64 + lane]
 #define D_TF(j) d_tf[(j) * 64 + lane]
@@ -118,8 +118,10 @@ __global__ __launch_bounds__(64) void k_sketch(const uint32_t *__restrict__ stor
             int run = 1;
             while (i + run < len && B.get(i + run) == c) run++;
             i += run - 1;
-            const int rs = min(run, 255); // saturating: one run >= 255 puts the span at >= 256 (= no minimizer) either way
-            Q_RUN((run_head + run_cnt++) & 63) = (uint8_t)rs;
+            // saturating at 256: exact up to 255 (with k = 1 a run of 255 is a minimizer of span 255), and one run of 256 or more
+            // puts the span at >= 256 (= no minimizer) whatever k is
+            const int rs = min(run, 256);
+            Q_RUN((run_head + run_cnt++) & 63) = (uint16_t)rs;
             span += rs;
             if (run_cnt > k) { span -= Q_RUN(run_head); run_head = (run_head + 1) & 63; run_cnt--; }
         } else {

@@ -274,7 +274,9 @@ int fsv_asm_fetch_reads(fsv_ctx *ctx, char *seq, uint64_t seq_cap, uint64_t *off
 
 /* ---- K1 exposed: minimizer sketch of every read (ha_sketch, sketch.cpp:39-137) -------------------------
  * out_mz receives, per read, its minimizers in position order; out_off (n_reads+1) indexes them.
- * variant: 0 = library's choice (position-parallel kernel for odd k, deque replay otherwise), 1 = force the replay kernel. */
+ * variant: 0 = library's choice (position-parallel kernel for odd k, deque replay otherwise), 1 = force the replay kernel.
+ * 1 <= k <= 63; 1 <= w <= 255 where the position-parallel kernel runs (odd k, variant 0), w <= 64 where the replay kernel does
+ * (even k, or variant 1): FSV_EINVAL otherwise, and fsv_last_error names the limit that applied. */
 int fsv_sketch_reads(fsv_ctx *ctx, const fsv_readsets *sets, int32_t w, int32_t k, int32_t hpc, int32_t variant,
                      fsv_mz *out_mz, uint64_t out_cap, uint64_t *out_off);
 

@@ -123,6 +123,7 @@ int orc_aln_chains(const orc_mz *mq, int nq, int lenq, const orc_mz *mt, int nt,
 int orc_align_contig_multi(const char *contig, int lenq, const char *ref, int lent, const orc_aln_params *P, orc_aln *out,
                            uint32_t *cigar, int cigar_cap, int max_rec);
 int orc_sketch(const char *s, int len, int w, int k, int hpc, orc_mz *out, int cap);
+int orc_sketch_ex(const char *s, int len, int w, int k, int hpc, orc_mz *out, int cap, int *info);
 int orc_bpm(const char *y, int m, const char *x, int n, int k, int *err);
 int orc_bpm_extension(const char *y, const char *x, int n, int k, int *err, int *p_end);
 int orc_bpm_wide(const char *y, int m, const char *x, int n, int k, int *err);

@@ -183,3 +183,27 @@ def split_calls(recs):
         d, i = S.extract_sig_from_split(a, b)
         out += d + i
     return out
+
+
+def mixed_window_cases(sizes, seed=31):
+    """reference groups of very different lengths for ONE fsv_align_batch call: the seed window of a group is max(w, L / 3000 + 1),
+    L = its longest sequence, so groups of 30 kb, 150 kb and 400 kb are sketched with w = 19, 51 and 134 in one launch.  Per group
+    three contigs, none longer than the window (the oracle takes L per pair): the window with a deletion and an insertion, forward;
+    an inner part with a deletion, reverse strand; an inner part with an insertion, forward.  -> (refs, [(Case, group)])"""
+    rng = np.random.default_rng(seed)
+    refs, out = [], []
+    for gi, L in enumerate(sizes):
+        ref = rnd(rng, L)
+        refs.append(ref)
+        a, b = L // 3, 2 * L // 3
+        ins = rnd(rng, 200)
+        hap = ref[:a] + ref[a + 500:b] + ins + ref[b:]
+        out.append((Case("mixed-%d-both" % L, ref, hap, [("DEL", left_del(ref, a, 500), 500), ("INS", left_ins(hap, b - 500, 200, b), 200)]), gi))
+        lo, hi, c = 2000, L - 1000, L // 2
+        hap = ref[lo:c] + ref[c + 1000:hi]
+        out.append((Case("mixed-%d-del-rev" % L, ref, synth.revcomp(hap), [("DEL", left_del(ref, c, 1000), 1000)], strands=[1]), gi))
+        lo, hi, c = L // 4, 3 * L // 4, L // 2 + 77
+        ins = rnd(rng, 400)
+        hap = ref[lo:c] + ins + ref[c:hi]
+        out.append((Case("mixed-%d-ins" % L, ref, hap, [("INS", left_ins(hap, c - lo, 400, c), 400)]), gi))
+    return refs, out

@@ -99,6 +99,16 @@ def sketch(seq: str, w=51, k=51, hpc=1):
     return out[:n]
 
 
+def sketch_info(seq: str, w=51, k=51, hpc=1):
+    """sketch() plus what the walk met: (minimizers, entries, copies flushed at the first full window, entries with span >= 256)"""
+    cap = len(seq) + 8
+    out = np.zeros(cap, dtype=MZ_DTYPE)
+    info = (C.c_int * 3)()
+    n = lib().orc_sketch_ex(seq.encode(), len(seq), w, k, hpc, out.ctypes.data_as(C.c_void_p), cap, info)
+    assert n <= cap
+    return out[:n], info[0], info[1], info[2]
+
+
 class AsmParams(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("k", "w", "hpc", "n_rounds", "min_ovlp", "min_anchors", "lookback", "bw_ec", "bw_final", "min_contig_reads", "partition",
                                          "win_rate_pm", "k_cap", "accept_err_pm", "bw_rechain", "w_later", "second_round", "ins_dag",

@@ -200,3 +200,24 @@ def test_reference_windows_with_n_runs(ctx):
     for c, got in zip(cases, by):
         A.check_case(c, got)
         _same_records(got, O.align_contig_multi(c.hap, c.ref), c.name)
+
+
+def test_mixed_seed_windows_in_one_batch(ctx):
+    """One fsv_align_batch call whose reference groups are about 30 kb, 150 kb and 400 kb long: k_sketch_fast runs with a window
+    per sequence (w = 19, 51 and 134 in one launch; the 400 kb sequences take hundreds of tiles), contigs on both strands, planted
+    DEL / INS.  Records are identical to the oracle's, which sketches every pair on its own with the w of that pair.  The same with
+    k = 18 and groups of 30 kb and 150 kb: an even k takes the replay kernel, here with w_per_read (19) below w_max (51) -- its LDS
+    arrays are laid out for w_max while a lane's deque wraps at the read's own w.  (oracle/aln.c takes k from its params.)"""
+    from tests import aln_cases as A
+    for k, sizes, ws in ((19, (30000, 150000, 400000), (19, 51, 134)), (18, (30000, 150000), (19, 51))):
+        refs, cases = A.mixed_window_cases(sizes)
+        p, po = ctx.default_aln_params(), O.aln_default_params()
+        p.k, po.k = k, k
+        assert p.w == po.w == 19 and tuple(max(p.w, len(r) // 3000 + 1) for r in refs) == ws
+        assert all(len(c.hap) <= len(c.ref) for c, g in cases)
+        rec, cigar, status = ctx.align_batch([c.hap for c, g in cases], [g for c, g in cases], refs, p)
+        assert (status == 0).all(), (k, list(status))
+        by = _records_by_contig(rec, cigar, len(cases))
+        for (c, g), got in zip(cases, by):
+            A.check_case(c, got)
+            _same_records(got, O.align_contig_multi(c.hap, c.ref, po), (k, c.name))

@@ -1,5 +1,7 @@
 """K1 on the GPU (both kernels: position-parallel and deque replay) vs minimizers minted from the reference's ha_sketch
-and vs the CPU oracle on synthetic reads (tandem repeats, homopolymers, read ends inside runs)."""
+and vs the CPU oracle on synthetic reads (tandem repeats, homopolymers, read ends inside runs), and -- further down -- on the cases
+of tests/sketch_cases.py over the whole (w, k, HPC) range: every case, any batch shape, a reused context, junk in the padding bits,
+sequences as long as the aligner's, the output capacity."""
 import json
 import os
 import random
@@ -55,3 +57,236 @@ def test_sketch_matches_oracle_on_reads(ctx, variant):
             a = [(int(m["hash"]), int(m["pos"]), int(m["rev"]), int(m["span"])) for m in g]
             b = [(int(m["hash"]), int(m["pos"]), int(m["rev"]), int(m["span"])) for m in want]
             assert a == b
+
+
+# ---- the whole (w, k, HPC) range: tests/sketch_cases.py against the oracle (which tests/test_oracle_sketch.py pins on the
+# ---- reference's digests over the same grid).  Exact equality on (hash, pos, rev, span) and on the count, nothing left out.
+from tests import sketch_cases as SC  # noqa: E402
+
+FIELDS = ("hash", "pos", "rev", "span")
+_cases, _want = {}, {}
+
+
+def _grid_cases(gp):
+    if gp not in _cases:
+        _cases[gp] = SC.cases_for(*gp)
+    return _cases[gp]
+
+
+def _oracle(gp, c):
+    key = gp + (c["kind"], c["tag"])
+    if key not in _want:
+        _want[key] = O.sketch(c["seq"], *gp)
+    return _want[key]
+
+
+def _diff(g, want):
+    """None when equal, else a short description of the first difference"""
+    if len(g) == len(want) and all(np.array_equal(g[f], want[f]) for f in FIELDS):
+        return None
+    n = min(len(g), len(want))
+    bad = np.zeros(n, dtype=bool)
+    for f in FIELDS:
+        bad |= g[f][:n] != want[f][:n]
+    i = int(np.argmax(bad)) if bad.any() else n
+    row = lambda a: tuple(int(a[f][i]) for f in FIELDS) if i < len(a) else None
+    return "n %d vs %d, first difference at #%d: got %s want %s" % (len(g), len(want), i, row(g), row(want))
+
+
+def _same_bits(a, b):
+    return len(a) == len(b) and all(np.array_equal(a[f], b[f]) for f in FIELDS)
+
+
+def _refused(ctx, gp, variant):
+    with pytest.raises(_lib.FsvError) as e:
+        _run(ctx, ["ACGT" * 100], gp[0], gp[1], gp[2], variant)
+    return e.value.code == _lib.EINVAL and "w <= 64 (replay kernel" in str(e.value)
+
+
+@pytest.mark.parametrize("variant", [0, 1])
+def test_grid_matches_oracle(ctx, variant):
+    """3a: every case of every grid point, one fsv_sketch_reads call per (w, k, hpc).  Variant 0 takes the position-parallel
+    kernel for odd k (all w up to 255) and the replay kernel for even k; variant 1 the replay kernel for every k.  The grid points
+    left out are exactly those the library is documented to refuse -- the replay kernel with w > 64 -- and each is shown to be
+    refused with that reason."""
+    skipped, bad, n_reads, n_mz = [], [], 0, 0
+    for gp in SC.GRID:
+        w, k, hpc = gp
+        why = SC.gpu_limit(w, k, variant)
+        if why:
+            assert _refused(ctx, gp, variant), gp
+            skipped.append(gp)
+            continue
+        cases = _grid_cases(gp)
+        got = _run(ctx, [c["seq"] for c in cases], w, k, hpc, variant)
+        assert len(got) == len(cases)
+        for c, g in zip(cases, got):
+            d = _diff(g, _oracle(gp, c))
+            if d:
+                bad.append((gp, c["kind"], c["tag"], len(c["seq"]), d))
+            n_mz += len(g)
+        n_reads += len(cases)
+    print("sketch grid, variant %d: %d grid points, %d reads, %d minimizers; refused (replay kernel, w > 64): %d grid points: %s"
+          % (variant, len(SC.GRID) - len(skipped), n_reads, n_mz, len(skipped), skipped))
+    assert not bad, (len(bad), len({b[0] for b in bad}), bad[:12])
+    n_wide = sum(w > 64 for w in SC.WS)
+    if variant == 0:
+        assert all(k % 2 == 0 and w > 64 for (w, k, hpc) in skipped) and len(skipped) == n_wide * sum(k % 2 == 0 for k in SC.KS) * 2
+        cov = SC.coverage([c for gp in SC.GRID if gp not in skipped for c in _grid_cases(gp)], O.sketch_info)
+        print("coverage:", {n: sum(d[n] for d in cov.values()) for n in SC.COUNTS})
+    else:
+        assert all(w > 64 for (w, k, hpc) in skipped) and len(skipped) == n_wide * len(SC.KS) * 2
+
+
+BATCH_POINTS = ((51, 51, 1, 0), (19, 19, 0, 0), (200, 19, 0, 0), (255, 63, 1, 0), (128, 3, 1, 0), (64, 62, 1, 0), (17, 20, 0, 0), (33, 31, 1, 1), (64, 19, 0, 1))
+
+
+def test_batch_shape_does_not_matter(ctx):
+    """3b: a read's result does not depend on its place in the batch or on its neighbours (bit planes and run ends of all reads
+    share one scratch, k-mers are cut from words past a read's own plane): the same reads shuffled; interleaved with reads of
+    other content; and alone -- one read of every grid point the library accepts, a call each."""
+    rng = random.Random(11)
+    for (w, k, hpc, variant) in BATCH_POINTS:
+        seqs = [c["seq"] for c in _grid_cases((w, k, hpc))]
+        plain = _run(ctx, seqs, w, k, hpc, variant)
+        perm = list(range(len(seqs)))
+        rng.shuffle(perm)
+        got = _run(ctx, [seqs[i] for i in perm], w, k, hpc, variant)
+        for j, i in enumerate(perm):
+            assert _same_bits(got[j], plain[i]), ("shuffled", w, k, hpc, variant, i)
+        other = [c["seq"] for c in _grid_cases((3, 15, 0))] + ["".join(rng.choices("ACGT", k=n)) for n in (1, 17, 700, 5000, 33)] + ["T" * 2000, "G"]
+        mixed, where = [], []
+        for i, s in enumerate(seqs):
+            for _ in range(rng.randrange(3)):
+                mixed.append(rng.choice(other))
+            where.append(len(mixed))
+            mixed.append(s)
+        mixed.append(rng.choice(other))
+        got = _run(ctx, mixed, w, k, hpc, variant)
+        for i, j in enumerate(where):
+            assert _same_bits(got[j], plain[i]), ("interleaved", w, k, hpc, variant, i)
+    n_single = 0
+    for n, gp in enumerate(SC.GRID):
+        w, k, hpc = gp
+        for variant in (0, 1):
+            if SC.gpu_limit(w, k, variant) or (variant == 1 and n % 3):
+                continue
+            cases = _grid_cases(gp)
+            i = (n * 7 + variant) % len(cases)
+            got = _run(ctx, [cases[i]["seq"]], w, k, hpc, variant)
+            assert _diff(got[0], _oracle(gp, cases[i])) is None, ("single", gp, variant, cases[i]["kind"], cases[i]["tag"])
+            n_single += 1
+    print("single-read calls:", n_single)
+    assert n_single >= 200
+
+
+@pytest.mark.parametrize("variant", [0, 1])
+def test_context_reuse(variant):
+    """3c: a large batch, then a few short reads with other parameters, then the large batch again on one context; each result
+    equals that of a context that has run nothing else (stale bit planes, counts, scratch and buffer sizes)"""
+    big_gp, small_gp = ((200, 19, 0), (3, 3, 1)) if variant == 0 else ((64, 51, 1), (2, 2, 0))
+    rng = random.Random(5)
+    big = [c["seq"] for c in _grid_cases(big_gp)] + ["".join(rng.choices("ACGT", k=60000))]
+    small = ["ACGTTGCA", "A", "AC" * 20, "".join(rng.choices("ACGT", k=63)), "GGGGGGGGGGGGGGGGGT"]
+
+    def fresh(seqs, gp):
+        with _lib.Context(0) as c:
+            return _run(c, seqs, gp[0], gp[1], gp[2], variant)
+
+    want_big, want_small = fresh(big, big_gp), fresh(small, small_gp)
+    for s, g in zip(big, want_big):
+        assert _diff(g, O.sketch(s, *big_gp)) is None
+    for s, g in zip(small, want_small):
+        assert _diff(g, O.sketch(s, *small_gp)) is None
+    with _lib.Context(0) as c:
+        for step, (seqs, gp, want) in enumerate(((big, big_gp, want_big), (small, small_gp, want_small), (big, big_gp, want_big),
+                                                 (small, big_gp, None), (small, small_gp, want_small))):
+            got = _run(c, seqs, gp[0], gp[1], gp[2], variant)
+            if want is None:
+                want = [O.sketch(s, *gp) for s in seqs]
+            for i, (g, x) in enumerate(zip(got, want)):
+                assert _same_bits(g, x), (step, gp, i)
+
+
+@pytest.mark.parametrize("fill", ["ones", "random"])
+@pytest.mark.parametrize("variant", [0, 1])
+def test_padding_bits_are_not_bases(ctx, variant, fill):
+    """3d: the 2-bit fields of a read's last word beyond its length, and the words behind the last read, hold anything"""
+    nprng = np.random.default_rng(17)
+    for gp in ((51, 51, 1), (19, 19, 0), (3, 1, 1), (64, 63, 1), (16, 20, 1), (2, 2, 0)) + (((255, 19, 0), (129, 3, 1)) if variant == 0 else ()):
+        w, k, hpc = gp
+        cases = _grid_cases(gp)
+        words, off, lens = _lib.pack_reads([c["seq"] for c in cases])
+        n_store = int(off[-1])
+        words = np.concatenate([words[:n_store], np.zeros(16, dtype=np.uint32)])
+        junk = np.full(len(words), 0xffffffff, dtype=np.uint32) if fill == "ones" else nprng.integers(0, 1 << 32, len(words), dtype=np.uint64).astype(np.uint32)
+        n_filled = 0
+        for r, n in enumerate(lens):
+            assert int(off[r + 1]) - int(off[r]) == (int(n) + 15) // 16
+            used = int(n) % 16
+            if used:
+                last = int(off[r + 1]) - 1
+                keep = np.uint32((1 << (2 * used)) - 1)
+                words[last] = (words[last] & keep) | (junk[last] & ~keep)
+                n_filled += 1
+        words[n_store:] = junk[n_store:]
+        assert n_filled > len(cases) // 2
+        d = ctx.upload(words)
+        try:
+            got = ctx.sketch_reads(d, off, lens, w, k, hpc, variant)
+        finally:
+            ctx.dev_free(d)
+        for c, g in zip(cases, got):
+            assert _diff(g, _oracle(gp, c)) is None, (gp, variant, fill, c["kind"], c["tag"], _diff(g, _oracle(gp, c)))
+
+
+def _tandem_rich(rng, n):
+    out, total = [], 0
+    while total < n:
+        if rng.random() < 0.5:
+            s = "".join(rng.choices("ACGT", k=rng.randrange(200, 6000)))
+        else:
+            u = "".join(rng.choices("ACGT", k=rng.choice((1, 2, 3, 7, 37, 100, 255, 300, 1000))))
+            s = u * (rng.randrange(300, 9000) // len(u) + 1)
+        out.append(s)
+        total += len(s)
+    return "".join(out)[:n]
+
+
+def test_long_sequences(ctx):
+    """3e: what the aligner sketches -- windows and contigs of up to 760 kb (hundreds of tiles) with w up to 255 -- through the
+    position-parallel kernel, and a read above 131 072 bases through the replay kernel, whose words then stay in HBM"""
+    rng = random.Random(23)
+    seqs = ["".join(rng.choices("ACGT", k=300000)), "".join(rng.choices("ACGT", k=760000)), _tandem_rich(rng, 760000)]
+    for gp in ((101, 19, 0), (255, 19, 0), (51, 51, 1)):
+        got = _run(ctx, seqs, gp[0], gp[1], gp[2], 0)
+        for s, g in zip(seqs, got):
+            d = _diff(g, O.sketch(s, *gp))
+            assert d is None, (gp, len(s), d)
+    s140 = _tandem_rich(rng, 70000) + "".join(rng.choices("ACGT", k=70000))
+    assert (len(s140) + 15) // 16 > 8192
+    for gp in ((51, 50, 1), (64, 62, 0)):
+        for variant in (0, 1):
+            got = _run(ctx, [s140, "ACGT" * 50], gp[0], gp[1], gp[2], variant)
+            d = _diff(got[0], O.sketch(s140, *gp))
+            assert d is None, (gp, variant, d)
+
+
+def test_capacity_one_short_is_ecap(ctx):
+    """3f: an output buffer one entry short is FSV_ECAP, and the context goes on working"""
+    for (w, k, hpc, variant) in ((51, 51, 1, 0), (19, 20, 0, 0), (200, 19, 0, 0), (31, 15, 1, 1)):
+        gp = (w, k, hpc)
+        cases = _grid_cases(gp)
+        need = sum(len(_oracle(gp, c)) for c in cases)
+        words, off, lens = _lib.pack_reads([c["seq"] for c in cases])
+        d = ctx.upload(words)
+        try:
+            with pytest.raises(_lib.FsvError) as e:
+                ctx.sketch_reads(d, off, lens, w, k, hpc, variant, out_cap=need - 1)
+            assert e.value.code == _lib.ECAP
+            got = ctx.sketch_reads(d, off, lens, w, k, hpc, variant, out_cap=need)
+        finally:
+            ctx.dev_free(d)
+        assert sum(len(g) for g in got) == need
+        for c, g in zip(cases, got):
+            assert _diff(g, _oracle(gp, c)) is None, (gp, variant, c["kind"], c["tag"])
