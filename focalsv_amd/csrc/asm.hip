@@ -2,7 +2,7 @@
 //
 // Replaces the process boundary `hifiasm -o <prefix> -t T <reads.fa>` + GFA read-back
 // (focalsv/3_assembly/run_assembly.py:15-44, post_assembly.py:79-95).  All base-level work runs in the
-// kernels of asm_kernels.h and k_sketch.h; the host only sizes buffers between stages and walks the (tiny, <= a few
+// kernels of asm_kernels.h, k_consensus.h and k_sketch.h; the host only sizes buffers between stages and walks the (tiny, <= a few
 // hundred nodes per set) overlap graph, which is host code in hifiasm as well (Overlaps.cpp).
 #include "asm_kernels.h"
 #include "layout.h"
@@ -517,7 +517,7 @@ static int path_stage(fsv_ctx *ctx, AsmWs &W, const PathJob &J)
     return FSV_OK;
 }
 
-// The second consensus pass of a round (process_boundary, Correct.cpp:4453): see asm_kernels.h "second consensus pass".
+// The second consensus pass of a round (process_boundary, Correct.cpp:4453): see k_consensus.h "second consensus pass".
 // Runs between the windows' consensus (cwin / cwin_len final for the first pass) and k_newlen; leaves cwin / cwin_len patched.
 static int second_pass(fsv_ctx *ctx, AsmWs &W, const Round &R)
 {
