@@ -23,6 +23,10 @@ assert WTASK_DTYPE.itemsize == 32 and WRES_DTYPE.itemsize == 16
 WPATH_DTYPE = np.dtype([("ry_start", "<i4"), ("ry_end", "<i4"), ("path_len", "<i2"), ("err", "<i2"), ("state", "u1"), ("y_rev", "u1"),
                         ("pad", "<u2"), ("y_word", "<u4"), ("y_len", "<i4"), ("ops", "u1", (104,))], align=False)
 assert WPATH_DTYPE.itemsize == 128
+OVL_DTYPE = np.dtype([("q", "<u4"), ("t", "<u4"), ("x_s", "<i4"), ("x_e", "<i4"), ("y_s", "<i4"), ("y_e", "<i4"), ("score", "<i4"), ("n_chain", "<i4"),
+                      ("chain_off", "<i4"), ("first_win", "<i4"), ("n_win", "<i4"), ("align_len", "<i4"), ("err_sum", "<i4"),
+                      ("rev", "u1"), ("is_match", "u1"), ("exact", "u1"), ("valid", "u1")], align=False)
+assert OVL_DTYPE.itemsize == 56
 
 
 class AsmParams(C.Structure):
@@ -136,6 +140,8 @@ def load():
         "fsv_asm_last_stats": (C.c_int, [vp, C.POINTER(AsmStats)]),
         "fsv_asm_fetch_reads": (C.c_int, [vp, vp, C.c_uint64, vp, C.c_uint32]),
         "fsv_sketch_reads": (C.c_int, [vp, C.POINTER(ReadSets), C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, C.c_uint64, vp]),
+        "fsv_asm_overlaps": (C.c_int, [vp, C.POINTER(ReadSets), C.POINTER(AsmParams), C.c_int32, vp, C.c_uint32, vp, C.c_uint64, vp, vp, C.c_uint64,
+                                       u32p, u32p, vp]),
         "fsv_aln_default_params": (None, [C.POINTER(AlnParams)]),
         "fsv_align_batch": (C.c_int, [vp, vp, vp, C.c_uint32, vp, vp, vp, C.c_uint32, C.POINTER(AlnParams), C.POINTER(Alns)]),
         "fsv_aln_last_stats": (C.c_int, [vp, C.POINTER(AlnStats)]),
@@ -354,6 +360,29 @@ class Context:
         off = np.zeros(len(read_len) + 1, dtype=np.uint64)
         self.check(self._lib.fsv_sketch_reads(self._h, C.byref(rs), w, k, hpc, variant, _ptr(out), cap, _ptr(off)), "fsv_sketch_reads")
         return [out[int(off[i]):int(off[i + 1])].copy() for i in range(len(read_len))]
+
+    def asm_overlaps(self, store_dev, word_off, read_len, set_start, params=None, pass_=0, rechain=()):
+        """fsv_asm_overlaps (test hook): the overlap stage of one pass -> (ovl[OVL_DTYPE] per ordered pair slot, pair_base[n_sets + 1],
+        tasks[WTASK_DTYPE], overflow flag, warn[n_reads]); see include/focalsv_hip.h for the slot formula"""
+        word_off = np.ascontiguousarray(word_off, dtype=np.uint64)
+        read_len = np.ascontiguousarray(read_len, dtype=np.int32)
+        set_start = np.ascontiguousarray(set_start, dtype=np.uint32)
+        rs = ReadSets(C.c_void_p(store_dev), _ptr(word_off).value, _ptr(read_len).value, _ptr(set_start).value, len(read_len), len(set_start) - 1, None)
+        n_pairs = task_cap = 0
+        for s in range(len(set_start) - 1):
+            ns = int(set_start[s + 1]) - int(set_start[s])
+            n_pairs += ns * (ns - 1)
+            task_cap += int(((read_len[int(set_start[s]):int(set_start[s + 1])].astype(np.int64) + FSV_WINDOW - 1) // FSV_WINDOW).sum()) * max(0, ns - 1)
+        ovl = np.zeros(max(1, n_pairs), dtype=OVL_DTYPE)
+        pair_base = np.zeros(len(set_start), dtype=np.uint32)
+        tasks = np.zeros(max(1, task_cap), dtype=WTASK_DTYPE)
+        warn = np.zeros(max(1, len(read_len)), dtype=np.uint32)
+        lst = np.ascontiguousarray(rechain, dtype=np.uint32)
+        n_tasks, overflow = C.c_uint32(0), C.c_uint32(0)
+        p = params if params is not None else self.default_asm_params()
+        self.check(self._lib.fsv_asm_overlaps(self._h, C.byref(rs), C.byref(p), int(pass_), _ptr(lst) if len(lst) else None, len(lst), _ptr(ovl), n_pairs,
+                                              _ptr(pair_base), _ptr(tasks), task_cap, C.byref(n_tasks), C.byref(overflow), _ptr(warn)), "fsv_asm_overlaps")
+        return ovl[:n_pairs], pair_base, tasks[: n_tasks.value], int(overflow.value), warn[: len(read_len)]
 
     def asm_stats(self):
         st = AsmStats()

@@ -919,15 +919,47 @@ struct Final {
     void trace(const char *what) { if (getenv("FSV_TRACE")) { (void)hipStreamSynchronize(ctx->stream); auto t = std::chrono::steady_clock::now(); fprintf(stderr, "[fsv] final %-14s %.2f ms\n", what, std::chrono::duration<double, std::milli>(t - tr0).count()); tr0 = t; } }
 };
 
-// final overlaps on the corrected reads: the exact ones (k_exact), and the inexact ones the last correction round had verified
-static int final_overlaps(fsv_ctx *ctx, AsmWs &W, Round &R, Final &F)
+// the final pass's geometry on the device; its counter row
+static int begin_final(fsv_ctx *ctx, AsmWs &W, Round &R)
 {
-    const fsv_asm_params &P = R.P; const Batch &B = R.B;
-    R.ct = W.ct_of(P.n_rounds); R.task_cap = 0;      // (the final pass emits no window tasks)
+    R.ct = W.ct_of(R.P.n_rounds); R.task_cap = 0;      // (the final pass emits no window tasks)
     TRY(upload(ctx, W.word_off, R.G.word_off));
     TRY(upload(ctx, W.len, R.len));
     TRY(upload(ctx, W.mz_off, R.G.mz_off));
     TRY(ensure(ctx, W.tasks, 2));
+    return FSV_OK;
+}
+
+// the gapped re-chain of the unordered pairs listed in W.inexact_list (*n_list_dev of them, a count on the device), after the final
+// pass's overlap_stage: both slots of a listed pair are overwritten, the other slots stay
+static int rechain_listed(fsv_ctx *ctx, AsmWs &W, const Round &R, const uint32_t *n_list_dev)
+{
+    const fsv_asm_params &P = R.P; const Batch &B = R.B;
+    ChainArgs A2 = W.last_chain;
+    A2.bw = P.bw_rechain; A2.emit_tasks = 0; A2.pair_list = W.inexact_list.p; A2.n_list_dev = n_list_dev;
+    // Either direction of a listed pair is chained from its own side, as hifiasm does: with an indel budget the chain DP depends
+    // on the end it starts from (the budget is a rate over the span chained so far; on the reverse strand the two sides start
+    // from opposite ends), and the mirror image of one side's chain can be off by the bases of an indel near a read end.
+    A2.primary_only = 1;
+    TRY(ensure(ctx, W.upair_tab_sw, std::max(1u, B.n_upairs)));
+    FSV_LAUNCH(ctx, ctx->stream, k_pair_tab_swap, dim3(fsv_grid_for(B.n_upairs, 256)), dim3(256), 0, W.upair_tab.p, B.n_upairs, W.upair_tab_sw.p);
+    // timed like the other k_chain launches (a profiler counts it too)
+    W.kt.begin(ctx, KN_CHAIN, 0);
+    for (int side = 0; side < 2; side++) {
+        if (side == 1) A2.upair_tab = W.upair_tab_sw.p;
+        if (A2.wide_list) FSV_HIP(ctx, hipMemsetAsync(A2.n_wide, 0, 4, ctx->stream));   // (the final pass's own wide pairs are done)
+        TRY(launch_chain(ctx, CHAIN_PAIRS, R.short_reads, B.n_upairs, A2, B.n_upairs));
+        if (A2.wide_list) TRY(chain_wide_pairs(ctx, A2, R.short_reads, B.n_upairs));
+    }
+    W.kt.end(ctx);
+    return FSV_OK;
+}
+
+// final overlaps on the corrected reads: the exact ones (k_exact), and the inexact ones the last correction round had verified
+static int final_overlaps(fsv_ctx *ctx, AsmWs &W, Round &R, Final &F)
+{
+    const fsv_asm_params &P = R.P; const Batch &B = R.B;
+    TRY(begin_final(ctx, W, R));
     // what the last correction round verified (coordinates on the reads as they were before that round) -- the final pass
     // accepts inexact overlaps against it; the slots are about to be overwritten
     const bool have_prev = P.n_rounds > 0 && B.n_pairs > 0;
@@ -954,23 +986,7 @@ static int final_overlaps(fsv_ctx *ctx, AsmWs &W, Round &R, Final &F)
     uint32_t *n_list_dev = R.ct + CT_INEXACT;
     FSV_LAUNCH(ctx, ctx->stream, k_inexact_list, dim3(fsv_grid_for(B.n_upairs, 256)), dim3(256), 0, W.upair_tab.p, W.exact_flag.p, W.ovl_prev.p, B.n_upairs,
                W.inexact_list.p, n_list_dev);
-    ChainArgs A2 = W.last_chain;
-    A2.bw = P.bw_rechain; A2.emit_tasks = 0; A2.pair_list = W.inexact_list.p; A2.n_list_dev = n_list_dev;
-    // Either direction of a listed pair is chained from its own side, as hifiasm does: with an indel budget the chain DP depends
-    // on the end it starts from (the budget is a rate over the span chained so far; on the reverse strand the two sides start
-    // from opposite ends), and the mirror image of one side's chain can be off by the bases of an indel near a read end.
-    A2.primary_only = 1;
-    TRY(ensure(ctx, W.upair_tab_sw, std::max(1u, B.n_upairs)));
-    FSV_LAUNCH(ctx, ctx->stream, k_pair_tab_swap, dim3(fsv_grid_for(B.n_upairs, 256)), dim3(256), 0, W.upair_tab.p, B.n_upairs, W.upair_tab_sw.p);
-    // timed like the other k_chain launches (a profiler counts it too)
-    W.kt.begin(ctx, KN_CHAIN, 0);
-    for (int side = 0; side < 2; side++) {
-        if (side == 1) A2.upair_tab = W.upair_tab_sw.p;
-        if (A2.wide_list) FSV_HIP(ctx, hipMemsetAsync(A2.n_wide, 0, 4, ctx->stream));   // (the final pass's own wide pairs are done)
-        TRY(launch_chain(ctx, CHAIN_PAIRS, R.short_reads, B.n_upairs, A2, B.n_upairs));
-        if (A2.wide_list) TRY(chain_wide_pairs(ctx, A2, R.short_reads, B.n_upairs));
-    }
-    W.kt.end(ctx);
+    TRY(rechain_listed(ctx, W, R, n_list_dev));
     FSV_LAUNCH(ctx, ctx->stream, k_accept_inexact, dim3(fsv_grid_for(2ull * B.n_upairs, 256)), dim3(256), 0, W.upair_tab.p, W.inexact_list.p, 0u, W.ovl.p, W.ovl_prev.p,
                W.read_set.p, W.pair_base.p, W.hits.p, W.set_hits.p, n_list_dev);
     return FSV_OK;
@@ -1269,17 +1285,23 @@ static void set_cost(const fsv_readsets *sets, uint32_t s, uint64_t &tasks, uint
     pairs = ns > 1 ? ns * (ns - 1) : 0;
 }
 
+static int check_asm_params(fsv_ctx *ctx, const fsv_asm_params &P)
+{
+    if (P.k < 1 || P.k > 63 || P.w < 1 || P.w > 64 || P.lookback != 64 || P.n_rounds < 0 || P.n_rounds > 16 || P.min_anchors < 1)
+        return fsv_fail(ctx, FSV_EINVAL, "fsv_asm_params out of range (k<=63, w<=64, lookback==64)");
+    if (P.k_cap < 1 || P.k_cap > FSV_K_WIDE || P.win_rate_pm < 1 || (int)(FSV_WINDOW * (P.win_rate_pm / 1000.0)) > P.k_cap || P.accept_err_pm < 0 || P.accept_err_pm > 1000 ||
+        P.w_later < 0 || P.w_later > 64)
+        return fsv_fail(ctx, FSV_EINVAL, "fsv_asm_params error model out of range (k_cap <= 95, 375 x win_rate_pm / 1000 <= k_cap)");
+    return FSV_OK;
+}
+
 static int fsv_assemble_batch_impl(fsv_ctx *ctx, const fsv_readsets *sets, const fsv_asm_params *params, fsv_contigs *out)
 {
     if (!ctx || !sets || !out || !sets->store_dev || !sets->word_off || !sets->read_len || !sets->set_start) return FSV_EINVAL;
     if (!out->seq || !out->off || !out->set || !out->n_reads || !out->set_status) return FSV_EINVAL;
     fsv_asm_params P;
     if (params) P = *params; else fsv_asm_default_params(&P);
-    if (P.k < 1 || P.k > 63 || P.w < 1 || P.w > 64 || P.lookback != 64 || P.n_rounds < 0 || P.n_rounds > 16 || P.min_anchors < 1)
-        return fsv_fail(ctx, FSV_EINVAL, "fsv_asm_params out of range (k<=63, w<=64, lookback==64)");
-    if (P.k_cap < 1 || P.k_cap > FSV_K_WIDE || P.win_rate_pm < 1 || (int)(FSV_WINDOW * (P.win_rate_pm / 1000.0)) > P.k_cap || P.accept_err_pm < 0 || P.accept_err_pm > 1000 ||
-        P.w_later < 0 || P.w_later > 64)
-        return fsv_fail(ctx, FSV_EINVAL, "fsv_asm_params error model out of range (k_cap <= 95, 375 x win_rate_pm / 1000 <= k_cap)");
+    TRY(check_asm_params(ctx, P));
     FSV_HIP(ctx, hipSetDevice(ctx->device));
     AsmWs &W = *ws_get(ctx);
     out->n_contigs = 0; out->off[0] = 0;
@@ -1440,6 +1462,56 @@ static int fsv_sketch_reads_impl(fsv_ctx *ctx, const fsv_readsets *sets, int32_t
     return FSV_OK;
 }
 
+// The overlap stage of one pass, alone (test hook): prepare_batch -> begin_round / begin_final -> overlap_stage, and for pass 2
+// rechain_listed on the caller's pairs -- the functions assemble_chunk runs, on one pass's worth of them -- then the raw records.
+static int fsv_asm_overlaps_impl(fsv_ctx *ctx, const fsv_readsets *sets, const fsv_asm_params *params, int32_t pass, const uint32_t *rechain,
+                                 uint32_t n_rechain, fsv_ovl *ovl, uint64_t ovl_cap, uint32_t *pair_base, fsv_wtask *tasks, uint64_t task_cap,
+                                 uint32_t *n_tasks, uint32_t *overflow, uint32_t *warn)
+{
+    if (!ctx || !sets || !sets->store_dev || !sets->word_off || !sets->read_len || !sets->set_start || !pair_base || !n_tasks || !overflow || !warn) return FSV_EINVAL;
+    if (pass < 0 || pass > 2 || (n_rechain && (pass != 2 || !rechain)) || (ovl_cap && !ovl) || (task_cap && !tasks)) return fsv_fail(ctx, FSV_EINVAL, "fsv_asm_overlaps: pass is 0, 1 or 2; a pair list goes with pass 2");
+    fsv_asm_params P;
+    if (params) P = *params; else fsv_asm_default_params(&P);
+    TRY(check_asm_params(ctx, P));
+    if (pass > 0) P.n_rounds = 0;     // a final pass with no round before it: every read is sketched, no verdict of an earlier round
+    if (sets->n_reads == 0 || sets->n_sets == 0) return fsv_fail(ctx, FSV_EINVAL, "fsv_asm_overlaps: no reads");
+    if (sets->set_start[0] != 0 || sets->set_start[sets->n_sets] != sets->n_reads) return fsv_fail(ctx, FSV_EINVAL, "set_start must span [0, n_reads]");
+    for (uint32_t s = 0; s < sets->n_sets; s++) if (sets->set_start[s + 1] < sets->set_start[s]) return fsv_fail(ctx, FSV_EINVAL, "set_start not monotone");
+    FSV_HIP(ctx, hipSetDevice(ctx->device));
+    AsmWs &W = *ws_get(ctx);
+    memset(&W.stats, 0, sizeof(W.stats));
+    W.kt.reset();
+    W.n_reads = 0; W.cur_store = nullptr;     // (nothing here for fsv_asm_fetch_reads)
+    Round R(P);
+    TRY(prepare_batch(ctx, W, sets, R));
+    const Batch &B = R.B;
+    if (B.n_pairs > ovl_cap) return fsv_fail(ctx, FSV_ECAP, "fsv_asm_overlaps: ovl holds fewer than one record per ordered pair");
+    if (n_rechain > B.n_upairs) return fsv_fail(ctx, FSV_EINVAL, "fsv_asm_overlaps: more listed pairs than the batch has");
+    for (uint32_t i = 0; i < n_rechain; i++) if (rechain[i] >= B.n_upairs) return fsv_fail(ctx, FSV_EINVAL, "fsv_asm_overlaps: no such unordered pair");
+    if (pass == 0) { TRY(begin_round(ctx, W, R)); TRY(overlap_stage(ctx, W, R, false)); }
+    else { TRY(begin_final(ctx, W, R)); TRY(overlap_stage(ctx, W, R, true)); }
+    if (pass == 2 && B.n_pairs) {
+        TRY(ensure(ctx, W.inexact_list, (size_t)B.n_upairs + 4));
+        if (n_rechain) FSV_HIP(ctx, hipMemcpyAsync(W.inexact_list.p, rechain, (size_t)n_rechain * 4, hipMemcpyHostToDevice, ctx->stream));
+        FSV_HIP(ctx, hipMemcpyAsync(R.ct + CT_INEXACT, &n_rechain, 4, hipMemcpyHostToDevice, ctx->stream));
+        TRY(rechain_listed(ctx, W, R, R.ct + CT_INEXACT));
+    }
+    uint32_t h_ct[CT_SLOT];
+    FSV_HIP(ctx, hipMemcpyAsync(h_ct, R.ct, sizeof(h_ct), hipMemcpyDeviceToHost, ctx->stream));
+    TRY(download(ctx, warn, W.warn, B.n_reads));
+    if (B.n_pairs) TRY(download(ctx, ovl, W.ovl, B.n_pairs));
+    FSV_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    memcpy(pair_base, B.pair_base.data(), (size_t)(B.n_sets + 1) * 4);
+    *overflow = h_ct[CT_OVERFLOW];
+    *n_tasks = std::min(h_ct[CT_TASKS], R.task_cap);    // (after an overflow the counter has run past the array)
+    if (*n_tasks > task_cap) return fsv_fail(ctx, FSV_ECAP, "fsv_asm_overlaps: tasks too small");
+    if (*n_tasks) {
+        TRY(download(ctx, tasks, W.tasks, *n_tasks));
+        FSV_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    return FSV_OK;
+}
+
 // ---- the guarded C entry points (FSV_GUARD: no C++ exception crosses the boundary)
 extern "C" int fsv_assemble_batch(fsv_ctx *ctx, const fsv_readsets *sets, const fsv_asm_params *params, fsv_contigs *out)
 {
@@ -1461,4 +1533,11 @@ extern "C" int fsv_sketch_reads(fsv_ctx *ctx, const fsv_readsets *sets, int32_t 
                                 uint64_t out_cap, uint64_t *out_off)
 {
     FSV_GUARD(ctx, fsv_sketch_reads_impl(ctx, sets, w, k, hpc, variant, out_mz, out_cap, out_off));
+}
+
+extern "C" int fsv_asm_overlaps(fsv_ctx *ctx, const fsv_readsets *sets, const fsv_asm_params *params, int32_t pass, const uint32_t *rechain,
+                                uint32_t n_rechain, fsv_ovl *ovl, uint64_t ovl_cap, uint32_t *pair_base, fsv_wtask *tasks, uint64_t task_cap,
+                                uint32_t *n_tasks, uint32_t *overflow, uint32_t *warn)
+{
+    FSV_GUARD(ctx, fsv_asm_overlaps_impl(ctx, sets, params, pass, rechain, n_rechain, ovl, ovl_cap, pair_base, tasks, task_cap, n_tasks, overflow, warn));
 }

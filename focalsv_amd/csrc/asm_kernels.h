@@ -354,7 +354,8 @@ __device__ __forceinline__ void chain_pair(const ChainArgs &A, unsigned char *s_
         //   repair       the first anchor whose hypothesis fails (an illegal link, a better candidate) and the few behind it go
         //                through the sequential step -- the 64 predecessors in registers, lane l = anchor i-1-l, handed on by
         //                DPP wave_shr -- and the blocks resume after them.
-        // By induction over the anchors the result is the sequential DP's, bit for bit (tests/test_gpu_asm.py against the oracle).
+        // By induction over the anchors the result is the sequential DP's, bit for bit (tests/test_gpu_chain.py: every record and window task
+        // against the oracle, on the pairs of tests/chain_cases.py).
         dp_t *const s_sl = SHORT ? (dp_t *)s_chain : (dp_t *)(s_rest + 8 * (size_t)AMAX);   // chain span per anchor (free arrays during the DP)
         const int kk = A.k_score;
         // candidate (i <- j): score or -1, with the chain's indel sum / span it would give

@@ -272,6 +272,25 @@ int fsv_asm_last_stats(const fsv_ctx *ctx, fsv_asm_stats *out);
  * can be fetched as ASCII (same order as the input reads). */
 int fsv_asm_fetch_reads(fsv_ctx *ctx, char *seq, uint64_t seq_cap, uint64_t *off, uint32_t n_reads);
 
+/* Test hook: the overlap stage of ONE pass of fsv_assemble_batch on the caller's read sets, up to the end of chaining -- sketch, per-read
+ * index, k_chain -- through the code the batch call runs (same launches, same tile choice), and the raw records it leaves.
+ *   pass 0  a correction round: bw_ec, min_anchors, min_ovlp; window tasks are emitted
+ *   pass 1  the final pass (as with n_rounds = 0): w_later, bw_final, min_anchors_final, min_ovlp_final; no tasks
+ *   pass 2  pass 1, then the gapped re-chain (bw_rechain, either direction chained from its own side) of the n_rechain unordered
+ *           pairs listed in `rechain`; the slots of the other pairs keep their pass-1 records
+ * ovl       one record per ORDERED pair slot, ovl_cap >= sum over the sets of ns (ns - 1).  Set s owns slots [pair_base[s],
+ *           pair_base[s + 1]); with q, t the read indices inside the set (ns reads), the slot of (q, t) is
+ *           pair_base[s] + q (ns - 1) + (t < q ? t : t - 1).  A slot without an overlap has valid == 0.
+ * pair_base n_sets + 1 entries (out).  The UNORDERED pair (q < t) of set s has index pair_base[s] / 2 + q (2 ns - q - 1) / 2 + (t - q - 1):
+ *           the entries of `rechain`.
+ * tasks     the window tasks in the order the kernel's atomics gave them (an overlap's tasks are [first_win, first_win + n_win));
+ *           task_cap >= sum over the sets of (grid windows of the set) x (ns - 1) always suffices.  *n_tasks: how many.
+ * overflow  1 when the library's own task array ran full (then the overlaps hit have valid == 0)
+ * warn      n_reads words of FSV_W_* bits, per read */
+int fsv_asm_overlaps(fsv_ctx *ctx, const fsv_readsets *sets, const fsv_asm_params *params, int32_t pass, const uint32_t *rechain,
+                     uint32_t n_rechain, fsv_ovl *ovl, uint64_t ovl_cap, uint32_t *pair_base, fsv_wtask *tasks, uint64_t task_cap,
+                     uint32_t *n_tasks, uint32_t *overflow, uint32_t *warn);
+
 /* ---- K1 exposed: minimizer sketch of every read (ha_sketch, sketch.cpp:39-137) -------------------------
  * out_mz receives, per read, its minimizers in position order; out_off (n_reads+1) indexes them.
  * variant: 0 = library's choice (position-parallel kernel for odd k, deque replay otherwise), 1 = force the replay kernel.

@@ -110,14 +110,16 @@ static int anchor_cmp(const void *a, const void *b)
     return 0;
 }
 
-/* returns 1 and fills *o (+ chain anchors, sorted by qe) when the pair overlaps */
-int orc_chain_pair(const orc_mz *q, int nq, int lenq, const orc_mz *t, int nt, int lent, const orc_asm_params *P,
-                   int bw_per_mille, orc_ovl *o, int32_t *chain_qe, int32_t *chain_te, int chain_cap)
+/* returns 1 and fills *o (+ chain anchors, sorted by qe) when the pair overlaps.
+ * info (ORC_CI_COUNT ints, or NULL): what the DP met on the way -- the tests classify read pairs by it (tests/chain_cases.py) */
+int orc_chain_pair_ex(const orc_mz *q, int nq, int lenq, const orc_mz *t, int nt, int lent, const orc_asm_params *P,
+                      int bw_per_mille, orc_ovl *o, int32_t *chain_qe, int32_t *chain_te, int chain_cap, int *info)
 {
     anchor_t *a;
     int32_t *f, *pre, *ind, *sl;
     int i, j, n = 0, nf = 0, nr = 0, rev, best = -1, ok = 0;
     int cap = nq < nt ? nq : nt;
+    if (info) { for (i = 0; i < ORC_CI_COUNT; i++) info[i] = 0; info[ORC_CI_FIRST] = info[ORC_CI_BEST] = -1; }
     if (cap <= 0) return 0;
     a = (anchor_t *)malloc(sizeof(anchor_t) * (size_t)cap * 2);
     {
@@ -155,29 +157,49 @@ int orc_chain_pair(const orc_mz *q, int nq, int lenq, const orc_mz *t, int nt, i
         n = j;
         free(srev); free(tspan); free(qspan);
     }
+    if (info) { info[ORC_CI_ANCHORS] = n; info[ORC_CI_NFWD] = nf; info[ORC_CI_NREV] = nr; }
     if (n < P->min_anchors) { free(a); return 0; }
     qsort(a, (size_t)n, sizeof(anchor_t), anchor_cmp);
+    if (info) {
+        info[ORC_CI_ONE_DIAG] = 1;
+        for (i = 1; i < n; i++) if (a[i].te - a[i].qe != a[0].te - a[0].qe) info[ORC_CI_ONE_DIAG] = 0;
+    }
 
     f = (int32_t *)malloc(sizeof(int32_t) * (size_t)n * 4);
     pre = f + n; ind = pre + n; sl = ind + n;
+    {
+    int run = 0;    /* consecutive anchors whose link is not to the anchor before them */
     for (i = 0; i < n; i++) {
         int32_t bs = P->k, bp = -1, bi = 0, bl = 0;
-        int lo = i - P->lookback < 0 ? 0 : i - P->lookback;
+        int lo = i - P->lookback < 0 ? 0 : i - P->lookback, tied = 0;
         for (j = i - 1; j >= lo; j--) { /* nearest predecessor first; strict '>' keeps the nearest on ties */
             int32_t dq = a[i].qe - a[j].qe, dt = a[i].te - a[j].te, gap, ti, tl, sc;
             if (dq <= 0 || dt <= 0) continue;
             gap = dq > dt ? dq - dt : dt - dq;
             ti = ind[j] + gap; tl = sl[j] + dq;
-            if ((int64_t)ti * 1000 > (int64_t)tl * bw_per_mille) continue; /* bw 0 = co-linear anchors only */
+            if ((int64_t)ti * 1000 > (int64_t)tl * bw_per_mille) { if (info && j == i - 1) info[ORC_CI_REFUSED]++; continue; } /* bw 0 = co-linear anchors only */
             sc = dq < dt ? dq : dt;
             if (sc > P->k) sc = P->k;
             if (ti) sc -= (int32_t)(((int64_t)ti * sc * 1000) / ((int64_t)tl * bw_per_mille));
             sc += f[j];
-            if (sc > bs) { bs = sc; bp = j; bi = ti; bl = tl; }
+            if (sc > bs) { bs = sc; bp = j; bi = ti; bl = tl; tied = 0; }
+            else if (sc == bs && bp >= 0) tied = 1;
         }
         f[i] = bs; pre[i] = bp; ind[i] = bi; sl[i] = bl;
+        if (info && i > 0) {
+            if (bp != i - 1) { info[ORC_CI_NOT_PREV]++; run++; if (run > info[ORC_CI_NOT_PREV_RUN]) info[ORC_CI_NOT_PREV_RUN] = run; }
+            else run = 0;
+            info[ORC_CI_PRED_TIES] += tied;
+        }
+    }
     }
     for (i = 0; i < n; i++) if (best < 0 || f[i] > f[best]) best = i;
+    if (info) {
+        int c;
+        for (i = 0; i < n; i++) if (i != best && f[i] == f[best]) info[ORC_CI_END_TIES]++;
+        for (c = best; pre[c] >= 0; c = pre[c]) {}
+        info[ORC_CI_FIRST] = c; info[ORC_CI_BEST] = best;
+    }
     {
         int cnt = 0, c;
         for (c = best; c >= 0; c = pre[c]) cnt++;
@@ -210,6 +232,12 @@ int orc_chain_pair(const orc_mz *q, int nq, int lenq, const orc_mz *t, int nt, i
     }
     free(f); free(a);
     return ok;
+}
+
+int orc_chain_pair(const orc_mz *q, int nq, int lenq, const orc_mz *t, int nt, int lent, const orc_asm_params *P,
+                   int bw_per_mille, orc_ovl *o, int32_t *chain_qe, int32_t *chain_te, int chain_cap)
+{
+    return orc_chain_pair_ex(q, nq, lenq, t, nt, lent, P, bw_per_mille, o, chain_qe, chain_te, chain_cap, NULL);
 }
 
 /* diagonal (te - qe) predicted for query position x: last chain anchor with qe <= x, else the first anchor */
@@ -513,6 +541,30 @@ static void free_sketch(const readset *R, orc_mz **uq, int *nuq)
     free(uq); free(nuq);
 }
 
+/* The window grid of the overlaps (Correct.cpp:306-531): overlap i owns windows [first_win, first_win + n_win), one per 375-base
+ * grid cell of the query that it touches; returns their number */
+static int window_ranges(orc_ovl *ov, int n_ov)
+{
+    int i, total = 0;
+    for (i = 0; i < n_ov; i++) {
+        ov[i].first_win = total;
+        ov[i].n_win = ov[i].x_e / ORC_WINDOW - ov[i].x_s / ORC_WINDOW + 1;
+        total += ov[i].n_win;
+    }
+    return total;
+}
+
+/* window j of overlap o: the part of its grid cell inside the overlap, the threshold for that length, and where the chain puts
+ * its first base on the target */
+static void window_grid(const orc_asm_params *P, const orc_ovl *o, int j, const int32_t *cq, const int32_t *ct, orc_win *w)
+{
+    const int gs = (o->x_s / ORC_WINDOW + j) * ORC_WINDOW, ge = gs + ORC_WINDOW - 1;
+    w->x_start = gs > o->x_s ? gs : o->x_s;
+    w->x_len = (int16_t)((ge < o->x_e ? ge : o->x_e) - w->x_start + 1);
+    w->k = (uint8_t)orc_thr_for_len_p(P, w->x_len);
+    w->y_start = w->x_start + diag_at(cq + o->chain_off, ct + o->chain_off, o->n_chain, w->x_start);
+}
+
 /* Build + verify + rescue + accept + path every window of every overlap of the set.
  * Returns the window array (owned by caller); ov[].first_win/n_win index into it. */
 static orc_win *align_overlaps(const readset *R, const orc_asm_params *P, orc_ovl *ov, int n_ov, const int32_t *cq, const int32_t *ct, int *n_win_out)
@@ -525,26 +577,18 @@ static orc_win *align_overlaps(const readset *R, const orc_asm_params *P, orc_ov
     uint8_t tmp[2 * ORC_WINDOW + 4 * ORC_K_WIDE + 16];
     int rl[2 * ORC_WINDOW + 64];
     uint8_t ro[2 * ORC_WINDOW + 64];
-    for (i = 0; i < n_ov; i++) {
-        ov[i].first_win = total;
-        ov[i].n_win = ov[i].x_e / ORC_WINDOW - ov[i].x_s / ORC_WINDOW + 1;
-        total += ov[i].n_win;
-    }
+    total = window_ranges(ov, n_ov);
     W = (orc_win *)calloc((size_t)total + 1, sizeof(orc_win));
     for (i = 0; i < n_ov; i++) {
         orc_ovl *o = &ov[i];
         const char *x = R->seq[o->q], *y = R->seq[o->t];
-        int ylen = R->len[o->t], w0 = o->x_s / ORC_WINDOW;
+        int ylen = R->len[o->t];
         int64_t tlen = 0, terr = 0;
         o->align_len = 0;
         for (j = 0; j < o->n_win; j++) {
             orc_win *w = &W[o->first_win + j];
-            int gs = (w0 + j) * ORC_WINDOW, ge = gs + ORC_WINDOW - 1;
             w->ovl = (uint32_t)i; w->win = (uint32_t)j;
-            w->x_start = gs > o->x_s ? gs : o->x_s;
-            w->x_len = (int16_t)((ge < o->x_e ? ge : o->x_e) - w->x_start + 1);
-            w->k = (uint8_t)orc_thr_for_len_p(P, w->x_len);
-            w->y_start = w->x_start + diag_at(cq + o->chain_off, ct + o->chain_off, o->n_chain, w->x_start);
+            window_grid(P, o, j, cq, ct, w);
             window_verify(x, y, ylen, o->rev, w, ybuf, P->k_cap);
             if (w->err >= 0) o->align_len += w->x_len;
         }
@@ -1641,4 +1685,74 @@ done:
     for (r = 0; r < n_reads; r++) free(R.seq[r]);
     free(R.seq); free(R.len); free(hits); free(piece_read); free(piece_len); free(piece_rev); free(contig_first);
     return 0;
+}
+
+/* ---------------------------------------------------------------- the overlap stage alone (tests/test_gpu_chain.py)
+ * What one pass over a read set computes up to the end of chaining, from the functions above:
+ *   pass 0  a correction round: P->w, bw_ec, min_anchors, min_ovlp; the overlaps of collect_overlaps and the window grid of
+ *           align_overlaps (x_start, x_len, y_start, k per window; overlap i owns win[first_win .. first_win + n_win));
+ *   pass 1  the final pass: w_later (or w), bw_final, min_anchors_final, min_ovlp_final; no windows (n_win = 0);
+ *   pass 2  the final pass's gapped re-chain: as pass 1 with bw_rechain, every pair chained from both sides (both_ways).
+ * ovl: sorted by (q, t), chain_off into cq / ct (anchors in query order, target in strand coordinates).  nuq: unique minimizers
+ * per read.  pair_info: ORC_CI_COUNT counters of orc_chain_pair_ex per unordered pair (q < t, row-major), chained from q.
+ * Returns the number of overlaps, or -1 when a capacity is too small. */
+int orc_set_overlaps(const char *seqs, const uint64_t *seq_off, int n_reads, const orc_asm_params *P0, int pass,
+                     orc_ovl *ovl, int ovl_cap, int32_t *cq_out, int32_t *ct_out, int chain_cap, orc_gwin *win, int win_cap, int *n_win_out,
+                     int32_t *nuq_out, int32_t *pair_info)
+{
+    readset R;
+    orc_asm_params Pf = *P0;
+    orc_mz **uq; int *nuq, n_ov, n_win = 0, i, j, r, q, t, used = 0, rc;
+    orc_ovl *ov; int32_t *cq, *ct;
+    const int bw = pass == 0 ? P0->bw_ec : pass == 1 ? P0->bw_final : P0->bw_rechain;
+    if (pass != 0) {
+        Pf.min_anchors = P0->min_anchors_final > 0 ? P0->min_anchors_final : P0->min_anchors;
+        Pf.min_ovlp = P0->min_ovlp_final > 0 ? P0->min_ovlp_final : P0->min_ovlp;
+    }
+    R.n = n_reads;
+    R.seq = (char **)malloc(sizeof(char *) * (size_t)n_reads);
+    R.len = (int *)malloc(sizeof(int) * (size_t)n_reads);
+    for (r = 0; r < n_reads; r++) { R.seq[r] = (char *)seqs + seq_off[r]; R.len[r] = (int)(seq_off[r + 1] - seq_off[r]); }
+    sketch_set(&R, &Pf, pass != 0 && Pf.w_later > 0 ? Pf.w_later : Pf.w, &uq, &nuq);
+    g_both_ways = pass == 2;
+    collect_overlaps(&R, &Pf, bw, uq, nuq, &ov, &cq, &ct, &n_ov);
+    g_both_ways = 0;
+    for (i = 0; i < n_ov; i++) used += ov[i].n_chain;
+    if (pass == 0) n_win = window_ranges(ov, n_ov);
+    else for (i = 0; i < n_ov; i++) { ov[i].first_win = 0; ov[i].n_win = 0; }
+    rc = n_ov;
+    if (n_ov > ovl_cap || used > chain_cap || n_win > win_cap) rc = -1;
+    else {
+        int at = 0;
+        for (i = 0; i < n_ov; i++) {       /* the chains, packed in the overlaps' order */
+            memcpy(cq_out + at, cq + ov[i].chain_off, sizeof(int32_t) * (size_t)ov[i].n_chain);
+            memcpy(ct_out + at, ct + ov[i].chain_off, sizeof(int32_t) * (size_t)ov[i].n_chain);
+            ov[i].chain_off = at; at += ov[i].n_chain;
+            for (j = 0; j < ov[i].n_win; j++) {
+                orc_win w;
+                orc_gwin *g = &win[ov[i].first_win + j];
+                window_grid(&Pf, &ov[i], j, cq_out, ct_out, &w);
+                g->x_start = w.x_start; g->x_len = w.x_len; g->y_start = w.y_start; g->k = w.k;
+            }
+            ovl[i] = ov[i];
+        }
+        *n_win_out = n_win;
+        if (nuq_out) for (r = 0; r < n_reads; r++) nuq_out[r] = nuq[r];
+        if (pair_info) {
+            int maxn = 1;
+            int32_t *tq, *tt;
+            for (r = 0; r < n_reads; r++) if (nuq[r] > maxn) maxn = nuq[r];
+            tq = (int32_t *)malloc(sizeof(int32_t) * (size_t)maxn * 2); tt = tq + maxn;
+            for (q = 0, i = 0; q < n_reads; q++)
+                for (t = q + 1; t < n_reads; t++, i++) {
+                    orc_ovl o;
+                    orc_chain_pair_ex(uq[q], nuq[q], R.len[q], uq[t], nuq[t], R.len[t], &Pf, bw, &o, tq, tt, maxn, pair_info + (size_t)i * ORC_CI_COUNT);
+                }
+            free(tq);
+        }
+    }
+    free(ov); free(cq); free(ct);
+    free_sketch(&R, uq, nuq);
+    free(R.seq); free(R.len);
+    return rc;
 }

@@ -79,6 +79,23 @@ int orc_double_thr_p(const orc_asm_params *P, int pre, int x_len);
 int orc_unique_sorted(orc_mz *mz, int n);
 int orc_chain_pair(const orc_mz *q, int nq, int lenq, const orc_mz *t, int nt, int lent, const orc_asm_params *P,
                    int bw_per_mille, orc_ovl *o, int32_t *chain_qe, int32_t *chain_te, int chain_cap);
+/* orc_chain_pair, and what its DP met (info: ORC_CI_COUNT ints) */
+enum { ORC_CI_ANCHORS,      /* anchors on the majority strand */
+       ORC_CI_NFWD, ORC_CI_NREV, /* shared minimizers per strand (reverse wins when there are more of them) */
+       ORC_CI_ONE_DIAG,     /* 1: all those anchors share one diagonal */
+       ORC_CI_NOT_PREV,     /* anchors (from the second on) whose link is not to the anchor before them */
+       ORC_CI_NOT_PREV_RUN, /* longest run of consecutive such anchors */
+       ORC_CI_REFUSED,      /* links to the anchor before that the indel budget refused */
+       ORC_CI_PRED_TIES,    /* anchors whose best score two predecessors reached (the nearer one is linked) */
+       ORC_CI_END_TIES,     /* other anchors that score as much as the best chain end (the first one is the end) */
+       ORC_CI_FIRST, ORC_CI_BEST, /* index of the best chain's first and last anchor among the ORC_CI_ANCHORS */
+       ORC_CI_COUNT };
+int orc_chain_pair_ex(const orc_mz *q, int nq, int lenq, const orc_mz *t, int nt, int lent, const orc_asm_params *P,
+                      int bw_per_mille, orc_ovl *o, int32_t *chain_qe, int32_t *chain_te, int chain_cap, int *info);
+typedef struct { int32_t x_start, x_len, y_start, k; } orc_gwin;   /* a window of the grid align_overlaps lays over an overlap */
+int orc_set_overlaps(const char *seqs, const uint64_t *seq_off, int n_reads, const orc_asm_params *P, int pass,
+                     orc_ovl *ovl, int ovl_cap, int32_t *cq, int32_t *ct, int chain_cap, orc_gwin *win, int win_cap, int *n_win,
+                     int32_t *nuq, int32_t *pair_info);
 void orc_asm_default_params(orc_asm_params *P);
 int orc_layout_graph(const char *const *seq, const int *len, int n, const orc_ovl *hit, int n_hit, int min_reads, int32_t *piece_read,
                      uint8_t *piece_rev, int32_t *piece_len, int32_t *contig_first, int piece_cap, int contig_cap);

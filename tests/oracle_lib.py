@@ -215,3 +215,57 @@ def align_contig_multi(contig: bytes, ref: bytes, params=None, max_rec=5):
         out.append({"ref_start": a.ref_start, "ref_end": a.ref_end, "rev": int(a.rev), "mapq": int(a.mapq), "q_start": a.q_start, "q_end": a.q_end,
                     "cigar": [(int(x) & 0xf, int(x) >> 4) for x in c], "raw": c.copy()})
     return out
+
+
+# ---- the overlap stage alone: orc_set_overlaps / orc_chain_pair_ex (oracle/asm.c)
+OVL_DTYPE = np.dtype([("q", "<u4"), ("t", "<u4"), ("x_s", "<i4"), ("x_e", "<i4"), ("y_s", "<i4"), ("y_e", "<i4"), ("score", "<i4"), ("n_chain", "<i4"),
+                      ("chain_off", "<i4"), ("first_win", "<i4"), ("n_win", "<i4"), ("align_len", "<i4"), ("err_sum", "<i4"),
+                      ("rev", "u1"), ("is_match", "u1"), ("exact", "u1"), ("pad", "u1")])
+GWIN_DTYPE = np.dtype([("x_start", "<i4"), ("x_len", "<i4"), ("y_start", "<i4"), ("k", "<i4")])
+assert OVL_DTYPE.itemsize == 56 and GWIN_DTYPE.itemsize == 16
+# the counters of orc_chain_pair_ex, in the order of oracle.h's ORC_CI_*
+CHAIN_INFO = ("anchors", "nfwd", "nrev", "one_diag", "not_prev", "not_prev_run", "refused", "pred_ties", "end_ties", "first", "best")
+
+
+def unique_sorted(mz):
+    """a read's sketch -> its minimizers whose hash occurs once, sorted by hash (orc_unique_sorted)"""
+    mz = np.ascontiguousarray(mz, dtype=MZ_DTYPE).copy()
+    n = lib().orc_unique_sorted(mz.ctypes.data_as(C.c_void_p), len(mz))
+    return mz[:n]
+
+
+def chain_pair_info(uq, lenq, ut, lent, params, bw):
+    """orc_chain_pair_ex on two unique-sorted lists -> (overlap record or None, chain (qe, te) arrays, dict of CHAIN_INFO)"""
+    cap = max(1, min(len(uq), len(ut)))
+    o = np.zeros(1, dtype=OVL_DTYPE)
+    cq, ct = np.zeros(cap, dtype=np.int32), np.zeros(cap, dtype=np.int32)
+    info = (C.c_int * len(CHAIN_INFO))()
+    vp = lambda a: a.ctypes.data_as(C.c_void_p)
+    ok = lib().orc_chain_pair_ex(vp(uq), len(uq), int(lenq), vp(ut), len(ut), int(lent), C.byref(params), int(bw), vp(o), vp(cq), vp(ct), cap, info)
+    n = int(o[0]["n_chain"]) if ok else 0
+    return (o[0] if ok else None), (cq[:n], ct[:n]), dict(zip(CHAIN_INFO, info))
+
+
+def set_overlaps(reads, params, pass_=0):
+    """orc_set_overlaps on one read set (list of str) -> dict: ovl (sorted by q, t; chain_off / first_win index cq, ct / win), cq, ct,
+    win (pass 0), nuq (unique minimizers per read), info (one row of CHAIN_INFO counters per unordered pair q < t, row-major)"""
+    n = len(reads)
+    off = np.zeros(n + 1, dtype=np.uint64)
+    np.cumsum([len(r) for r in reads], out=off[1:])
+    seqs = "".join(reads).encode()
+    total = int(off[-1])
+    n_up = n * (n - 1) // 2
+    ovl = np.zeros(max(1, 2 * n_up), dtype=OVL_DTYPE)
+    chain_cap = max(1, (n - 1) * total * 2)
+    cq, ct = np.zeros(chain_cap, dtype=np.int32), np.zeros(chain_cap, dtype=np.int32)
+    win_cap = max(1, (n - 1) * (total // 375 + n))
+    win = np.zeros(win_cap, dtype=GWIN_DTYPE)
+    nuq = np.zeros(max(1, n), dtype=np.int32)
+    info = np.zeros((max(1, n_up), len(CHAIN_INFO)), dtype=np.int32)
+    n_win = C.c_int(0)
+    vp = lambda a: a.ctypes.data_as(C.c_void_p)
+    n_ov = lib().orc_set_overlaps(seqs, vp(off), n, C.byref(params), int(pass_), vp(ovl), 2 * n_up, vp(cq), vp(ct), chain_cap, vp(win), win_cap,
+                                  C.byref(n_win), vp(nuq), vp(info))
+    assert n_ov >= 0, "orc_set_overlaps: a capacity was too small"
+    used = int(ovl["n_chain"][:n_ov].sum())
+    return {"ovl": ovl[:n_ov], "cq": cq[:used], "ct": ct[:used], "win": win[: n_win.value], "nuq": nuq[:n], "info": info[:n_up]}
