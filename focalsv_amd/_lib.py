@@ -32,7 +32,7 @@ assert OVL_DTYPE.itemsize == 56
 class AsmParams(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("k", "w", "hpc", "n_rounds", "min_ovlp", "min_anchors", "lookback", "bw_ec", "bw_final",
                                          "min_contig_reads", "win_rate_pm", "k_cap", "accept_err_pm", "bw_rechain", "w_later", "partition", "second_round", "ins_dag",
-                                         "min_anchors_final", "min_ovlp_final", "graph_layout", "junction_cigars")]
+                                         "min_anchors_final", "min_ovlp_final", "graph_layout", "junction_cigars", "kmer_table")]
 
 
 class ReadSets(C.Structure):
@@ -45,6 +45,12 @@ SET_UNPHASED = 1
 OK, ENODEV, EINVAL, ENOMEM, EHIP, ECAP, EUNSUP = 0, -1, -2, -3, -4, -5, -6
 # set_status warning bits (FSV_W_*)
 W_MZ_TRUNC, W_ANCHOR_TRUNC, W_NO_LAYOUT, W_INS_EVENTS, W_WINDOW_KEPT, W_INTERNAL, W_SITES = 1, 2, 4, 8, 16, 32, 64
+W_LOW_COV = 128
+KMER_BINS = 4096
+# fsv_kmer_set: the verdict of the k-mer count table stage on one read set
+KMER_SET_DTYPE = np.dtype([("peak_hom", "<i4"), ("peak_het", "<i4"), ("cutoff", "<i4"), ("low_i", "<i4"), ("max_i", "<i4"), ("pad", "<i4"),
+                           ("n_entries", "<u8"), ("n_distinct", "<u8"), ("n_filtered", "<u8"), ("n_indexed", "<u8")])
+assert KMER_SET_DTYPE.itemsize == 56
 
 
 class Contigs(C.Structure):
@@ -142,6 +148,9 @@ def load():
         "fsv_sketch_reads": (C.c_int, [vp, C.POINTER(ReadSets), C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, C.c_uint64, vp]),
         "fsv_asm_overlaps": (C.c_int, [vp, C.POINTER(ReadSets), C.POINTER(AsmParams), C.c_int32, vp, C.c_uint32, vp, C.c_uint64, vp, vp, C.c_uint64,
                                        u32p, u32p, vp]),
+        "fsv_kmer_peaks": (C.c_int, [vp, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+        "fsv_kmer_table": (C.c_int, [vp, C.POINTER(ReadSets), C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, C.c_uint64, vp]),
+        "fsv_asm_last_kmer_table": (C.c_int, [vp, vp, C.c_uint32, C.POINTER(C.c_double)]),
         "fsv_aln_default_params": (None, [C.POINTER(AlnParams)]),
         "fsv_align_batch": (C.c_int, [vp, vp, vp, C.c_uint32, vp, vp, vp, C.c_uint32, C.POINTER(AlnParams), C.POINTER(Alns)]),
         "fsv_aln_last_stats": (C.c_int, [vp, C.POINTER(AlnStats)]),
@@ -195,6 +204,17 @@ def join_refs(refs):
     roff = np.zeros(len(refs) + 1, dtype=np.uint64)
     np.cumsum([len(r) for r in refs], out=roff[1:])
     return np.frombuffer(b"".join(refs) + b"\0", dtype=np.uint8), roff
+
+
+def kmer_peaks(hist, start_cnt=5):
+    """fsv_kmer_peaks (host only, no GPU): hifiasm's ha_analyze_count on a k-mer count histogram
+    -> (peak_hom, peak_het, low_i, max_i); peak_hom -1 when the histogram has no coverage peak"""
+    h = np.ascontiguousarray(hist, dtype=np.int64)
+    het, low, mx = C.c_int32(), C.c_int32(), C.c_int32()
+    hom = load().fsv_kmer_peaks(_ptr(h), len(h), int(start_cnt), C.byref(het), C.byref(low), C.byref(mx))
+    if hom < -1:
+        raise FsvError(hom, "fsv_kmer_peaks")
+    return hom, het.value, low.value, mx.value
 
 
 def path_ops(p) -> bytes:
@@ -383,6 +403,32 @@ class Context:
         self.check(self._lib.fsv_asm_overlaps(self._h, C.byref(rs), C.byref(p), int(pass_), _ptr(lst) if len(lst) else None, len(lst), _ptr(ovl), n_pairs,
                                               _ptr(pair_base), _ptr(tasks), task_cap, C.byref(n_tasks), C.byref(overflow), _ptr(warn)), "fsv_asm_overlaps")
         return ovl[:n_pairs], pair_base, tasks[: n_tasks.value], int(overflow.value), warn[: len(read_len)]
+
+    def kmer_table(self, store_dev, word_off, read_len, set_start, w=1, k=51, hpc=1, want_hist=True, want_filter=True):
+        """fsv_kmer_table: the k-mer count table stage alone, per read set -> (sets[KMER_SET_DTYPE], hist uint64[n_sets, 4096] or None,
+        filter: list of ascending uint64 arrays, one per set, or None)"""
+        word_off = np.ascontiguousarray(word_off, dtype=np.uint64)
+        read_len = np.ascontiguousarray(read_len, dtype=np.int32)
+        set_start = np.ascontiguousarray(set_start, dtype=np.uint32)
+        n_sets = len(set_start) - 1
+        rs = ReadSets(C.c_void_p(store_dev), _ptr(word_off).value, _ptr(read_len).value, _ptr(set_start).value, len(read_len), n_sets, None)
+        out = np.zeros(max(1, n_sets), dtype=KMER_SET_DTYPE)
+        hist = np.zeros((max(1, n_sets), KMER_BINS), dtype=np.uint64) if want_hist else None
+        cap = int(read_len.astype(np.int64).sum()) + 1 if want_filter else 0       # at most one key per base
+        flt = np.zeros(cap, dtype=np.uint64) if want_filter else None
+        off = np.zeros(n_sets + 1, dtype=np.uint64) if want_filter else None
+        self.check(self._lib.fsv_kmer_table(self._h, C.byref(rs), int(w), int(k), int(hpc), _ptr(out), None if hist is None else _ptr(hist),
+                                            None if flt is None else _ptr(flt), cap, None if off is None else _ptr(off)), "fsv_kmer_table")
+        lists = None if flt is None else [flt[int(off[s]):int(off[s + 1])].copy() for s in range(n_sets)]
+        return out[:n_sets], (None if hist is None else hist[:n_sets]), lists
+
+    def last_kmer_table(self, n_sets):
+        """fsv_asm_last_kmer_table: the verdicts of the last assemble_batch with kmer_table = 1, in set order
+        -> (sets[KMER_SET_DTYPE], the stage's summed kernel time in ms)"""
+        out = np.zeros(max(1, n_sets), dtype=KMER_SET_DTYPE)
+        ms = C.c_double(0.0)
+        self.check(self._lib.fsv_asm_last_kmer_table(self._h, _ptr(out), int(n_sets), C.byref(ms)), "fsv_asm_last_kmer_table")
+        return out[:n_sets], ms.value
 
     def asm_stats(self):
         st = AsmStats()

@@ -50,11 +50,19 @@ def find_read_sets(regions_dir: str, data_type: int = 0) -> List[str]:
     return out
 
 
-def _set_cost(reads) -> int:
-    """device bytes a read set needs, dominated by the window-task bound: every read against every other, 176 B per window"""
+def _set_cost(reads, kmer_table: bool = False) -> int:
+    """device bytes a read set needs, dominated by the window-task bound: every read against every other, 176 B per window; with the
+    k-mer count table stage, its table besides (12 B a slot, a power of two of at least twice the bases) and the filter list (8 B a base)"""
     n = len(reads)
     win = sum((len(r) + 374) // 375 for r in reads)
-    return (n - 1) * win * 176 + n * n * 72 + sum(len(r) for r in reads) * 24 if n > 1 else 4096
+    bases = sum(len(r) for r in reads)
+    table = 0
+    if kmer_table and bases:
+        slots = 1024
+        while slots < 2 * bases:
+            slots *= 2
+        table = slots * 12 + bases * 8 + 4096 * 4
+    return ((n - 1) * win * 176 + n * n * 72 + bases * 24 if n > 1 else 4096) + table
 
 
 def assemble_sets(ctx: _lib.Context, sets, logger=None, budget_bytes: Optional[int] = None, set_flags=None, params=None):
@@ -92,7 +100,7 @@ def assemble_sets(ctx: _lib.Context, sets, logger=None, budget_bytes: Optional[i
 
     batch, used = [], 0
     for i, rs in enumerate(sets):
-        c = _set_cost(rs)
+        c = _set_cost(rs, bool(params is not None and params.kmer_table))
         if batch and used + c > budget_bytes:
             run_or_split(batch)
             batch, used = [], 0
@@ -104,8 +112,10 @@ def assemble_sets(ctx: _lib.Context, sets, logger=None, budget_bytes: Optional[i
 
 
 def assembly(out_dir: str, cpu: int = 10, threads: int = 8, data_type: int = 0, logger=None, ctx: Optional[_lib.Context] = None,
-             device: int = 0, skip_existing: bool = True) -> Dict[str, int]:
-    """3_assembly.py:28-41.  cpu/threads are accepted for CLI compatibility (the GPU batch replaces both)."""
+             device: int = 0, skip_existing: bool = True, kmer_table: bool = False) -> Dict[str, int]:
+    """3_assembly.py:28-41.  cpu/threads are accepted for CLI compatibility (the GPU batch replaces both).
+    kmer_table: run hifiasm's k-mer count table per read set first (fsv_asm_params.kmer_table): a set whose count histogram has no
+    coverage peak is left as hifiasm leaves it -- no contig, status bit 128 -- instead of being assembled"""
     logger = logger or setup_logging("3_ASSEMBLY", out_dir)
     regions_dir = os.path.join(out_dir, "regions")
     fas = find_read_sets(regions_dir, data_type)
@@ -123,7 +133,9 @@ def assembly(out_dir: str, cpu: int = 10, threads: int = 8, data_type: int = 0, 
         own = ctx is None
         ctx = ctx or _lib.Context(device)
         try:
-            per_set = assemble_sets(ctx, sets, logger, params=ctx.clr_asm_params() if data_type == 1 else ctx.ont_asm_params())
+            params = ctx.clr_asm_params() if data_type == 1 else ctx.ont_asm_params()
+            params.kmer_table = int(bool(kmer_table))
+            per_set = assemble_sets(ctx, sets, logger, params=params)
         finally:
             if own:
                 ctx.close()
@@ -153,7 +165,10 @@ def assembly(out_dir: str, cpu: int = 10, threads: int = 8, data_type: int = 0, 
         own = ctx is None
         ctx = ctx or _lib.Context(device)
         try:
-            per_set = assemble_sets(ctx, sets, logger, set_flags=[_lib.SET_UNPHASED if 'unphased' in os.path.basename(f) else 0 for f in fas])
+            params = ctx.default_asm_params()
+            params.kmer_table = int(bool(kmer_table))
+            per_set = assemble_sets(ctx, sets, logger, set_flags=[_lib.SET_UNPHASED if 'unphased' in os.path.basename(f) else 0 for f in fas],
+                                    params=params if kmer_table else None)
         finally:
             if own:
                 ctx.close()

@@ -5,6 +5,7 @@
 // kernels of asm_kernels.h, k_consensus.h and k_sketch.h; the host only sizes buffers between stages and walks the (tiny, <= a few
 // hundred nodes per set) overlap graph, which is host code in hifiasm as well (Overlaps.cpp).
 #include "asm_kernels.h"
+#include "k_kmer.h"
 #include "layout.h"
 #include <algorithm>
 #include <chrono>
@@ -79,6 +80,13 @@ struct AsmWs {
     Dev<uint64_t> cols;          // k_path_dp's column scratch: 64-bit columns, or 32-bit ones in the same bytes
     Dev<unsigned long long> tmp; // cycle stamps of the diagnostic runs
     Dev<uint8_t> cov3, bnd_bytes, exact_flag, cwin, thr_tab; Dev<uint16_t> cwin_len; Dev<char> contig_out, contig_all;
+    // the k-mer count table stage (k_kmer.h): one open-addressed table per set back to back (keys, counts), the sets' histograms, the
+    // filter list of the last stage and -- for a batch of several chunks -- of all its chunks, in set order
+    Dev<unsigned long long> km_keys, km_flt, km_flt_all; Dev<uint32_t> km_cnt, km_hist, km_cursor, km_err; Dev<uint64_t> km_tab_off, km_flt_off;
+    Dev<int32_t> km_cutoff; Dev<KmerTile> km_tiles;
+    // what the last fsv_assemble_batch with kmer_table = 1 left for the follow-up stages: per set its verdict (peak_hom is hifiasm's hom_cov),
+    // and its segment [km_last_flt_off[s], km_last_flt_off[s + 1]) of the filter list on the device (km_last_flt, unordered inside a set)
+    std::vector<fsv_kmer_set> km_last; std::vector<uint64_t> km_last_flt_off; const unsigned long long *km_last_flt = nullptr; double km_ms = 0; bool km_valid = false;
     std::vector<uint32_t> h_store;   // the corrected reads of the sets whose layout compares bases (kept between calls: no 96 MB zero-fill a step)
     int occ_sb = 0, occ_fr[3] = {0, 0, 0}, occ_wide = 0;   // blocks per CU of the persistent K6 kernels (hipOccupancyMaxActiveBlocksPerMultiprocessor: asked once)
     ChainArgs last_chain;   // arguments of the last k_chain launch (the final pass re-chains a few pairs with another bandwidth)
@@ -99,7 +107,7 @@ struct AsmWs {
                        site_cursor, redo, site_lists, read_dirty, cov3, lb, sr_store, brel_off, tasks2, res2, paths2, idx2, bc_idx, bc_rec, bc_win, left_list, fix_list,
                        tasks3, res3, src3, bnd_flag, bnd_list, bnd_patch, bnd_bytes, changed, pair_read, wide_list, cols, tmp, gwin_off, gwin_read, sk_ends, sk_low, sk_high,
                        hits, hits_packed, set_hits, ovl_prev, exact_flag, inexact_list, upair_base, upair_tab, upair_tab_sw, ovl_c, gwin_tab, cwin, cwin_len, warn, thr_tab,
-                       pieces, contig_out, new_len, unpack_off);
+                       pieces, contig_out, new_len, unpack_off, km_keys, km_flt, km_flt_all, km_cnt, km_hist, km_cursor, km_err, km_tab_off, km_flt_off, km_cutoff, km_tiles);
     }
 };
 
@@ -184,6 +192,11 @@ struct Round {
     const fsv_asm_params &P;
     Batch B;
     const uint8_t *set_flags = nullptr;
+    // kmer_table = 1: the caller's sets whose k-mer histogram has no peak (empty: none).  Every read of such a set is a set of its own in B
+    // -- no pair, so no overlap stage sees it and no consensus changes it -- and caller_set maps B's sets back to the caller's
+    std::vector<uint8_t> low_cov;
+    std::vector<uint32_t> caller_set;
+    bool is_low(uint32_t s) const { return !low_cov.empty() && low_cov[caller_set[s]]; }
     const uint32_t *store = nullptr; std::vector<int32_t> len; Geometry G;   // the reads as they are now: the caller's in round 0, then the store the last round repacked
     std::vector<uint32_t> mz_fixed;  // minimizer slots: fixed for the whole call
     bool wide_bands = false;         // the error model allows thresholds above hifiasm's 31: wide-band K5 / K6 / rescue
@@ -383,6 +396,7 @@ extern "C" void fsv_asm_default_params(fsv_asm_params *p)
     p->bw_ec = 20; p->bw_final = 0; p->min_contig_reads = 4;
     p->win_rate_pm = 40; p->k_cap = FSV_K_MAX; p->accept_err_pm = 30; p->bw_rechain = 1; p->w_later = 0; p->partition = 1; p->second_round = 1; p->ins_dag = 1;
     p->min_anchors_final = 1; p->min_ovlp_final = 1; p->graph_layout = 1; p->junction_cigars = 1;
+    p->kmer_table = 0;
 }
 
 extern "C" void fsv_asm_ont_params(fsv_asm_params *p)
@@ -633,9 +647,16 @@ static int prepare_batch(fsv_ctx *ctx, AsmWs &W, const fsv_readsets *sets, Round
 {
     // (set_start spans [0, n_reads] and is monotone: fsv_assemble_batch_impl has checked)
     const fsv_asm_params &P = R.P; Batch &B = R.B;
-    B.n_reads = sets->n_reads; B.n_sets = sets->n_sets;
+    B.n_reads = sets->n_reads;
     R.set_flags = sets->set_flags;   // (FSV_SET_UNPHASED only picks the layout: the haplotype partition runs for every read of every set, as in hifiasm)
-    B.set_start.assign(sets->set_start, sets->set_start + B.n_sets + 1);
+    B.set_start.clear(); R.caller_set.clear();
+    for (uint32_t s = 0; s < sets->n_sets; s++) {
+        const bool low = !R.low_cov.empty() && R.low_cov[s];
+        for (uint32_t r = sets->set_start[s]; r < sets->set_start[s + 1]; r++) if (low || r == sets->set_start[s]) { B.set_start.push_back(r); R.caller_set.push_back(s); }
+        if (sets->set_start[s + 1] == sets->set_start[s]) { B.set_start.push_back(sets->set_start[s]); R.caller_set.push_back(s); }
+    }
+    B.n_sets = (uint32_t)R.caller_set.size();
+    B.set_start.push_back(B.n_reads);
     B.read_set.resize(B.n_reads); B.pair_base.resize(B.n_sets + 1); B.upair_base.resize(B.n_sets + 1);
     uint64_t np = 0;
     for (uint32_t s = 0; s < B.n_sets; s++) {
@@ -1068,8 +1089,9 @@ static int layout_sets(fsv_ctx *ctx, AsmWs &W, const Round &R, Final &F)
         for (uint32_t s = next.fetch_add(1); s < B.n_sets && rc_work.load() == FSV_OK; s = next.fetch_add(1)) {
             const uint32_t r0 = B.set_start[s], ns = B.set_start[s + 1] - r0;
             if (ns == 0) continue;
+            if (R.is_low(s)) { lay[s].fallback = true; continue; }   // no contig, whatever min_contig_reads is
             const uint32_t nh_s = hit_first[s + 1] - hit_first[s];
-            const bool unphased = set_flags && (set_flags[s] & FSV_SET_UNPHASED);
+            const bool unphased = set_flags && (set_flags[R.caller_set[s]] & FSV_SET_UNPHASED);
             if (P.graph_layout && !unphased) {
                 // the layout as hifiasm makes it (layout.h)
                 fsv_layout::ReadBases rb; rb.words = any_inexact ? h_store.data() : nullptr; rb.word_off = G.word_off.data() + r0; rb.len = len.data() + r0;
@@ -1120,17 +1142,18 @@ static int emit_contigs(fsv_ctx *ctx, AsmWs &W, const Round &R, Final &F, fsv_co
         const uint32_t r0 = B.set_start[s], ns = B.set_start[s + 1] - r0;
         int32_t st = 0;
         for (uint32_t r = r0; r < r0 + ns; r++) st |= (int32_t)(F.hwarn[r] & (FSV_W_MZ_TRUNC | FSV_W_ANCHOR_TRUNC | FSV_W_INS_EVENTS | FSV_W_WINDOW_KEPT | FSV_W_INTERNAL | FSV_W_SITES));
-        if (ns == 0) { out->set_status[s] = st; continue; }
+        const uint32_t cs = R.caller_set[s];      // (the status words were zeroed when the chunk began)
+        if (ns == 0) { out->set_status[cs] |= st; continue; }
         if (F.lay[s].fallback) st |= FSV_W_NO_LAYOUT;
         for (auto &c : F.lay[s].contigs) {
             uint64_t clen = 0;
             for (auto &pc : c) clen += pc.len;
             if (nc >= out->contig_cap || used + clen > out->seq_cap) { rc_out = fsv_fail(ctx, FSV_ECAP, "contig output buffers too small (use fsv_assemble_batch_bound)"); break; }
             for (auto &pc : c) { pieces.push_back(fsv_piece{r0 + pc.read, pc.rev, pc.len, 0u, used}); used += pc.len; }
-            out->set[nc] = s; out->n_reads[nc] = (uint32_t)c.size();
+            out->set[nc] = cs; out->n_reads[nc] = (uint32_t)c.size();
             out->off[++nc] = used;
         }
-        out->set_status[s] = st;
+        out->set_status[cs] |= st;
     }
     F.trace("layout");
     if (rc_out != FSV_OK) return rc_out;
@@ -1239,6 +1262,206 @@ static void fill_stats(AsmWs &W, const Round &R, const Final &F)
     }
 }
 
+// ---- the k-mer count table stage (k_kmer.h) --------------------------------------------------------------------------------------
+// HIP-event time of the stage's launches: a few spans on the stream (the host reads counts back between them), summed at the end
+struct KmerClock {
+    fsv_ctx *ctx; std::vector<hipEvent_t> ev;
+    explicit KmerClock(fsv_ctx *c) : ctx(c) {}
+    ~KmerClock() { for (auto e : ev) (void)hipEventDestroy(e); }
+    void mark() { hipEvent_t e; if (hipEventCreate(&e) == hipSuccess) { (void)hipEventRecord(e, ctx->stream); ev.push_back(e); } }
+    double ms() const { double t = 0; for (size_t i = 0; i + 1 < ev.size(); i += 2) { float x = 0; if (hipEventElapsedTime(&x, ev[i], ev[i + 1]) == hipSuccess) t += x; } return t; }
+};
+
+// The stage on the caller's read sets: sketch at (w, k, hpc) into W.mz, count per set, histogram, verdict (host: the histograms are 16 KB
+// a set), filter list.  out: n_sets records.  hist / flt_hash + flt_off: optional host copies (see fsv_kmer_table).  Leaves the filter
+// list in W.km_flt with the offsets in flt_off_out, and adds the launches' time to *ms.
+static int kmer_stage(fsv_ctx *ctx, AsmWs &W, const fsv_readsets *sets, int w, int k, int hpc, fsv_kmer_set *out, uint64_t *hist, uint64_t *flt_hash,
+                      uint64_t flt_cap, uint64_t *flt_off, std::vector<uint64_t> &flt_off_out, double *ms)
+{
+    const uint32_t n_reads = sets->n_reads, n_sets = sets->n_sets;
+    flt_off_out.assign((size_t)n_sets + 1, 0);
+    std::vector<uint64_t> entries(n_sets, 0);
+    std::vector<uint32_t> h_hist((size_t)n_sets * FSV_KMER_BINS, 0u);
+    std::vector<uint64_t> tab_off((size_t)n_sets + 1, 0);
+    std::vector<KmerTile> tiles;
+    KmerClock clock(ctx);
+    if (n_reads) {
+        Batch B;
+        B.n_reads = n_reads; B.n_sets = 1; B.set_start = {0u, n_reads};
+        std::vector<int32_t> len(sets->read_len, sets->read_len + n_reads);
+        for (uint32_t r = 0; r < n_reads; r++) if (len[r] < 1 || len[r] >= (1 << 24)) return fsv_fail(ctx, FSV_EUNSUP, "read length must be in [1, 2^24)");
+        Geometry G;
+        TRY(make_geometry(ctx, B, len, G, w));
+        for (uint32_t r = 0; r <= n_reads; r++) {
+            if (sets->word_off[r] >= (1ull << 32)) return fsv_fail(ctx, FSV_EUNSUP, "store larger than 2^32 words; split the batch");
+            G.word_off[r] = (uint32_t)sets->word_off[r];
+        }
+        std::vector<uint32_t> read_set(n_reads);
+        for (uint32_t s = 0; s < n_sets; s++) for (uint32_t r = sets->set_start[s]; r < sets->set_start[s + 1]; r++) read_set[r] = s;
+        TRY(upload(ctx, W.word_off, G.word_off));
+        TRY(upload(ctx, W.len, len));
+        TRY(upload(ctx, W.mz_off, G.mz_off));
+        TRY(upload(ctx, W.read_set, read_set));
+        TRY(ensure(ctx, W.warn, n_reads));
+        TRY(zero(ctx, W.warn, n_reads));
+        TRY(ensure(ctx, W.mz, G.mz_off[n_reads]));
+        TRY(ensure(ctx, W.mz_cnt, n_reads));
+        clock.mark();
+        TRY(launch_sketch(ctx, W, SketchJob{sets->store_dev, n_reads, G.word_off[n_reads], G.max_words, w, k, hpc, nullptr, w, false, nullptr}));
+        clock.mark();
+        // the tables are sized from what the sketch emitted
+        std::vector<uint32_t> cnt(n_reads);
+        TRY(download(ctx, cnt.data(), W.mz_cnt, n_reads));
+        FSV_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        for (uint32_t r = 0; r < n_reads; r++) entries[read_set[r]] += std::min<uint32_t>(cnt[r], G.mz_off[r + 1] - G.mz_off[r]);
+        for (uint32_t s = 0; s < n_sets; s++) {
+            const uint64_t slots = kmer_table_slots(entries[s]), tile = std::min<uint64_t>(slots, FSV_KMER_TILE);
+            tab_off[s + 1] = tab_off[s] + slots;
+            for (uint64_t f = 0; f < slots; f += tile) tiles.push_back(KmerTile{s, (uint32_t)tile, f});
+        }
+        if (tiles.size() >= (1ull << 31)) return fsv_fail(ctx, FSV_EUNSUP, "k-mer tables too large for one pass; split the batch");
+    }
+    const uint64_t total_slots = tab_off[n_sets];
+    TRY(ensure(ctx, W.km_err, 1));
+    TRY(zero(ctx, W.km_err, 1));
+    TRY(ensure(ctx, W.km_cursor, std::max(1u, n_sets)));
+    TRY(zero(ctx, W.km_cursor, std::max(1u, n_sets)));
+    TRY(upload(ctx, W.km_tab_off, tab_off));
+    uint32_t err = 0;
+    if (total_slots) {
+        TRY(ensure(ctx, W.km_keys, total_slots));
+        TRY(ensure(ctx, W.km_cnt, total_slots));
+        TRY(ensure(ctx, W.km_hist, h_hist.size()));
+        TRY(upload(ctx, W.km_tiles, tiles));
+        clock.mark();
+        FSV_HIP(ctx, hipMemsetAsync(W.km_keys.p, 0xff, total_slots * sizeof(unsigned long long), ctx->stream));   // every slot FSV_KMER_EMPTY
+        TRY(zero(ctx, W.km_cnt, total_slots));
+        TRY(zero(ctx, W.km_hist, h_hist.size()));
+        FSV_LAUNCH(ctx, ctx->stream, k_kmer_insert, dim3(n_reads), dim3(256), 0, W.mz.p, W.mz_off.p, W.mz_cnt.p, W.read_set.p, W.km_tab_off.p, W.km_keys.p, W.km_cnt.p,
+                   n_reads, W.km_err.p);
+        FSV_LAUNCH(ctx, ctx->stream, k_kmer_hist, dim3((uint32_t)tiles.size()), dim3(256), 0, W.km_tiles.p, W.km_tab_off.p, W.km_keys.p, W.km_cnt.p, W.km_hist.p);
+        clock.mark();
+        TRY(download(ctx, h_hist.data(), W.km_hist, h_hist.size()));
+        TRY(download(ctx, &err, W.km_err, 1));
+        FSV_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        if (err) return fsv_fail(ctx, FSV_EINTERNAL, "k-mer count table: a set's table ran full");
+    }
+    // the verdict per set, and the filter segments the histogram promises
+    std::vector<int32_t> cutoff(n_sets);
+    std::vector<int64_t> h64(FSV_KMER_BINS);
+    for (uint32_t s = 0; s < n_sets; s++) {
+        const uint32_t *h = h_hist.data() + (size_t)s * FSV_KMER_BINS;
+        fsv_kmer_set &o = out[s];
+        memset(&o, 0, sizeof(o));
+        for (int c = 0; c < FSV_KMER_BINS; c++) { h64[c] = h[c]; o.n_distinct += h[c]; if (hist) hist[(size_t)s * FSV_KMER_BINS + c] = h[c]; }
+        o.peak_hom = fsv_kmer_peaks_hd(h64.data(), FSV_KMER_BINS, FSV_KMER_START, &o.peak_het, &o.low_i, &o.max_i);
+        o.cutoff = cutoff[s] = fsv_kmer_cutoff(o.peak_hom);
+        o.n_entries = entries[s];
+        for (int c = 1; c < FSV_KMER_BINS; c++) if (c >= o.cutoff) o.n_filtered += h[c];
+        for (int c = 2; c <= FSV_KMER_BINS - 2; c++) o.n_indexed += (uint64_t)c * h[c];
+        flt_off_out[s + 1] = flt_off_out[s] + o.n_filtered;
+    }
+    const uint64_t n_flt = flt_off_out[n_sets];
+    if (n_flt) {
+        std::vector<uint32_t> cursor(n_sets);
+        TRY(ensure(ctx, W.km_flt, n_flt));
+        TRY(upload(ctx, W.km_cutoff, cutoff));
+        TRY(upload(ctx, W.km_flt_off, flt_off_out));
+        clock.mark();
+        FSV_LAUNCH(ctx, ctx->stream, k_kmer_filter, dim3((uint32_t)tiles.size()), dim3(256), 0, W.km_tiles.p, W.km_tab_off.p, W.km_keys.p, W.km_cnt.p, W.km_cutoff.p,
+                   W.km_flt_off.p, W.km_cursor.p, W.km_flt.p, W.km_err.p);
+        clock.mark();
+        TRY(download(ctx, cursor.data(), W.km_cursor, n_sets));
+        TRY(download(ctx, &err, W.km_err, 1));
+        FSV_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        for (uint32_t s = 0; s < n_sets; s++) if (cursor[s] != out[s].n_filtered) err |= FSV_KMER_E_FLT;
+        if (err) return fsv_fail(ctx, FSV_EINTERNAL, "k-mer count table: the filter pass and the histogram disagree");
+    } else {
+        FSV_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    if (ms) *ms += clock.ms();
+    if (flt_off) {
+        memcpy(flt_off, flt_off_out.data(), ((size_t)n_sets + 1) * sizeof(uint64_t));
+        if (n_flt > flt_cap) return fsv_fail(ctx, FSV_ECAP, "fsv_kmer_table: flt_hash too small");
+        if (n_flt) {
+            FSV_HIP(ctx, hipMemcpyAsync(flt_hash, W.km_flt.p, n_flt * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+            FSV_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        }
+        for (uint32_t s = 0; s < n_sets; s++) std::sort(flt_hash + flt_off[s], flt_hash + flt_off[s + 1]);
+    }
+    return FSV_OK;
+}
+
+// the (w, k) a sketch launch takes: fsv_sketch_reads with variant 0, fsv_kmer_table
+static int check_sketch_scheme(fsv_ctx *ctx, int w, int k)
+{
+    if (k < 1 || k > 63 || w < 1) return fsv_fail(ctx, FSV_EINVAL, "1 <= k <= 63, 1 <= w");
+    if (k & 1) { if (w > 255) return fsv_fail(ctx, FSV_EINVAL, "w <= 255 (position-parallel kernel: odd k)"); }
+    else if (w > 64) return fsv_fail(ctx, FSV_EINVAL, "w <= 64 (replay kernel: even k)");
+    return FSV_OK;
+}
+
+static int check_set_start(fsv_ctx *ctx, const fsv_readsets *sets)
+{
+    if (sets->n_sets == 0) return sets->n_reads == 0 ? FSV_OK : fsv_fail(ctx, FSV_EINVAL, "set_start must span [0, n_reads]");
+    if (sets->set_start[0] != 0 || sets->set_start[sets->n_sets] != sets->n_reads) return fsv_fail(ctx, FSV_EINVAL, "set_start must span [0, n_reads]");
+    for (uint32_t s = 0; s < sets->n_sets; s++) if (sets->set_start[s + 1] < sets->set_start[s]) return fsv_fail(ctx, FSV_EINVAL, "set_start not monotone");
+    return FSV_OK;
+}
+
+static int fsv_kmer_table_impl(fsv_ctx *ctx, const fsv_readsets *sets, int32_t w, int32_t k, int32_t hpc, fsv_kmer_set *out, uint64_t *hist,
+                               uint64_t *flt_hash, uint64_t flt_cap, uint64_t *flt_off)
+{
+    if (!ctx || !sets || !sets->store_dev || !sets->word_off || !sets->read_len || !sets->set_start || !out) return FSV_EINVAL;
+    if ((flt_hash == nullptr) != (flt_off == nullptr)) return fsv_fail(ctx, FSV_EINVAL, "fsv_kmer_table: flt_hash and flt_off go together");
+    TRY(check_sketch_scheme(ctx, w, k));
+    TRY(check_set_start(ctx, sets));
+    FSV_HIP(ctx, hipSetDevice(ctx->device));
+    AsmWs &W = *ws_get(ctx);
+    W.n_reads = 0; W.cur_store = nullptr;     // (the workspace's read tables are this call's now: nothing for fsv_asm_fetch_reads)
+    std::vector<uint64_t> off;
+    return kmer_stage(ctx, W, sets, w, k, hpc ? 1 : 0, out, hist, flt_hash, flt_cap, flt_off, off, nullptr);
+}
+
+static int fsv_asm_last_kmer_table_impl(const fsv_ctx *ctx, fsv_kmer_set *out, uint32_t n_sets, double *ms)
+{
+    if (!ctx || !ctx->asm_ws || (!out && n_sets)) return FSV_EINVAL;
+    const AsmWs &W = *(const AsmWs *)ctx->asm_ws;
+    if (!W.km_valid || W.km_last.size() != n_sets) return FSV_EINVAL;
+    if (n_sets) memcpy(out, W.km_last.data(), (size_t)n_sets * sizeof(fsv_kmer_set));
+    if (ms) *ms = W.km_ms;
+    return FSV_OK;
+}
+
+// kmer_table = 1: the stage on a chunk's raw reads at (w = 1, k, hpc) before round 0.  The verdicts and the filter list join what the
+// chunks before left on the context (fsv_assemble_batch_impl cleared it); low[s] = 1 for the sets without a peak.
+static int kmer_stage_of_chunk(fsv_ctx *ctx, AsmWs &W, const fsv_readsets *sets, const fsv_asm_params &P, std::vector<uint8_t> &low)
+{
+    std::vector<fsv_kmer_set> v(sets->n_sets);
+    std::vector<uint64_t> off;
+    TRY(kmer_stage(ctx, W, sets, 1, P.k, P.hpc ? 1 : 0, v.data(), nullptr, nullptr, 0, nullptr, off, &W.km_ms));
+    low.assign(sets->n_sets, 0);
+    bool any = false;
+    for (uint32_t s = 0; s < sets->n_sets; s++) if (v[s].peak_hom < 0) { low[s] = 1; any = true; }
+    if (!any) low.clear();
+    // the filter list of the chunks so far, back to back on the device
+    const uint64_t have = W.km_last_flt_off.back(), add = off.back();
+    if (add) {
+        if (W.km_flt_all.cap < (have + add) * sizeof(unsigned long long)) {
+            Dev<unsigned long long> bigger;
+            TRY(ensure(ctx, bigger, (have + add) * 2));
+            if (have) FSV_HIP(ctx, hipMemcpyAsync(bigger.p, W.km_flt_all.p, have * sizeof(unsigned long long), hipMemcpyDeviceToDevice, ctx->stream));
+            FSV_HIP(ctx, hipStreamSynchronize(ctx->stream));
+            W.km_flt_all.swap(bigger);
+        }
+        FSV_HIP(ctx, hipMemcpyAsync(W.km_flt_all.p + have, W.km_flt.p, add * sizeof(unsigned long long), hipMemcpyDeviceToDevice, ctx->stream));
+    }
+    for (uint32_t s = 0; s < sets->n_sets; s++) W.km_last_flt_off.push_back(have + off[s + 1]);
+    W.km_last.insert(W.km_last.end(), v.begin(), v.end());
+    W.km_last_flt = W.km_flt_all.p;
+    return FSV_OK;
+}
+
 static int assemble_chunk(fsv_ctx *ctx, const fsv_readsets *sets, const fsv_asm_params &P, fsv_contigs *out)
 {
     AsmWs &W = *ws_get(ctx);
@@ -1248,7 +1471,12 @@ static int assemble_chunk(fsv_ctx *ctx, const fsv_readsets *sets, const fsv_asm_
     out->n_contigs = 0;
     out->off[0] = 0;
     for (uint32_t s = 0; s < sets->n_sets; s++) out->set_status[s] = 0;
-    if (sets->n_reads == 0 || sets->n_sets == 0) return FSV_OK;
+    if (sets->n_sets == 0) return FSV_OK;
+    if (P.kmer_table) {
+        TRY(kmer_stage_of_chunk(ctx, W, sets, P, R.low_cov));
+        for (uint32_t s = 0; s < sets->n_sets; s++) if (!R.low_cov.empty() && R.low_cov[s]) out->set_status[s] = FSV_W_LOW_COV | FSV_W_NO_LAYOUT;
+    }
+    if (sets->n_reads == 0) return FSV_OK;
     TRY(prepare_batch(ctx, W, sets, R));
     for (R.round = 0; R.round < P.n_rounds; R.round++) {
         TRY(begin_round(ctx, W, R));
@@ -1276,13 +1504,16 @@ static int assemble_chunk(fsv_ctx *ctx, const fsv_readsets *sets, const fsv_asm_
 }
 
 // Work a set brings: its window-task bound (every read's windows against every other read) and its ordered pairs.
-static void set_cost(const fsv_readsets *sets, uint32_t s, uint64_t &tasks, uint64_t &pairs, uint64_t &bases)
+// kmer_bytes: what the k-mer count table stage would hold for the set -- a table slot (12 B) for at least twice its bases, the filter
+// list when every k-mer is filtered (8 B a base), its histogram.
+static void set_cost(const fsv_readsets *sets, uint32_t s, uint64_t &tasks, uint64_t &pairs, uint64_t &bases, uint64_t &kmer_bytes)
 {
     const uint64_t ns = sets->set_start[s + 1] - sets->set_start[s];
     uint64_t nw = 0; bases = 0;
     for (uint32_t r = sets->set_start[s]; r < sets->set_start[s + 1]; r++) { nw += ((uint64_t)sets->read_len[r] + FSV_WINDOW - 1) / FSV_WINDOW; bases += (uint64_t)sets->read_len[r]; }
     tasks = ns > 1 ? nw * (ns - 1) : 0;
     pairs = ns > 1 ? ns * (ns - 1) : 0;
+    kmer_bytes = kmer_table_slots(bases) * 12ull + bases * 8ull + FSV_KMER_BINS * 4ull;
 }
 
 static int check_asm_params(fsv_ctx *ctx, const fsv_asm_params &P)
@@ -1305,7 +1536,10 @@ static int fsv_assemble_batch_impl(fsv_ctx *ctx, const fsv_readsets *sets, const
     FSV_HIP(ctx, hipSetDevice(ctx->device));
     AsmWs &W = *ws_get(ctx);
     out->n_contigs = 0; out->off[0] = 0;
-    if (sets->n_reads == 0 || sets->n_sets == 0) { for (uint32_t s = 0; s < sets->n_sets; s++) out->set_status[s] = 0; memset(&W.stats, 0, sizeof(W.stats)); return FSV_OK; }
+    // what the k-mer count table stage leaves on the context belongs to this call from here on (its chunks add to it)
+    W.km_last.clear(); W.km_last_flt_off.assign(1, 0); W.km_last_flt = nullptr; W.km_ms = 0; W.km_valid = false;
+    // (without reads a kmer_table call still goes on: every set gets its verdict -- no k-mer, no peak)
+    if (sets->n_sets == 0 || (sets->n_reads == 0 && !P.kmer_table)) { for (uint32_t s = 0; s < sets->n_sets; s++) out->set_status[s] = 0; memset(&W.stats, 0, sizeof(W.stats)); return FSV_OK; }
     if (sets->set_start[0] != 0 || sets->set_start[sets->n_sets] != sets->n_reads) return fsv_fail(ctx, FSV_EINVAL, "set_start must span [0, n_reads]");
     for (uint32_t s = 0; s < sets->n_sets; s++) if (sets->set_start[s + 1] < sets->set_start[s]) return fsv_fail(ctx, FSV_EINVAL, "set_start not monotone");
     // Read sets are independent, so a batch that is too large for one pass -- 32-bit pair / task / offset indices, or a workspace
@@ -1327,19 +1561,21 @@ static int fsv_assemble_batch_impl(fsv_ctx *ctx, const fsv_readsets *sets, const
     if (env && atof(env) > 0) budget = atof(env) * 1e9;
     std::vector<uint32_t> cut{0};
     {
-        uint64_t tk = 0, pr = 0, bs = 0;
+        uint64_t tk = 0, pr = 0, bs = 0, km = 0;
         for (uint32_t s = 0; s < sets->n_sets; s++) {
-            uint64_t t1, p1, b1;
-            set_cost(sets, s, t1, p1, b1);
+            uint64_t t1, p1, b1, k1;
+            set_cost(sets, s, t1, p1, b1, k1);
+            if (!P.kmer_table) k1 = 0;
             if (t1 >= (1ull << 31) || p1 >= (1ull << 31) || b1 + b1 / 4 >= (1ull << 32)) return fsv_fail(ctx, FSV_EUNSUP, "a single read set exceeds the 2^31 window-task / pair bound");
             const bool over = tk + t1 >= (1ull << 31) || pr + p1 >= (1ull << 31) || (bs + b1) + (bs + b1) / 4 >= (1ull << 32) ||     /* minimizer slots: one per base + slack, 32-bit offsets */
-                              (double)(tk + t1) * (P.second_round ? 400.0 : 200.0) + (double)(pr + p1) * 200.0 + (double)(bs + b1) * (P.second_round ? 52.0 : 48.0) > budget;   /* second pass: the junction tasks' records, the patch slots */
-            if (over && s > cut.back()) { cut.push_back(s); tk = pr = bs = 0; }
-            tk += t1; pr += p1; bs += b1;
+                              (double)(tk + t1) * (P.second_round ? 400.0 : 200.0) + (double)(pr + p1) * 200.0 + (double)(bs + b1) * (P.second_round ? 52.0 : 48.0) +
+                              (double)(km + k1) > budget;   /* second pass: the junction tasks' records, the patch slots; kmer_table: the sets' tables */
+            if (over && s > cut.back()) { cut.push_back(s); tk = pr = bs = km = 0; }
+            tk += t1; pr += p1; bs += b1; km += k1;
         }
         cut.push_back(sets->n_sets);
     }
-    if (cut.size() == 2) return assemble_chunk(ctx, sets, P, out);
+    if (cut.size() == 2) { TRY(assemble_chunk(ctx, sets, P, out)); W.km_valid = P.kmer_table != 0; return FSV_OK; }
     fsv_asm_stats total; memset(&total, 0, sizeof(total));
     uint64_t used = 0; uint32_t nc = 0;
     std::vector<uint64_t> all_off{0};
@@ -1391,6 +1627,7 @@ static int fsv_assemble_batch_impl(fsv_ctx *ctx, const fsv_readsets *sets, const
     FSV_HIP(ctx, hipStreamSynchronize(ctx->stream));
     out->n_contigs = nc;
     W.stats = total;
+    W.km_valid = P.kmer_table != 0;
     W.n_reads = 0; W.cur_store = nullptr;        // fsv_asm_fetch_reads serves single-pass batches only
     ctx->last_contigs_dev = nc ? W.contig_all.p : nullptr;
     ctx->last_contig_off.assign(out->off, out->off + nc + 1);
@@ -1533,6 +1770,23 @@ extern "C" int fsv_sketch_reads(fsv_ctx *ctx, const fsv_readsets *sets, int32_t 
                                 uint64_t out_cap, uint64_t *out_off)
 {
     FSV_GUARD(ctx, fsv_sketch_reads_impl(ctx, sets, w, k, hpc, variant, out_mz, out_cap, out_off));
+}
+
+extern "C" int fsv_kmer_peaks(const int64_t *hist, int32_t n_cnt, int32_t start_cnt, int32_t *peak_het, int32_t *low_i, int32_t *max_i)
+{
+    if (!hist || !peak_het || !low_i || !max_i || n_cnt < 3 || start_cnt < 0 || start_cnt >= n_cnt) return FSV_EINVAL;
+    return fsv_kmer_peaks_hd(hist, n_cnt, start_cnt, peak_het, low_i, max_i);
+}
+
+extern "C" int fsv_kmer_table(fsv_ctx *ctx, const fsv_readsets *sets, int32_t w, int32_t k, int32_t hpc, fsv_kmer_set *out, uint64_t *hist,
+                              uint64_t *flt_hash, uint64_t flt_cap, uint64_t *flt_off)
+{
+    FSV_GUARD(ctx, fsv_kmer_table_impl(ctx, sets, w, k, hpc, out, hist, flt_hash, flt_cap, flt_off));
+}
+
+extern "C" int fsv_asm_last_kmer_table(const fsv_ctx *ctx, fsv_kmer_set *out, uint32_t n_sets, double *ms)
+{
+    FSV_GUARD((fsv_ctx *)nullptr, fsv_asm_last_kmer_table_impl(ctx, out, n_sets, ms));
 }
 
 extern "C" int fsv_asm_overlaps(fsv_ctx *ctx, const fsv_readsets *sets, const fsv_asm_params *params, int32_t pass, const uint32_t *rechain,

@@ -178,6 +178,9 @@ typedef struct fsv_asm_params {
                                * for every set that is not flagged FSV_SET_UNPHASED; 0: best-buddy chains (ONT profile, unphased sets) */
     int32_t junction_cigars;  /* 1 (default): the haplotype partition reads the ~50 columns on each side of a window junction off the re-aligned
                                * junction cigar, as hifiasm does (calculate_boundary_cigars, Correct.cpp:2310; markSNP_advance :5054); 0: window cigars */
+    int32_t kmer_table;       /* 0 (default in all three profiles): off.  1: hifiasm's k-mer count table per read set before round 0 (ha_ft_gen, htab.cpp:917;
+                               * see fsv_kmer_table) at (w = 1, k, hpc) -- a set whose count histogram has no coverage peak is left as hifiasm leaves
+                               * it: reads uncorrected, no contig, FSV_W_LOW_COV | FSV_W_NO_LAYOUT; every other set is assembled as with 0 */
 } fsv_asm_params;
 void fsv_asm_default_params(fsv_asm_params *p);
 /* ONT-profile reads (BASELINE configs[4]: ~10 % error): k = 15, w = 15 without homopolymer compression (a 30 kb read then has ~3 750 minimizers: below the 4 096 a list holds), chain indel budget 0.15 / 0.05,
@@ -238,6 +241,8 @@ typedef struct fsv_contigs {
 #define FSV_W_SITES       64  /* haplotype partition: more than 255 candidate sites in a window, 1 024 in a read (512 once sites beside another site are
                                  * dropped), or the site pool ran out;
                                  * that window's sites / that read's partition were skipped */
+#define FSV_W_LOW_COV    128  /* kmer_table = 1: the set's k-mer count histogram has no coverage peak (ha_analyze_count returns -1); hifiasm then
+                                 * filters every k-mer, finds no overlap and writes no contig, and so does this set (comes with FSV_W_NO_LAYOUT) */
 
 /* capacity needed for fsv_contigs.seq / contig count for these read sets */
 int fsv_assemble_batch_bound(const fsv_readsets *sets, uint64_t *seq_cap, uint32_t *contig_cap);
@@ -298,6 +303,29 @@ int fsv_asm_overlaps(fsv_ctx *ctx, const fsv_readsets *sets, const fsv_asm_param
  * (even k, or variant 1): FSV_EINVAL otherwise, and fsv_last_error names the limit that applied. */
 int fsv_sketch_reads(fsv_ctx *ctx, const fsv_readsets *sets, int32_t w, int32_t k, int32_t hpc, int32_t variant,
                      fsv_mz *out_mz, uint64_t out_cap, uint64_t *out_off);
+
+/* ---- k-mer count table of a read set (ha_ft_gen / ha_analyze_count, htab.cpp:917-950, hist.cpp:15-96) ----------
+ * Keys: the 64-bit hash of every entry the sketch emits for (w, k, hpc) -- with w = 1 every k-mer ha_sketch accepts, both strands
+ * counted together.  Count: occurrences over all reads of the set, saturating at 4095.  hist[c]: distinct keys with count c. */
+typedef struct fsv_kmer_set {           /* one read set */
+    int32_t  peak_hom, peak_het;        /* -1: none */
+    int32_t  cutoff, low_i, max_i;      /* cutoff: (int)(peak_hom x 5.0), at most 4094, -5 without a peak; max_i -1 when there is no peak */
+    int32_t  pad;
+    uint64_t n_entries, n_distinct;     /* sketch entries counted; distinct keys */
+    uint64_t n_filtered, n_indexed;     /* distinct keys with count >= cutoff (all of them without a peak); sum of c x hist[c], c = 2..4094 */
+} fsv_kmer_set;                         /* 56 bytes */
+/* pure host function, no GPU: ha_analyze_count over n_cnt bins (3 <= n_cnt, 0 <= start_cnt < n_cnt; hifiasm: 4096, 5).  Returns peak_hom, -1 when
+ * the histogram has no peak, FSV_EINVAL on a bad argument */
+int fsv_kmer_peaks(const int64_t *hist, int32_t n_cnt, int32_t start_cnt, int32_t *peak_het, int32_t *low_i, int32_t *max_i);
+/* the stage alone, on the caller's read sets (per-set, unlike fsv_sketch_reads); (w, k) as fsv_sketch_reads takes them with variant 0.
+ * out: n_sets records.
+ * hist: n_sets x 4096 uint64 or NULL.
+ * flt_hash / flt_off (n_sets + 1): every set's filtered hashes in ascending order, or both NULL; FSV_ECAP when flt_cap is too small. */
+int fsv_kmer_table(fsv_ctx *ctx, const fsv_readsets *sets, int32_t w, int32_t k, int32_t hpc,
+                   fsv_kmer_set *out, uint64_t *hist, uint64_t *flt_hash, uint64_t flt_cap, uint64_t *flt_off);
+/* verdicts of the last fsv_assemble_batch with kmer_table = 1 on this context, all chunks, in set order (n_sets: that call's; FSV_EINVAL
+ * otherwise, or when that call ran with kmer_table = 0); ms: the stage's summed kernel time */
+int fsv_asm_last_kmer_table(const fsv_ctx *ctx, fsv_kmer_set *out, uint32_t n_sets, double *ms);
 
 /* ---- aligner boundary ---------------------------------------------------------
  * Replaces `minimap2 -a -x asm5 --cs -r2k ref_chr.fa assemblies.fa | samtools sort` and the pysam read-back
