@@ -935,9 +935,7 @@ struct Final {
     bool any_inexact = false;                             // some set's layout compares bases: W.h_store holds its reads
     std::vector<SetLayout> lay;
     uint64_t used = 0;                                    // contig bases written
-    // FSV_TRACE: the host's view of the final pass, step by step (each line waits for the stream)
-    fsv_ctx *ctx; std::chrono::steady_clock::time_point tr0 = std::chrono::steady_clock::now();
-    void trace(const char *what) { if (getenv("FSV_TRACE")) { (void)hipStreamSynchronize(ctx->stream); auto t = std::chrono::steady_clock::now(); fprintf(stderr, "[fsv] final %-14s %.2f ms\n", what, std::chrono::duration<double, std::milli>(t - tr0).count()); tr0 = t; } }
+    Trace trace;                                          // FSV_TRACE: the final pass, step by step
 };
 
 // the final pass's geometry on the device; its counter row
@@ -1492,7 +1490,7 @@ static int assemble_chunk(fsv_ctx *ctx, const fsv_readsets *sets, const fsv_asm_
     }
     Span tf(ctx, W.kt, ST_FINAL);
     Final F;
-    F.ctx = ctx;
+    F.trace = Trace{ctx, "final"};
     TRY(final_overlaps(ctx, W, R, F));
     TRY(gather_hits(ctx, W, R, F));
     TRY(layout_sets(ctx, W, R, F));

@@ -2,6 +2,9 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <chrono>
+#include <cstdio>
+#include <cstdlib>
 #include <new>
 #include <stdexcept>
 #include <string>
@@ -132,6 +135,26 @@ template <class... Ts> int ensure_each(fsv_ctx *ctx, size_t n, Dev<Ts> &...b) { 
 // a kernel launch on a stream; every launch is checked on its own
 #define FSV_LAUNCH(ctx, stream, kern, grid, block, lds, ...) \
     do { hipLaunchKernelGGL(kern, grid, block, lds, stream, __VA_ARGS__); FSV_HIP(ctx, hipGetLastError()); } while (0)
+
+// ---- host clocks ----------------------------------------------------------------------
+// wall-clock milliseconds of a stretch of work on the context's stream: both ends wait for the stream
+struct Timer {
+    std::chrono::steady_clock::time_point t0; fsv_ctx *ctx;
+    explicit Timer(fsv_ctx *c) : ctx(c) { (void)hipStreamSynchronize(c->stream); t0 = std::chrono::steady_clock::now(); }
+    double stop() { (void)hipStreamSynchronize(ctx->stream); return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
+};
+// FSV_TRACE: the host's view of a pass, step by step, on stderr -- "[fsv] <who> <step> <ms since the last line>" (each line waits for the stream)
+struct Trace {
+    fsv_ctx *ctx = nullptr; const char *who = ""; std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
+    void operator()(const char *what)
+    {
+        if (!getenv("FSV_TRACE")) return;
+        (void)hipStreamSynchronize(ctx->stream);
+        const auto t = std::chrono::steady_clock::now();
+        fprintf(stderr, "[fsv] %s %-14s %.2f ms\n", who, what, std::chrono::duration<double, std::milli>(t - t0).count());
+        t0 = t;
+    }
+};
 
 // K5 with the task count left on the device (k5_bpm.hip): n_tasks sizes the grid, *n_dev is the count the kernel uses
 // k_cap: the largest threshold of the batch's error model (31 = hifiasm's; above it every window goes through the wide-band kernel)

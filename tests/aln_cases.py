@@ -160,6 +160,19 @@ def n_window_cases():
     return out
 
 
+def cigar_head_cases():
+    """nine contigs of one 6 kb reference, contig n (1 ... 9) without the n single bases at 3000, 3010, ..., 3000 + 10 (n - 1).  No
+    19-mer fits between two deletions, so they share one DP event of 2n - 1 ... 2n + 1 runs (the padding M at either end): in one
+    batch the events fall on both sides of the 8 runs per event that the host reads back in its one strided copy"""
+    ref = rnd(np.random.default_rng(11), 6000)
+    out = []
+    for n in range(1, 10):
+        cut = [3000 + 10 * i for i in range(n)]
+        hap = b"".join(ref[a + 1:b] for a, b in zip([-1] + cut, cut + [len(ref)]))
+        out.append(Case("single-DEL-x%d" % n, ref, hap, [], n_rec=1))
+    return out
+
+
 def check_case(case, recs):
     """recs: the records of the contig (dicts with ref_start, rev, cigar): every planted SV within 1 bp with its exact length,
     nothing else; the expected number of records and their strands"""

@@ -202,6 +202,20 @@ def test_reference_windows_with_n_runs(ctx):
         _same_records(got, O.align_contig_multi(c.hap, c.ref), c.name)
 
 
+def test_cigar_read_back_on_both_sides_of_the_head(ctx):
+    """The host reads the first 8 CIGAR runs of every DP event back in one strided copy and fetches longer events one by one.
+    aln_cases.cigar_head_cases: events of 1 ... 19 runs in one batch, next to the tandem array whose box is closed from its
+    corners: every status 0, records bit-identical to the oracle's"""
+    from tests import aln_cases as A
+    cases = A.cigar_head_cases() + [c for c in A.other_cases() if c.name == "array-INS"]
+    assert len(cases) == 10
+    rec, cigar, status = ctx.align_batch([c.hap for c in cases], list(range(len(cases))), [c.ref for c in cases])
+    assert (status == 0).all(), list(status)
+    by = _records_by_contig(rec, cigar, len(cases))
+    for c, got in zip(cases, by):
+        _same_records(got, O.align_contig_multi(c.hap, c.ref), c.name)
+
+
 def test_mixed_seed_windows_in_one_batch(ctx):
     """One fsv_align_batch call whose reference groups are about 30 kb, 150 kb and 400 kb long: k_sketch_fast runs with a window
     per sequence (w = 19, 51 and 134 in one launch; the 400 kb sequences take hundreds of tiles), contigs on both strands, planted

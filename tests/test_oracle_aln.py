@@ -157,6 +157,17 @@ def test_split_records_beyond_max_gap():
         assert len(calls) == 1 and calls[0][1] == want[0] and abs(calls[0][2] - want[1]) <= 2 and abs(calls[0][3] - want[2]) <= 2
 
 
+def test_single_base_deletions_ten_apart_share_one_event():
+    """n = 1 ... 9 single-base deletions ten bases apart: one record of 2n + 1 runs, exactly n deletions of length 1 (at n = 10 the
+    DP prefers one long gap).  The GPU test aligns all nine in one batch: DP events of up to and of more than 8 runs"""
+    from tests import aln_cases as A
+    for n, case in enumerate(A.cigar_head_cases(), 1):
+        recs = O.align_contig_multi(case.hap, case.ref)
+        assert len(case.hap) == len(case.ref) - n and len(recs) == 1, case.name
+        cg = recs[0]["cigar"]
+        assert len(cg) == 2 * n + 1 and [x for x in cg if x[0] != 0] == [(2, 1)] * n, (case.name, cg)
+
+
 def test_reference_windows_with_n_runs():
     """an N of the reference window pairs with nothing and costs 1 (minimap2's sc_ambi), N runs do not
     seed -- the alignment runs through runs of 1 .. 1 500 N as 'M', no SV is called there (nor where the contig has poly-A against
