@@ -32,7 +32,7 @@ assert OVL_DTYPE.itemsize == 56
 class AsmParams(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("k", "w", "hpc", "n_rounds", "min_ovlp", "min_anchors", "lookback", "bw_ec", "bw_final",
                                          "min_contig_reads", "win_rate_pm", "k_cap", "accept_err_pm", "bw_rechain", "w_later", "partition", "second_round", "ins_dag",
-                                         "min_anchors_final", "min_ovlp_final", "graph_layout", "junction_cigars", "kmer_table")]
+                                         "min_anchors_final", "min_ovlp_final", "graph_layout", "junction_cigars", "kmer_table", "partial_charge")]
 
 
 class ReadSets(C.Structure):
@@ -51,6 +51,14 @@ KMER_BINS = 4096
 KMER_SET_DTYPE = np.dtype([("peak_hom", "<i4"), ("peak_het", "<i4"), ("cutoff", "<i4"), ("low_i", "<i4"), ("max_i", "<i4"), ("pad", "<i4"),
                            ("n_entries", "<u8"), ("n_distinct", "<u8"), ("n_filtered", "<u8"), ("n_indexed", "<u8")])
 assert KMER_SET_DTYPE.itemsize == 56
+# fsv_wext: the result of one extension alignment (fsv_bpm_extensions)
+WEXT_DTYPE = np.dtype([("t_end", "<i4"), ("err", "<i4"), ("p_end", "<i4"), ("pad", "<i4")])
+assert WEXT_DTYPE.itemsize == 16
+
+
+class ChargeStats(C.Structure):
+    """fsv_charge_stats: counters of the partial-charge stage of the last assemble_batch with partial_charge = 1"""
+    _fields_ = [(n, C.c_uint64) for n in ("n_overlaps", "n_windows", "n_ext", "n_accepted", "n_flipped")] + [("ms", C.c_double)]
 
 
 class Contigs(C.Structure):
@@ -151,6 +159,9 @@ def load():
         "fsv_kmer_peaks": (C.c_int, [vp, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
         "fsv_kmer_table": (C.c_int, [vp, C.POINTER(ReadSets), C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, C.c_uint64, vp]),
         "fsv_asm_last_kmer_table": (C.c_int, [vp, vp, C.c_uint32, C.POINTER(C.c_double)]),
+        "fsv_bpm_extensions": (C.c_int, [vp, vp, C.c_size_t, vp, vp, C.c_uint32, C.c_int32, vp]),
+        "fsv_partial_charge": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64]),
+        "fsv_asm_last_charge": (C.c_int, [vp, C.POINTER(ChargeStats)]),
         "fsv_aln_default_params": (None, [C.POINTER(AlnParams)]),
         "fsv_align_batch": (C.c_int, [vp, vp, vp, C.c_uint32, vp, vp, vp, C.c_uint32, C.POINTER(AlnParams), C.POINTER(Alns)]),
         "fsv_aln_last_stats": (C.c_int, [vp, C.POINTER(AlnStats)]),
@@ -215,6 +226,12 @@ def kmer_peaks(hist, start_cnt=5):
     if hom < -1:
         raise FsvError(hom, "fsv_kmer_peaks")
     return hom, het.value, low.value, mx.value
+
+
+def partial_charge(n, al0, er0, al1, er1, terr):
+    """fsv_partial_charge (host only, no GPU): non_trim_error_rate's charge for an unmatched window of n bases that the extension from the
+    left covers al0 bases of with er0 errors and the one from the right al1 with er1 (al = 0: none) -> the new running total"""
+    return int(load().fsv_partial_charge(int(n), int(al0), int(er0), int(al1), int(er1), int(terr)))
 
 
 def path_ops(p) -> bytes:
@@ -309,6 +326,18 @@ class Context:
         paths = np.zeros(len(tasks), dtype=WPATH_DTYPE)
         self.check(self._lib.fsv_bpm_paths(self._h, _ptr(words), words.size, _ptr(tasks), len(tasks), _ptr(res), _ptr(paths)), "fsv_bpm_paths")
         return res, paths
+
+    def bpm_extensions(self, words, tasks, dirs, k_cap=31):
+        """the extension kernel of the partial charge on host tasks (fsv_bpm_extensions) -> WEXT_DTYPE rows; dirs[i] = 1 aligns both
+        strings reversed and answers in the reversed coordinates"""
+        tasks = np.ascontiguousarray(tasks, dtype=WTASK_DTYPE)
+        words = np.ascontiguousarray(words, dtype=np.uint32)
+        dirs = np.ascontiguousarray(dirs, dtype=np.uint8)
+        assert len(dirs) == len(tasks)
+        out = np.zeros(len(tasks), dtype=WEXT_DTYPE)
+        self.check(self._lib.fsv_bpm_extensions(self._h, _ptr(words), words.size, _ptr(tasks), _ptr(dirs), len(tasks), int(k_cap), _ptr(out)),
+                   "fsv_bpm_extensions")
+        return out
 
     def bpm_windows_dev(self, store_ptr, tasks_ptr, n_tasks, res_ptr):
         self.check(self._lib.fsv_bpm_windows_dev(self._h, C.c_void_p(store_ptr), C.c_void_p(tasks_ptr), n_tasks, C.c_void_p(res_ptr)),
@@ -429,6 +458,13 @@ class Context:
         ms = C.c_double(0.0)
         self.check(self._lib.fsv_asm_last_kmer_table(self._h, _ptr(out), int(n_sets), C.byref(ms)), "fsv_asm_last_kmer_table")
         return out[:n_sets], ms.value
+
+    def last_charge(self):
+        """fsv_asm_last_charge: counters of the last assemble_batch with partial_charge = 1 (all rounds and chunks) -> dict;
+        FsvError(EINVAL) when that call ran with partial_charge = 0"""
+        st = ChargeStats()
+        self.check(self._lib.fsv_asm_last_charge(self._h, C.byref(st)), "fsv_asm_last_charge")
+        return {n: getattr(st, n) for n, _ in ChargeStats._fields_}
 
     def asm_stats(self):
         st = AsmStats()

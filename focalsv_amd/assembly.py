@@ -112,10 +112,14 @@ def assemble_sets(ctx: _lib.Context, sets, logger=None, budget_bytes: Optional[i
 
 
 def assembly(out_dir: str, cpu: int = 10, threads: int = 8, data_type: int = 0, logger=None, ctx: Optional[_lib.Context] = None,
-             device: int = 0, skip_existing: bool = True, kmer_table: bool = False) -> Dict[str, int]:
+             device: int = 0, skip_existing: bool = True, kmer_table: bool = False, partial_charge: bool = False) -> Dict[str, int]:
     """3_assembly.py:28-41.  cpu/threads are accepted for CLI compatibility (the GPU batch replaces both).
     kmer_table: run hifiasm's k-mer count table per read set first (fsv_asm_params.kmer_table): a set whose count histogram has no
-    coverage peak is left as hifiasm leaves it -- no contig, status bit 128 -- instead of being assembled"""
+    coverage peak is left as hifiasm leaves it -- no contig, status bit 128 -- instead of being assembled
+    partial_charge: hifiasm's non_trim_error_rate (fsv_asm_params.partial_charge): an unmatched window beside a matched one costs an overlap
+    what two extension alignments leave uncovered, not its whole length; HiFi read sets only (the wide-band profiles refuse it)"""
+    if partial_charge and data_type != 0:
+        raise ValueError("partial_charge applies to HiFi read sets (data_type 0) only: the CLR / ONT profiles use thresholds above 31")
     logger = logger or setup_logging("3_ASSEMBLY", out_dir)
     regions_dir = os.path.join(out_dir, "regions")
     fas = find_read_sets(regions_dir, data_type)
@@ -167,8 +171,9 @@ def assembly(out_dir: str, cpu: int = 10, threads: int = 8, data_type: int = 0, 
         try:
             params = ctx.default_asm_params()
             params.kmer_table = int(bool(kmer_table))
+            params.partial_charge = int(bool(partial_charge))
             per_set = assemble_sets(ctx, sets, logger, set_flags=[_lib.SET_UNPHASED if 'unphased' in os.path.basename(f) else 0 for f in fas],
-                                    params=params if kmer_table else None)
+                                    params=params if kmer_table or partial_charge else None)
         finally:
             if own:
                 ctx.close()

@@ -84,6 +84,12 @@ struct AsmWs {
     // filter list of the last stage and -- for a batch of several chunks -- of all its chunks, in set order
     Dev<unsigned long long> km_keys, km_flt, km_flt_all; Dev<uint32_t> km_cnt, km_hist, km_cursor, km_err; Dev<uint64_t> km_tab_off, km_flt_off;
     Dev<int32_t> km_cutoff; Dev<KmerTile> km_tiles;
+    // partial_charge = 1 (charge_stage): two extension tasks and results per window task at fixed slots, the slots in use, the overlaps
+    // waiting for their verdict, the two list lengths, the stage's counters (fsv_charge_stats' five, summed over the chunk's rounds)
+    Dev<fsv_wtask> ext_tasks; Dev<fsv_wext> ext_res; Dev<uint32_t> ext_list, charge_list, charge_n; Dev<unsigned long long> charge_ct;
+    std::vector<hipEvent_t> charge_ev;   // start / end of every charge_stage of the chunk, resolved when the chunk ends
+    fsv_charge_stats charge_last{};      // the last fsv_assemble_batch's, all chunks
+    bool charge_valid = false;
     // what the last fsv_assemble_batch with kmer_table = 1 left for the follow-up stages: per set its verdict (peak_hom is hifiasm's hom_cov),
     // and its segment [km_last_flt_off[s], km_last_flt_off[s + 1]) of the filter list on the device (km_last_flt, unordered inside a set)
     std::vector<fsv_kmer_set> km_last; std::vector<uint64_t> km_last_flt_off; const unsigned long long *km_last_flt = nullptr; double km_ms = 0; bool km_valid = false;
@@ -107,7 +113,8 @@ struct AsmWs {
                        site_cursor, redo, site_lists, read_dirty, cov3, lb, sr_store, brel_off, tasks2, res2, paths2, idx2, bc_idx, bc_rec, bc_win, left_list, fix_list,
                        tasks3, res3, src3, bnd_flag, bnd_list, bnd_patch, bnd_bytes, changed, pair_read, wide_list, cols, tmp, gwin_off, gwin_read, sk_ends, sk_low, sk_high,
                        hits, hits_packed, set_hits, ovl_prev, exact_flag, inexact_list, upair_base, upair_tab, upair_tab_sw, ovl_c, gwin_tab, cwin, cwin_len, warn, thr_tab,
-                       pieces, contig_out, new_len, unpack_off, km_keys, km_flt, km_flt_all, km_cnt, km_hist, km_cursor, km_err, km_tab_off, km_flt_off, km_cutoff, km_tiles);
+                       pieces, contig_out, new_len, unpack_off, km_keys, km_flt, km_flt_all, km_cnt, km_hist, km_cursor, km_err, km_tab_off, km_flt_off, km_cutoff, km_tiles,
+                       ext_tasks, ext_res, ext_list, charge_list, charge_n, charge_ct);
     }
 };
 
@@ -116,6 +123,7 @@ void ws_free(fsv_ctx *ctx)
     AsmWs *w = (AsmWs *)ctx->asm_ws;
     if (!w) return;
     if (w->h_pin) (void)hipHostFree(w->h_pin);
+    for (auto e : w->charge_ev) (void)hipEventDestroy(e);
     delete w;
     ctx->asm_ws = nullptr;
 }
@@ -397,6 +405,7 @@ extern "C" void fsv_asm_default_params(fsv_asm_params *p)
     p->win_rate_pm = 40; p->k_cap = FSV_K_MAX; p->accept_err_pm = 30; p->bw_rechain = 1; p->w_later = 0; p->partition = 1; p->second_round = 1; p->ins_dag = 1;
     p->min_anchors_final = 1; p->min_ovlp_final = 1; p->graph_layout = 1; p->junction_cigars = 1;
     p->kmer_table = 0;
+    p->partial_charge = 0;
 }
 
 extern "C" void fsv_asm_ont_params(fsv_asm_params *p)
@@ -630,6 +639,57 @@ static int fsv_bpm_paths_impl(fsv_ctx *ctx, const uint32_t *store, size_t store_
     return FSV_OK;
 }
 
+// the extension kernel over a task list: the launch fsv_assemble_batch (charge_stage) and fsv_bpm_extensions share.  A persistent grid
+// striding through the list; bound sizes it, *n_dev (when given) is the count.  list: the slots to run (null: slot i = task i).
+static int launch_bpm_ext(fsv_ctx *ctx, const uint32_t *store, const fsv_wtask *tasks, const uint32_t *list, const uint32_t *n_dev, uint32_t bound, int k_cap,
+                          fsv_wext *out, unsigned long long *n_run)
+{
+    if (!bound) return FSV_OK;
+    const uint32_t grid = std::min<uint32_t>(fsv_grid_for(bound, 64), 8u * (uint32_t)std::max(1, ctx->n_cu));
+    FSV_LAUNCH(ctx, ctx->stream, k_bpm_ext, dim3(grid), dim3(64), 0, store, tasks, list, n_dev, bound, k_cap, out, n_run);
+    return FSV_OK;
+}
+
+// the extension kernel on caller-supplied tasks, through launch_bpm_ext as charge_stage drives it (here: every slot holds a task)
+static int fsv_bpm_extensions_impl(fsv_ctx *ctx, const uint32_t *store, size_t store_words, const fsv_wtask *tasks, const uint8_t *dir, uint32_t n_tasks,
+                                   int32_t k_cap, fsv_wext *out)
+{
+    if (!ctx || !store || (n_tasks && (!tasks || !dir || !out))) return FSV_EINVAL;
+    if (k_cap < 1 || k_cap > FSV_K_WIDE) return fsv_fail(ctx, FSV_EINVAL, "k_cap must be in [1, 95]");
+    if (n_tasks == 0) return FSV_OK;
+    std::vector<fsv_wtask> t(tasks, tasks + n_tasks);
+    for (uint32_t i = 0; i < n_tasks; i++) {
+        fsv_wtask &x = t[i];
+        if (x.k > FSV_K_MAX || x.x_len == 0 || x.x_len > FSV_WINDOW || dir[i] > 1) return fsv_fail(ctx, FSV_EINVAL, "extension task: k <= 31 (FSV_K_MAX), 1 <= x_len <= 375, dir 0 or 1");
+        // every base the kernel may touch lies inside the caller's store
+        if (x.x_start < 0 || x.y_len < 0 || (uint64_t)x.x_word + ((uint64_t)x.x_start + x.x_len + 15) / 16 > store_words ||
+            (uint64_t)x.y_word + ((uint64_t)x.y_len + 15) / 16 > store_words)
+            return fsv_fail(ctx, FSV_EINVAL, "extension task reaches outside the store");
+        x.ovl = i; x.win = dir[i];
+    }
+    FSV_HIP(ctx, hipSetDevice(ctx->device));
+    AsmWs &W = *ws_get(ctx);
+    Dev<uint32_t> d_store;
+    TRY(ensure(ctx, d_store, store_words + 16));
+    TRY(zero(ctx, d_store, store_words + 16));
+    FSV_HIP(ctx, hipMemcpyAsync(d_store.p, store, store_words * 4, hipMemcpyHostToDevice, ctx->stream));
+    TRY(upload(ctx, W.ext_tasks, t));
+    TRY(ensure(ctx, W.ext_res, n_tasks));
+    TRY(launch_bpm_ext(ctx, d_store.p, W.ext_tasks.p, nullptr, nullptr, n_tasks, k_cap, W.ext_res.p, nullptr));
+    TRY(download(ctx, out, W.ext_res, n_tasks));
+    FSV_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return FSV_OK;
+}
+
+static int fsv_asm_last_charge_impl(const fsv_ctx *ctx, fsv_charge_stats *out)
+{
+    if (!ctx || !out || !ctx->asm_ws) return FSV_EINVAL;
+    const AsmWs &W = *(const AsmWs *)ctx->asm_ws;
+    if (!W.charge_valid) return FSV_EINVAL;
+    *out = W.charge_last;
+    return FSV_OK;
+}
+
 extern "C" int fsv_asm_last_stats(const fsv_ctx *ctx, fsv_asm_stats *out)
 {
     if (!ctx || !out || !ctx->asm_ws) return FSV_EINVAL;
@@ -735,6 +795,30 @@ static int begin_round(fsv_ctx *ctx, AsmWs &W, Round &R)
     return FSV_OK;
 }
 
+// partial_charge = 1, after K6: the final verdict on every overlap the rescue kernels let through provisionally (asm_kernels.h,
+// "partial charge").  Nothing here waits for the GPU; the counters are read when the chunk ends.
+static int charge_stage(fsv_ctx *ctx, AsmWs &W, const Round &R)
+{
+    const fsv_asm_params &P = R.P; const Batch &B = R.B;
+    const uint32_t ext_cap = 2u * R.task_cap;      // (task_cap < 2^31: begin_round)
+    TRY(ensure_each(ctx, ext_cap, W.ext_tasks, W.ext_res, W.ext_list));
+    TRY(ensure(ctx, W.charge_list, (size_t)B.n_pairs + 4));
+    TRY(ensure(ctx, W.charge_n, 2));
+    TRY(zero(ctx, W.charge_n, 2));
+    ChargeArgs A;
+    A.ovl = W.ovl.p; A.n_pairs = B.n_pairs; A.tasks = W.tasks.p; A.res = W.res.p; A.paths = W.paths.p; A.ovl_c = W.ovl_c.p;
+    A.ext_tasks = W.ext_tasks.p; A.ext_res = W.ext_res.p; A.ext_list = W.ext_list.p; A.n_ext = W.charge_n.p;
+    A.ovl_list = W.charge_list.p; A.n_ovl = W.charge_n.p + 1; A.stats = W.charge_ct.p;
+    A.k_cap = P.k_cap; A.accept_err_pm = P.accept_err_pm;
+    auto mark = [&]() -> int { hipEvent_t e; FSV_HIP(ctx, hipEventCreate(&e)); W.charge_ev.push_back(e); FSV_HIP(ctx, hipEventRecord(e, ctx->stream)); return FSV_OK; };
+    TRY(mark());
+    FSV_LAUNCH(ctx, ctx->stream, k_charge_tasks, dim3(fsv_grid_for(B.n_pairs, 64)), dim3(64), 0, A);
+    TRY(launch_bpm_ext(ctx, R.store, W.ext_tasks.p, W.ext_list.p, W.charge_n.p, ext_cap, P.k_cap, W.ext_res.p, W.charge_ct.p + CH_EXT));
+    FSV_LAUNCH(ctx, ctx->stream, k_charge_accept, dim3(fsv_grid_for(B.n_pairs, 64)), dim3(64), 0, A);
+    TRY(mark());
+    return FSV_OK;
+}
+
 // K5 on the window tasks, the rescue of unmatched windows and the verdict on every overlap, then K6 on the same tasks
 static int verify_stage(fsv_ctx *ctx, AsmWs &W, const Round &R)
 {
@@ -753,17 +837,26 @@ static int verify_stage(fsv_ctx *ctx, AsmWs &W, const Round &R)
         // the right-extension pass and the verdict in one kernel; an overlap with an unmatched window LEFT of a matched one is set
         // aside for the left-extension pass (k_left_rescue: it needs the matched window's path first), which then gives its verdict
         TRY(ensure(ctx, W.left_list, (size_t)B.n_pairs + 4));
-        FSV_LAUNCH(ctx, ctx->stream, k_rescue_accept<false>, dim3(fsv_grid_for(B.n_pairs, 64)), dim3(64), 0, R.store, W.ovl.p, B.n_pairs, W.tasks.p, W.res.p, cols,
-                   W.ovl_c.p, P.k_cap, P.accept_err_pm, W.left_list.p, ct + CT_LEFT);
         const uint32_t gridl = std::min<uint32_t>(std::max(1u, B.n_pairs), 8u * (uint32_t)ctx->n_cu);
-        FSV_LAUNCH(ctx, ctx->stream, k_left_rescue, dim3(gridl), dim3(64), 0, R.store, W.ovl.p, W.left_list.p, ct + CT_LEFT, W.tasks.p, W.res.p, W.paths.p,
-                   (uint64_t *)nullptr, W.ovl_c.p, P.k_cap, P.accept_err_pm);
+        if (!P.partial_charge) {
+            FSV_LAUNCH(ctx, ctx->stream, k_rescue_accept<false>, dim3(fsv_grid_for(B.n_pairs, 64)), dim3(64), 0, R.store, W.ovl.p, B.n_pairs, W.tasks.p, W.res.p, cols,
+                       W.ovl_c.p, P.k_cap, P.accept_err_pm, W.left_list.p, ct + CT_LEFT);
+            FSV_LAUNCH(ctx, ctx->stream, k_left_rescue<false>, dim3(gridl), dim3(64), 0, R.store, W.ovl.p, W.left_list.p, ct + CT_LEFT, W.tasks.p, W.res.p, W.paths.p,
+                       (uint64_t *)nullptr, W.ovl_c.p, P.k_cap, P.accept_err_pm);
+        } else {
+            // the same two kernels with the error-rate test deferred: charge_stage gives the verdict once K6 has run
+            FSV_LAUNCH(ctx, ctx->stream, (k_rescue_accept<false, true>), dim3(fsv_grid_for(B.n_pairs, 64)), dim3(64), 0, R.store, W.ovl.p, B.n_pairs, W.tasks.p, W.res.p,
+                       cols, W.ovl_c.p, P.k_cap, P.accept_err_pm, W.left_list.p, ct + CT_LEFT);
+            FSV_LAUNCH(ctx, ctx->stream, k_left_rescue<true>, dim3(gridl), dim3(64), 0, R.store, W.ovl.p, W.left_list.p, ct + CT_LEFT, W.tasks.p, W.res.p, W.paths.p,
+                       (uint64_t *)nullptr, W.ovl_c.p, P.k_cap, P.accept_err_pm);
+        }
     }
     W.kt.end(ctx);
     tv.stop();
     Span tp(ctx, W.kt, ST_PATH);
     TRY(path_stage(ctx, W, PathJob{R.store, W.tasks.p, W.res.p, W.paths.p, R.task_cap, R.ct + CT_TASKS, R.ct, PASS_WINDOWS, R.round, R.wide_bands, R.P.k_cap, false}));
     tp.stop();
+    if (P.partial_charge) TRY(charge_stage(ctx, W, R));
     return FSV_OK;
 }
 
@@ -1460,6 +1553,20 @@ static int kmer_stage_of_chunk(fsv_ctx *ctx, AsmWs &W, const fsv_readsets *sets,
     return FSV_OK;
 }
 
+// the chunk's charge counters and stage time join the call's (W.charge_last)
+static int charge_collect(fsv_ctx *ctx, AsmWs &W)
+{
+    unsigned long long h[8] = {0};
+    TRY(download(ctx, h, W.charge_ct, 8));
+    FSV_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    fsv_charge_stats &c = W.charge_last;
+    c.n_overlaps += h[CH_OVERLAPS]; c.n_windows += h[CH_WINDOWS]; c.n_ext += h[CH_EXT]; c.n_accepted += h[CH_ACCEPTED]; c.n_flipped += h[CH_FLIPPED];
+    for (size_t i = 0; i + 1 < W.charge_ev.size(); i += 2) { float ms = 0; if (hipEventElapsedTime(&ms, W.charge_ev[i], W.charge_ev[i + 1]) == hipSuccess) c.ms += ms; }
+    for (auto e : W.charge_ev) (void)hipEventDestroy(e);
+    W.charge_ev.clear();
+    return FSV_OK;
+}
+
 static int assemble_chunk(fsv_ctx *ctx, const fsv_readsets *sets, const fsv_asm_params &P, fsv_contigs *out)
 {
     AsmWs &W = *ws_get(ctx);
@@ -1476,6 +1583,7 @@ static int assemble_chunk(fsv_ctx *ctx, const fsv_readsets *sets, const fsv_asm_
     }
     if (sets->n_reads == 0) return FSV_OK;
     TRY(prepare_batch(ctx, W, sets, R));
+    if (P.partial_charge) { TRY(ensure(ctx, W.charge_ct, 8)); TRY(zero(ctx, W.charge_ct, 8)); }
     for (R.round = 0; R.round < P.n_rounds; R.round++) {
         TRY(begin_round(ctx, W, R));
         TRY(overlap_stage(ctx, W, R, false));
@@ -1498,6 +1606,7 @@ static int assemble_chunk(fsv_ctx *ctx, const fsv_readsets *sets, const fsv_asm_
     tf.stop();
     W.h_word_off = R.G.word_off; W.h_len = R.len; W.cur_store = R.store; W.n_reads = R.B.n_reads;
     fill_stats(W, R, F);
+    if (P.partial_charge) TRY(charge_collect(ctx, W));
     return FSV_OK;
 }
 
@@ -1521,6 +1630,8 @@ static int check_asm_params(fsv_ctx *ctx, const fsv_asm_params &P)
     if (P.k_cap < 1 || P.k_cap > FSV_K_WIDE || P.win_rate_pm < 1 || (int)(FSV_WINDOW * (P.win_rate_pm / 1000.0)) > P.k_cap || P.accept_err_pm < 0 || P.accept_err_pm > 1000 ||
         P.w_later < 0 || P.w_later > 64)
         return fsv_fail(ctx, FSV_EINVAL, "fsv_asm_params error model out of range (k_cap <= 95, 375 x win_rate_pm / 1000 <= k_cap)");
+    if (P.partial_charge && P.k_cap > FSV_K_MAX)
+        return fsv_fail(ctx, FSV_EINVAL, "partial_charge needs k_cap <= 31 (FSV_K_MAX): the charge is not restated for the wide-band profiles");
     return FSV_OK;
 }
 
@@ -1536,8 +1647,11 @@ static int fsv_assemble_batch_impl(fsv_ctx *ctx, const fsv_readsets *sets, const
     out->n_contigs = 0; out->off[0] = 0;
     // what the k-mer count table stage leaves on the context belongs to this call from here on (its chunks add to it)
     W.km_last.clear(); W.km_last_flt_off.assign(1, 0); W.km_last_flt = nullptr; W.km_ms = 0; W.km_valid = false;
+    W.charge_last = fsv_charge_stats{}; W.charge_valid = false;
+    for (auto e : W.charge_ev) (void)hipEventDestroy(e);     // (left by a call that failed half-way)
+    W.charge_ev.clear();
     // (without reads a kmer_table call still goes on: every set gets its verdict -- no k-mer, no peak)
-    if (sets->n_sets == 0 || (sets->n_reads == 0 && !P.kmer_table)) { for (uint32_t s = 0; s < sets->n_sets; s++) out->set_status[s] = 0; memset(&W.stats, 0, sizeof(W.stats)); return FSV_OK; }
+    if (sets->n_sets == 0 || (sets->n_reads == 0 && !P.kmer_table)) { for (uint32_t s = 0; s < sets->n_sets; s++) out->set_status[s] = 0; memset(&W.stats, 0, sizeof(W.stats)); W.charge_valid = P.partial_charge != 0; return FSV_OK; }
     if (sets->set_start[0] != 0 || sets->set_start[sets->n_sets] != sets->n_reads) return fsv_fail(ctx, FSV_EINVAL, "set_start must span [0, n_reads]");
     for (uint32_t s = 0; s < sets->n_sets; s++) if (sets->set_start[s + 1] < sets->set_start[s]) return fsv_fail(ctx, FSV_EINVAL, "set_start not monotone");
     // Read sets are independent, so a batch that is too large for one pass -- 32-bit pair / task / offset indices, or a workspace
@@ -1567,13 +1681,13 @@ static int fsv_assemble_batch_impl(fsv_ctx *ctx, const fsv_readsets *sets, const
             if (t1 >= (1ull << 31) || p1 >= (1ull << 31) || b1 + b1 / 4 >= (1ull << 32)) return fsv_fail(ctx, FSV_EUNSUP, "a single read set exceeds the 2^31 window-task / pair bound");
             const bool over = tk + t1 >= (1ull << 31) || pr + p1 >= (1ull << 31) || (bs + b1) + (bs + b1) / 4 >= (1ull << 32) ||     /* minimizer slots: one per base + slack, 32-bit offsets */
                               (double)(tk + t1) * (P.second_round ? 400.0 : 200.0) + (double)(pr + p1) * 200.0 + (double)(bs + b1) * (P.second_round ? 52.0 : 48.0) +
-                              (double)(km + k1) > budget;   /* second pass: the junction tasks' records, the patch slots; kmer_table: the sets' tables */
+                              (double)(km + k1) + (P.partial_charge ? (double)(tk + t1) * 104.0 : 0.0) > budget;   /* second pass: the junction tasks' records, the patch slots; kmer_table: the sets' tables */
             if (over && s > cut.back()) { cut.push_back(s); tk = pr = bs = km = 0; }
             tk += t1; pr += p1; bs += b1; km += k1;
         }
         cut.push_back(sets->n_sets);
     }
-    if (cut.size() == 2) { TRY(assemble_chunk(ctx, sets, P, out)); W.km_valid = P.kmer_table != 0; return FSV_OK; }
+    if (cut.size() == 2) { TRY(assemble_chunk(ctx, sets, P, out)); W.km_valid = P.kmer_table != 0; W.charge_valid = P.partial_charge != 0; return FSV_OK; }
     fsv_asm_stats total; memset(&total, 0, sizeof(total));
     uint64_t used = 0; uint32_t nc = 0;
     std::vector<uint64_t> all_off{0};
@@ -1626,6 +1740,7 @@ static int fsv_assemble_batch_impl(fsv_ctx *ctx, const fsv_readsets *sets, const
     out->n_contigs = nc;
     W.stats = total;
     W.km_valid = P.kmer_table != 0;
+    W.charge_valid = P.partial_charge != 0;
     W.n_reads = 0; W.cur_store = nullptr;        // fsv_asm_fetch_reads serves single-pass batches only
     ctx->last_contigs_dev = nc ? W.contig_all.p : nullptr;
     ctx->last_contig_off.assign(out->off, out->off + nc + 1);
@@ -1792,4 +1907,20 @@ extern "C" int fsv_asm_overlaps(fsv_ctx *ctx, const fsv_readsets *sets, const fs
                                 uint32_t *n_tasks, uint32_t *overflow, uint32_t *warn)
 {
     FSV_GUARD(ctx, fsv_asm_overlaps_impl(ctx, sets, params, pass, rechain, n_rechain, ovl, ovl_cap, pair_base, tasks, task_cap, n_tasks, overflow, warn));
+}
+
+extern "C" int fsv_bpm_extensions(fsv_ctx *ctx, const uint32_t *store, size_t store_words, const fsv_wtask *tasks, const uint8_t *dir,
+                                  uint32_t n_tasks, int32_t k_cap, fsv_wext *out)
+{
+    FSV_GUARD(ctx, fsv_bpm_extensions_impl(ctx, store, store_words, tasks, dir, n_tasks, k_cap, out));
+}
+
+extern "C" int64_t fsv_partial_charge(int32_t n, int32_t al0, int32_t er0, int32_t al1, int32_t er1, int64_t terr)
+{
+    return (int64_t)fsv_partial_charge_hd(n, al0, er0, al1, er1, (long long)terr);
+}
+
+extern "C" int fsv_asm_last_charge(const fsv_ctx *ctx, fsv_charge_stats *out)
+{
+    FSV_GUARD((fsv_ctx *)nullptr, fsv_asm_last_charge_impl(ctx, out));
 }

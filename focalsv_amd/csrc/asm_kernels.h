@@ -725,7 +725,10 @@ __device__ __forceinline__ int double_thr(int pre, int x_len, int k_cap)
 }
 
 // WIDE: the batch's error model allows thresholds above 31 (k_cap up to 95): the re-runs go through the wide-band BPM
-template <bool WIDE>
+// DEFER (fsv_asm_params.partial_charge): the error-rate test is left to k_charge_tasks / k_charge_accept, which need the windows' paths
+// first -- an overlap that passes the 0.9 coverage filter gets is_match = 1 for K6's sake (k_path_fast gates on it) while its accepted
+// bit in ovl_c stays clear; nothing but K6 runs between this verdict and the final one
+template <bool WIDE, bool DEFER = false>
 __global__ __launch_bounds__(64) void k_rescue_accept(const uint32_t *__restrict__ store, fsv_ovl *__restrict__ ovl, uint32_t n_pairs,
                                                       fsv_wtask *__restrict__ tasks, fsv_wres *__restrict__ res,
                                                       unsigned long long *__restrict__ stat_cols, uint4 *__restrict__ ovl_c, int k_cap, int accept_err_pm,
@@ -789,9 +792,11 @@ __global__ __launch_bounds__(64) void k_rescue_accept(const uint32_t *__restrict
         for (int j = 0; j < o.n_win; j++) { const int e = R[j].err; terr += e >= 0 ? e : T[j].x_len; }
     }
     o.align_len = align; o.err_sum = (int32_t)terr;
-    o.is_match = ((long long)(o.x_e - o.x_s + 1) * 9 <= (long long)align * 10 && terr * 1000 <= tlen * accept_err_pm) ? 1 : 0;
+    // DEFER: the 0.9 filter alone, and the accepted bit of ovl_c stays clear until k_charge_tasks / k_charge_accept have spoken
+    const bool covered = (long long)(o.x_e - o.x_s + 1) * 9 <= (long long)align * 10;
+    o.is_match = (covered && (DEFER || terr * 1000 <= tlen * accept_err_pm)) ? 1 : 0;
     ovl[p] = o;
-    ovl_c[p] = make_uint4((uint32_t)o.x_s, (uint32_t)o.first_win, (uint32_t)o.n_win | (o.is_match ? 0x80000000u : 0u), 0u);
+    ovl_c[p] = make_uint4((uint32_t)o.x_s, (uint32_t)o.first_win, (uint32_t)o.n_win | (o.is_match && !DEFER ? 0x80000000u : 0u), 0u);
     if (cols) atomicAdd(stat_cols, cols);
 }
 
@@ -1152,6 +1157,8 @@ __global__ __launch_bounds__(64) void k_fix_boundary(const uint32_t *__restrict_
 // once (the next one needs its start).  Then the overlap is accepted or not, as k_rescue_accept does: a window whose path was
 // computed here counts with its distance after generate_cigar, as in hifiasm.  One block (one working lane) per listed overlap, a
 // persistent grid over the list; oracle/asm.c:align_overlaps (left_rescue) statement for statement.
+// DEFER: as in k_rescue_accept -- the 0.9 filter alone decides here, provisionally.
+template <bool DEFER = false>
 __global__ __launch_bounds__(64) void k_left_rescue(const uint32_t *__restrict__ store, fsv_ovl *__restrict__ ovl, const uint32_t *__restrict__ list,
                                                     const uint32_t *__restrict__ n_list_dev, fsv_wtask *__restrict__ tasks, fsv_wres *__restrict__ res,
                                                     fsv_wpath *__restrict__ paths, uint64_t *__restrict__ cols, uint4 *__restrict__ ovl_c, int k_cap, int accept_err_pm)
@@ -1215,9 +1222,143 @@ __global__ __launch_bounds__(64) void k_left_rescue(const uint32_t *__restrict__
             tlen += xl;
         }
         o.align_len = align; o.err_sum = (int32_t)terr;
-        o.is_match = ((long long)(o.x_e - o.x_s + 1) * 9 <= (long long)align * 10 && terr * 1000 <= tlen * accept_err_pm) ? 1 : 0;
+        const bool covered = (long long)(o.x_e - o.x_s + 1) * 9 <= (long long)align * 10;
+        o.is_match = (covered && (DEFER || terr * 1000 <= tlen * accept_err_pm)) ? 1 : 0;
         ovl[p] = o;
-        ovl_c[p] = make_uint4((uint32_t)o.x_s, (uint32_t)o.first_win, (uint32_t)o.n_win | (o.is_match ? 0x80000000u : 0u), 0u);
+        ovl_c[p] = make_uint4((uint32_t)o.x_s, (uint32_t)o.first_win, (uint32_t)o.n_win | (o.is_match && !DEFER ? 0x80000000u : 0u), 0u);
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ partial charge (opt-in)
+// non_trim_error_rate (Correct.cpp:725-845), for fsv_asm_params.partial_charge = 1; oracle/asm.c:align_overlaps with partial_charge
+// (the acceptance test and unmatched_charge) statement for statement.  The rescue kernels ran with DEFER: every overlap that passed the
+// 0.9 coverage filter carries is_match = 1 and K6 (path_stage, fix_boundary included) has left its matched windows' paths.  Now
+//   k_charge_tasks   one lane per overlap slot: the error sum over the matched windows' distances AFTER generate_cigar (the path headers),
+//                    as the reference has them when it sums up (Correct.cpp:2920-3003).  No unmatched window: the verdict, here.  Otherwise
+//                    two extension tasks per unmatched window -- from the left neighbour's exact end, to the right neighbour's exact start,
+//                    doubled threshold -- at the fixed slots 2 x window task + direction, and the overlap goes on the list;
+//   k_bpm_ext        one lane per extension task (bpm_ext_run, bpm_device.h);
+//   k_charge_accept  one lane per listed overlap: its windows in order with the running total (the float branch of the charge reads it),
+//                    then the verdict.
+// An overlap rejected in the end gets the path state of all its windows cleared, which is how k_path_fast leaves a rejected overlap's
+// windows on the default path: the consensus, partition and junction kernels that look at the path state alone see no difference.
+struct ChargeArgs {
+    fsv_ovl *ovl; uint32_t n_pairs;
+    const fsv_wtask *tasks; const fsv_wres *res; fsv_wpath *paths; uint4 *ovl_c;
+    fsv_wtask *ext_tasks;            // slot 2 x (window task) + direction; .win: the direction, .ovl: the window task
+    const fsv_wext *ext_res;         // the same slots
+    uint32_t *ext_list, *n_ext;      // the slots that hold a task, in no particular order (results sit at fixed slots)
+    uint32_t *ovl_list, *n_ovl;      // overlap slots waiting for k_charge_accept
+    unsigned long long *stats;       // fsv_charge_stats' five counters, in its order
+    int k_cap, accept_err_pm;
+};
+enum { CH_OVERLAPS = 0, CH_WINDOWS = 1, CH_EXT = 2, CH_ACCEPTED = 3, CH_FLIPPED = 4 };
+
+// a window counts as matched when K5 (or a rescue pass) aligned it and K6 left a path (a path too long for a record leaves the window
+// unused, as oracle/asm.c:window_path does; with thresholds up to 31 there is none)
+__device__ __forceinline__ bool charge_matched(const fsv_wres *R, const fsv_wpath *P, uint4 &h)
+{
+    h = *reinterpret_cast<const uint4 *>(P);
+    return R->err >= 0 && (h.w & 0xffu) == 1u;
+}
+
+__device__ __forceinline__ void charge_verdict(const ChargeArgs &A, uint32_t p, fsv_ovl &o, long long tlen, long long terr)
+{
+    o.err_sum = (int32_t)terr;
+    o.is_match = ((long long)(o.x_e - o.x_s + 1) * 9 <= (long long)o.align_len * 10 && terr * 1000 <= tlen * A.accept_err_pm) ? 1 : 0;
+    A.ovl[p] = o;
+    A.ovl_c[p] = make_uint4((uint32_t)o.x_s, (uint32_t)o.first_win, (uint32_t)o.n_win | (o.is_match ? 0x80000000u : 0u), 0u);
+    if (!o.is_match) for (int j = 0; j < o.n_win; j++) A.paths[o.first_win + j].state = 0;
+}
+
+__global__ __launch_bounds__(64) void k_charge_tasks(ChargeArgs A)
+{
+    const uint32_t p = blockIdx.x * 64 + threadIdx.x;
+    if (p >= A.n_pairs) return;
+    fsv_ovl o = A.ovl[p];
+    if (!o.valid || !o.is_match) return;      // (no overlap, or below the 0.9 filter: ovl_c says "not accepted" already, no path was made)
+    const fsv_wtask *T = A.tasks + o.first_win;
+    const fsv_wres *R = A.res + o.first_win;
+    const fsv_wpath *PP = A.paths + o.first_win;
+    long long tlen = 0, terr = 0;
+    int n_bad = 0;
+    for (int j = 0; j < o.n_win; j++) {
+        uint4 h;
+        tlen += T[j].x_len;
+        if (charge_matched(R + j, PP + j, h)) terr += (int)(int16_t)(h.z >> 16); else n_bad++;
+    }
+    if (!n_bad) { charge_verdict(A, p, o, tlen, terr); return; }
+    o.is_match = 0;                           // until k_charge_accept has spoken
+    A.ovl[p] = o;
+    A.ovl_list[atomicAdd(A.n_ovl, 1u)] = p;
+    atomicAdd(A.stats + CH_OVERLAPS, 1ull);
+    atomicAdd(A.stats + CH_WINDOWS, (unsigned long long)n_bad);
+    uint4 h, hl = make_uint4(0u, 0u, 0u, 0u);
+    bool left = false, cur = charge_matched(R, PP, h);
+    for (int j = 0; j < o.n_win; j++) {
+        // h / cur: window j; hl / left: window j - 1; hr / right: window j + 1
+        uint4 hr = make_uint4(0u, 0u, 0u, 0u);
+        const bool right = j + 1 < o.n_win && charge_matched(R + j + 1, PP + j + 1, hr);
+        if (!cur && R[j].y_beg >= 0) {
+            fsv_wtask t = T[j];
+            const int n = t.x_len, k0 = t.k;
+            int yb0 = left ? (int)hl.y + 1 : -1, yb1 = right ? (int)hr.x - n : -1;     // ry_end + 1 / ry_start - n
+            if (yb0 < 0 && yb1 < 0) yb0 = yb1 = R[j].y_beg + k0 - R[j].extra_begin;
+            if (yb0 < 0) yb0 = yb1;
+            if (yb1 < 0) yb1 = yb0;
+            const uint32_t tid = (uint32_t)o.first_win + (uint32_t)j;
+            t.k = (uint8_t)double_thr(k0, n, A.k_cap);
+            t.ovl = tid;
+            const uint32_t at = atomicAdd(A.n_ext, 2u);
+            t.y_start = yb0; t.win = 0u; A.ext_tasks[2 * tid] = t; A.ext_list[at] = 2 * tid;
+            t.y_start = yb1; t.win = 1u; A.ext_tasks[2 * tid + 1] = t; A.ext_list[at + 1] = 2 * tid + 1;
+        }
+        hl = h; left = cur; h = hr; cur = right;
+    }
+}
+
+// list == null: task i sits in slot i (fsv_bpm_extensions); n_list_dev == null: n_tasks is the count
+__global__ __launch_bounds__(64) void k_bpm_ext(const uint32_t *__restrict__ store, const fsv_wtask *__restrict__ tasks, const uint32_t *__restrict__ list,
+                                                const uint32_t *__restrict__ n_list_dev, uint32_t n_tasks, int k_cap, fsv_wext *__restrict__ out,
+                                                unsigned long long *__restrict__ n_run)
+{
+    if (n_list_dev) n_tasks = min(*n_list_dev, n_tasks);
+    unsigned int ran = 0;
+    for (uint32_t i = blockIdx.x * 64 + threadIdx.x; i < n_tasks; i += gridDim.x * 64) {
+        const uint32_t slot = list ? list[i] : i;
+        const fsv_wtask t = tasks[slot];
+        fsv_wext r;
+        ran += bpm_ext_run(store, t, (int)(t.win & 1u), k_cap, r) ? 1u : 0u;
+        out[slot] = r;
+    }
+    if (n_run && ran) atomicAdd(n_run, (unsigned long long)ran);
+}
+
+__global__ __launch_bounds__(64) void k_charge_accept(ChargeArgs A)
+{
+    const uint32_t li = blockIdx.x * 64 + threadIdx.x;
+    if (li >= min(*A.n_ovl, A.n_pairs)) return;
+    const uint32_t p = A.ovl_list[li];
+    fsv_ovl o = A.ovl[p];
+    const fsv_wtask *T = A.tasks + o.first_win;
+    const fsv_wres *R = A.res + o.first_win;
+    const fsv_wpath *PP = A.paths + o.first_win;
+    long long tlen = 0, terr = 0, full = 0;
+    for (int j = 0; j < o.n_win; j++) {
+        uint4 h;
+        const int n = T[j].x_len;
+        tlen += n;
+        if (charge_matched(R + j, PP + j, h)) { const int e = (int)(int16_t)(h.z >> 16); terr += e; full += e; continue; }
+        full += n;
+        if (R[j].y_beg < 0) { terr += n; continue; }       // the window lies outside y
+        const fsv_wext e0 = A.ext_res[2 * ((size_t)o.first_win + j)], e1 = A.ext_res[2 * ((size_t)o.first_win + j) + 1];
+        terr = fsv_partial_charge_hd(n, e0.t_end >= 0 ? e0.t_end + 1 : 0, e0.t_end >= 0 ? e0.err : 0, e1.t_end >= 0 ? e1.t_end + 1 : 0,
+                                     e1.t_end >= 0 ? e1.err : 0, terr);
+    }
+    charge_verdict(A, p, o, tlen, terr);
+    if (o.is_match) {
+        atomicAdd(A.stats + CH_ACCEPTED, 1ull);
+        if (full * 1000 > tlen * A.accept_err_pm) atomicAdd(A.stats + CH_FLIPPED, 1ull);
     }
 }
 

@@ -480,3 +480,81 @@ __device__ __forceinline__ void bpm_run_wide(const uint32_t *__restrict__ store,
     r.end_site = bpm_pick_end_wide(vp, vn, err, n, k, best);
     r.err = best;
 }
+
+// ---- the extension alignment: Reserve_Banded_BPM_Extension (Levenshtein_distance.h:14-205) ------------------------------------------
+// non_trim_error_rate (Correct.cpp:725-845; fsv_asm_params.partial_charge) extends a matched window's alignment into the unmatched window
+// beside it: K5's recurrence in 64-bit words with bpm_pick_end after EVERY column, and the answer is the last x column that has a band cell
+// within k (oracle/bpm.c:orc_bpm_extension, statement for statement).  dir 1 aligns both strings reversed -- x from its last base down,
+// the padded y window from its last column down -- which is what the reference does for the extension from the right; only base equality
+// enters, so no strand is taken.  One lane per task, the reference's column-by-column slide for every k: the end-site scan after each
+// column (2k steps) is what the lane spends its time on, not the slide, and bases come through one cached 16-base word per operand.
+struct ExtBaseCache {
+    uint32_t w = 0; int idx = -0x7fffffff;
+    // base at forward position q of the read at word_off (0 <= q < its length)
+    __device__ __forceinline__ uint32_t get(const uint32_t *__restrict__ store, uint32_t word_off, int q)
+    {
+        const int wi = q >> 4;
+        if (wi != idx) { w = store[word_off + (uint32_t)wi]; idx = wi; }
+        return (w >> ((q & 15) << 1)) & 3u;
+    }
+};
+
+// false: the window geometry was rejected (determine_overlap_region), nothing ran
+__device__ __forceinline__ bool bpm_ext_run(const uint32_t *__restrict__ store, const fsv_wtask &t, int dir, int k_cap, fsv_wext &out)
+{
+    out.t_end = -1; out.err = -1; out.p_end = -1; out.pad = 0;
+    fsv_wres g;
+    if (!bpm_window_geometry(t, g, k_cap)) return false;
+    const int n = t.x_len, k = t.k, wlen = n + 2 * k, win0 = t.y_start - k;
+    ExtBaseCache xc, yc;
+    // column c of the (possibly reversed) padded y window: 4 outside the read; base i of the (possibly reversed) x window
+    auto ycol = [&](int c) -> uint32_t {
+        const int p = win0 + (dir ? wlen - 1 - c : c);
+        if (p < 0 || p >= t.y_len) return 4u;
+        const uint32_t b = yc.get(store, t.y_word, t.y_rev ? t.y_len - 1 - p : p);
+        return t.y_rev ? 3u - b : b;
+    };
+    auto xcol = [&](int i) -> uint32_t { return xc.get(store, t.x_word, t.x_start + (dir ? n - 1 - i : i)); };
+    BpmState s;
+    s.eq0 = s.eq1 = s.eq2 = s.eq3 = 0; s.vp = 0; s.vn = 0;
+    for (int b = 0; b <= 2 * k; b++) bpm_eq_set(s, ycol(b), 1ull << b);
+    const uint64_t top = 1ull << (2 * k);
+    int err = 0;
+    for (int i = 0; i < n; i++) {
+        uint64_t d0;
+        if (!bpm_column(bpm_pick_eq(s, xcol(i)), s.vp, s.vn, d0)) {
+            ++err;
+            if (err - 2 * k > k) return true; // Levenshtein_distance.h:367-375: what was found so far stands
+        }
+        int best;
+        const int site = bpm_pick_end(s, err, i + 1, k, best);
+        if (best >= 0) { out.t_end = i; out.err = best; out.p_end = site; }
+        if (i + 1 < n) {
+            s.eq0 >>= 1; s.eq1 >>= 1; s.eq2 >>= 1; s.eq3 >>= 1;
+            bpm_eq_set(s, ycol(i + 1 + 2 * k), top);
+        }
+    }
+    return true;
+}
+
+// Correct.cpp:820-838 (oracle/asm.c:unmatched_charge, its last six lines): the charge of an unmatched window of n bases that the left
+// extension covers al0 bases of with er0 errors and the right one al1 with er1 (al = 0: no extension); terr is the overlap's running
+// total, the new total is returned.  Where the extensions overlap, the reference scales their errors in float, one rounding per operation
+// (x86-64 without FMA); the device must not contract the multiply and the add, hence the _rn intrinsics.
+__host__ __device__ inline long long fsv_partial_charge_hd(int n, int al0, int er0, int al1, int er1, long long terr)
+{
+    if (al0 && al1) {
+        if (al0 + al1 <= n) return terr + er0 + er1 + (n - al0 - al1);
+#if defined(__HIP_DEVICE_COMPILE__)
+        const float rate = __fdiv_rn((float)n, (float)(al0 + al1));
+        return (long long)__fadd_rn(__ll2float_rn(terr), __fmul_rn((float)(unsigned)(er0 + er1), rate));
+#else
+        volatile float rate = (float)n / (float)(al0 + al1);       // (volatile: every operation rounded to float, whatever the host's flags)
+        volatile float scaled = (float)(unsigned)(er0 + er1) * rate;
+        volatile float sum = (float)terr + scaled;
+        return (long long)sum;
+#endif
+    }
+    if (!al0 && !al1) return terr + n;
+    return al0 ? terr + er0 + (n - al0) : terr + er1 + (n - al1);
+}

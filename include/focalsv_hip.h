@@ -181,6 +181,11 @@ typedef struct fsv_asm_params {
     int32_t kmer_table;       /* 0 (default in all three profiles): off.  1: hifiasm's k-mer count table per read set before round 0 (ha_ft_gen, htab.cpp:917;
                                * see fsv_kmer_table) at (w = 1, k, hpc) -- a set whose count histogram has no coverage peak is left as hifiasm leaves
                                * it: reads uncorrected, no contig, FSV_W_LOW_COV | FSV_W_NO_LAYOUT; every other set is assembled as with 0 */
+    int32_t partial_charge;   /* 0 (default in all three profiles): an unmatched window costs an overlap its whole length.  1: hifiasm's non_trim_error_rate
+                               * (Correct.cpp:725-845): the window is charged what two banded extension alignments -- from the left neighbour's exact end,
+                               * from the right neighbour's exact start, doubled threshold -- leave uncovered, plus their errors, and every overlap's error
+                               * sum counts the matched windows' distances after generate_cigar (see fsv_bpm_extensions, fsv_asm_last_charge).  Needs
+                               * k_cap <= FSV_K_MAX: FSV_EINVAL with the wide-band profiles */
 } fsv_asm_params;
 void fsv_asm_default_params(fsv_asm_params *p);
 /* ONT-profile reads (BASELINE configs[4]: ~10 % error): k = 15, w = 15 without homopolymer compression (a 30 kb read then has ~3 750 minimizers: below the 4 096 a list holds), chain indel budget 0.15 / 0.05,
@@ -326,6 +331,38 @@ int fsv_kmer_table(fsv_ctx *ctx, const fsv_readsets *sets, int32_t w, int32_t k,
 /* verdicts of the last fsv_assemble_batch with kmer_table = 1 on this context, all chunks, in set order (n_sets: that call's; FSV_EINVAL
  * otherwise, or when that call ran with kmer_table = 0); ms: the stage's summed kernel time */
 int fsv_asm_last_kmer_table(const fsv_ctx *ctx, fsv_kmer_set *out, uint32_t n_sets, double *ms);
+
+/* ---- partial charge of unmatched windows (non_trim_error_rate, Correct.cpp:725-845; fsv_asm_params.partial_charge) ----------
+ * The extension alignment (Reserve_Banded_BPM_Extension, Levenshtein_distance.h:14-205): K5's recurrence, and after every column the
+ * best band cell within k; the extension ends at the last x column that has one. */
+typedef struct fsv_wext {
+    int32_t t_end;   /* last x column with a band cell within k, -1: none (or the window geometry was rejected) */
+    int32_t err;     /* its distance, -1: none */
+    int32_t p_end;   /* offset inside the padded y window it ends at, -1: none */
+    int32_t pad;     /* 0 */
+} fsv_wext;          /* 16 bytes */
+/* The extension kernel alone, on host tasks, through the launch code fsv_assemble_batch runs with partial_charge = 1.  A task is read as
+ * K5 reads it: y_start is the strand coordinate where the window's first x base is placed, k the (already doubled) threshold <= FSV_K_MAX,
+ * the padded window columns y_start - k .. y_start + x_len + k - 1 ('N' outside the read); the geometry rule is K5's with k_cap.
+ * dir[i] = 0: x against the padded window.  dir[i] = 1: both strings reversed; the results are in the reversed coordinates. */
+int fsv_bpm_extensions(fsv_ctx *ctx, const uint32_t *store, size_t store_words, const fsv_wtask *tasks, const uint8_t *dir,
+                       uint32_t n_tasks, int32_t k_cap, fsv_wext *out);
+
+/* The charge itself (Correct.cpp:820-838): an unmatched window of n bases, al0 bases covered from the left with er0 errors, al1 from the
+ * right with er1 (al = 0: no extension on that side), terr the overlap's running error total; returns the new total.  Where the two
+ * extensions overlap the reference scales their errors in single precision, so the running total takes part.  Pure host function. */
+int64_t fsv_partial_charge(int32_t n, int32_t al0, int32_t er0, int32_t al1, int32_t er1, int64_t terr);
+
+typedef struct fsv_charge_stats {
+    uint64_t n_overlaps;   /* overlaps that passed the 0.9 filter with at least one unmatched window */
+    uint64_t n_windows;    /* unmatched windows charged */
+    uint64_t n_ext;        /* extension alignments run (at most 2 per window) */
+    uint64_t n_accepted;   /* of n_overlaps: accepted */
+    uint64_t n_flipped;    /* of n_accepted: the full-length charge (same matched distances) would have rejected them */
+    double   ms;           /* summed kernel time of the stage (k_charge_tasks, k_bpm_ext, k_charge_accept) */
+} fsv_charge_stats;
+/* counters of the last fsv_assemble_batch on this context, all rounds and chunks; FSV_EINVAL when that call ran with partial_charge = 0 */
+int fsv_asm_last_charge(const fsv_ctx *ctx, fsv_charge_stats *out);
 
 /* ---- aligner boundary ---------------------------------------------------------
  * Replaces `minimap2 -a -x asm5 --cs -r2k ref_chr.fa assemblies.fa | samtools sort` and the pysam read-back
