@@ -32,7 +32,7 @@ assert OVL_DTYPE.itemsize == 56
 class AsmParams(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("k", "w", "hpc", "n_rounds", "min_ovlp", "min_anchors", "lookback", "bw_ec", "bw_final",
                                          "min_contig_reads", "win_rate_pm", "k_cap", "accept_err_pm", "bw_rechain", "w_later", "partition", "second_round", "ins_dag",
-                                         "min_anchors_final", "min_ovlp_final", "graph_layout", "junction_cigars", "kmer_table", "partial_charge")]
+                                         "min_anchors_final", "min_ovlp_final", "graph_layout", "junction_cigars", "kmer_filter", "kmer_table", "partial_charge")]
 
 
 class ReadSets(C.Structure):
@@ -51,6 +51,10 @@ KMER_BINS = 4096
 KMER_SET_DTYPE = np.dtype([("peak_hom", "<i4"), ("peak_het", "<i4"), ("cutoff", "<i4"), ("low_i", "<i4"), ("max_i", "<i4"), ("pad", "<i4"),
                            ("n_entries", "<u8"), ("n_distinct", "<u8"), ("n_filtered", "<u8"), ("n_indexed", "<u8")])
 assert KMER_SET_DTYPE.itemsize == 56
+# fsv_kmer_index_set: the figures of hifiasm's first ha_pt_gen on one read set (the filtered sketch, counted)
+KMER_INDEX_DTYPE = np.dtype([("n_entries", "<u8"), ("n_distinct", "<u8"), ("n_indexed", "<u8"), ("low_i", "<i4"), ("max_i", "<i4"),
+                             ("peak_hom", "<i4"), ("peak_het", "<i4")])
+assert KMER_INDEX_DTYPE.itemsize == 40
 # fsv_wext: the result of one extension alignment (fsv_bpm_extensions)
 WEXT_DTYPE = np.dtype([("t_end", "<i4"), ("err", "<i4"), ("p_end", "<i4"), ("pad", "<i4")])
 assert WEXT_DTYPE.itemsize == 16
@@ -156,6 +160,9 @@ def load():
         "fsv_sketch_reads": (C.c_int, [vp, C.POINTER(ReadSets), C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, C.c_uint64, vp]),
         "fsv_asm_overlaps": (C.c_int, [vp, C.POINTER(ReadSets), C.POINTER(AsmParams), C.c_int32, vp, C.c_uint32, vp, C.c_uint64, vp, vp, C.c_uint64,
                                        u32p, u32p, vp]),
+        "fsv_sketch_reads_filtered": (C.c_int, [vp, C.POINTER(ReadSets), C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, C.c_uint64, vp, vp, vp]),
+        "fsv_kmer_index": (C.c_int, [vp, C.POINTER(ReadSets), C.c_int32, C.c_int32, C.c_int32, vp, vp, vp]),
+        "fsv_asm_last_kmer_index": (C.c_int, [vp, vp, C.c_uint32, C.POINTER(C.c_double)]),
         "fsv_kmer_peaks": (C.c_int, [vp, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
         "fsv_kmer_table": (C.c_int, [vp, C.POINTER(ReadSets), C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, C.c_uint64, vp]),
         "fsv_asm_last_kmer_table": (C.c_int, [vp, vp, C.c_uint32, C.POINTER(C.c_double)]),
@@ -410,6 +417,28 @@ class Context:
         self.check(self._lib.fsv_sketch_reads(self._h, C.byref(rs), w, k, hpc, variant, _ptr(out), cap, _ptr(off)), "fsv_sketch_reads")
         return [out[int(off[i]):int(off[i + 1])].copy() for i in range(len(read_len))]
 
+    def sketch_reads_filtered(self, store_dev, word_off, read_len, set_start, filters, w=51, k=51, hpc=1, variant=0, out_cap=None):
+        """fsv_sketch_reads_filtered: the sketch through the sets' high-count k-mer filters.  filters: one sequence of uint64 hashes per
+        read set (any order, duplicates allowed), or None for no lists at all -> per read its minimizers, as sketch_reads"""
+        word_off = np.ascontiguousarray(word_off, dtype=np.uint64)
+        read_len = np.ascontiguousarray(read_len, dtype=np.int32)
+        set_start = np.ascontiguousarray(set_start, dtype=np.uint32)
+        n_sets = len(set_start) - 1
+        rs = ReadSets(C.c_void_p(store_dev), _ptr(word_off).value, _ptr(read_len).value, _ptr(set_start).value, len(read_len), n_sets, None)
+        flt = off = None
+        if filters is not None:
+            assert len(filters) == n_sets
+            lists = [np.ascontiguousarray(f, dtype=np.uint64) for f in filters]
+            off = np.zeros(n_sets + 1, dtype=np.uint64)
+            off[1:] = np.cumsum([len(f) for f in lists])
+            flt = np.concatenate(lists + [np.zeros(1, dtype=np.uint64)])      # (never an empty buffer)
+        cap = int(read_len.sum()) + 64 * len(read_len) + 64 if out_cap is None else int(out_cap)
+        out = np.zeros(max(cap, 1), dtype=MZ_DTYPE)
+        o = np.zeros(len(read_len) + 1, dtype=np.uint64)
+        self.check(self._lib.fsv_sketch_reads_filtered(self._h, C.byref(rs), w, k, hpc, variant, _ptr(out), cap, _ptr(o), None if flt is None else _ptr(flt),
+                                                       None if off is None else _ptr(off)), "fsv_sketch_reads_filtered")
+        return [out[int(o[i]):int(o[i + 1])].copy() for i in range(len(read_len))]
+
     def asm_overlaps(self, store_dev, word_off, read_len, set_start, params=None, pass_=0, rechain=()):
         """fsv_asm_overlaps (test hook): the overlap stage of one pass -> (ovl[OVL_DTYPE] per ordered pair slot, pair_base[n_sets + 1],
         tasks[WTASK_DTYPE], overflow flag, warn[n_reads]); see include/focalsv_hip.h for the slot formula"""
@@ -457,6 +486,29 @@ class Context:
         out = np.zeros(max(1, n_sets), dtype=KMER_SET_DTYPE)
         ms = C.c_double(0.0)
         self.check(self._lib.fsv_asm_last_kmer_table(self._h, _ptr(out), int(n_sets), C.byref(ms)), "fsv_asm_last_kmer_table")
+        return out[:n_sets], ms.value
+
+    def kmer_index(self, store_dev, word_off, read_len, set_start, w=51, k=51, hpc=1, want_hist=True):
+        """fsv_kmer_index: hifiasm's first ha_pt_gen per read set -- the count table at w = 1, its filter, the filtered sketch at w, counted
+        -> (table[KMER_SET_DTYPE], index[KMER_INDEX_DTYPE], index hist uint64[n_sets, 4096] or None)"""
+        word_off = np.ascontiguousarray(word_off, dtype=np.uint64)
+        read_len = np.ascontiguousarray(read_len, dtype=np.int32)
+        set_start = np.ascontiguousarray(set_start, dtype=np.uint32)
+        n_sets = len(set_start) - 1
+        rs = ReadSets(C.c_void_p(store_dev), _ptr(word_off).value, _ptr(read_len).value, _ptr(set_start).value, len(read_len), n_sets, None)
+        tab = np.zeros(max(1, n_sets), dtype=KMER_SET_DTYPE)
+        idx = np.zeros(max(1, n_sets), dtype=KMER_INDEX_DTYPE)
+        hist = np.zeros((max(1, n_sets), KMER_BINS), dtype=np.uint64) if want_hist else None
+        self.check(self._lib.fsv_kmer_index(self._h, C.byref(rs), int(w), int(k), int(hpc), _ptr(tab), _ptr(idx), None if hist is None else _ptr(hist)),
+                   "fsv_kmer_index")
+        return tab[:n_sets], idx[:n_sets], (None if hist is None else hist[:n_sets])
+
+    def last_kmer_index(self, n_sets):
+        """fsv_asm_last_kmer_index: the index figures of round 0 of the last assemble_batch with kmer_filter = 1, in set order
+        -> (index[KMER_INDEX_DTYPE], the summed kernel time of the filter-set build and the index in ms)"""
+        out = np.zeros(max(1, n_sets), dtype=KMER_INDEX_DTYPE)
+        ms = C.c_double(0.0)
+        self.check(self._lib.fsv_asm_last_kmer_index(self._h, _ptr(out), int(n_sets), C.byref(ms)), "fsv_asm_last_kmer_index")
         return out[:n_sets], ms.value
 
     def last_charge(self):

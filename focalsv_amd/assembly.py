@@ -50,9 +50,10 @@ def find_read_sets(regions_dir: str, data_type: int = 0) -> List[str]:
     return out
 
 
-def _set_cost(reads, kmer_table: bool = False) -> int:
+def _set_cost(reads, kmer_table: bool = False, kmer_filter: bool = False) -> int:
     """device bytes a read set needs, dominated by the window-task bound: every read against every other, 176 B per window; with the
-    k-mer count table stage, its table besides (12 B a slot, a power of two of at least twice the bases) and the filter list (8 B a base)"""
+    k-mer count table stage, its table besides (12 B a slot, a power of two of at least twice the bases) and the filter list (8 B a base);
+    with the k-mer filter, the set's filter set (8 B a slot, a power of two of at least twice a thirtieth of the bases)"""
     n = len(reads)
     win = sum((len(r) + 374) // 375 for r in reads)
     bases = sum(len(r) for r in reads)
@@ -62,6 +63,11 @@ def _set_cost(reads, kmer_table: bool = False) -> int:
         while slots < 2 * bases:
             slots *= 2
         table = slots * 12 + bases * 8 + 4096 * 4
+    if kmer_filter and bases:
+        slots = 2
+        while slots < 2 * (bases // 30 + 1):
+            slots *= 2
+        table += slots * 8
     return ((n - 1) * win * 176 + n * n * 72 + bases * 24 if n > 1 else 4096) + table
 
 
@@ -100,7 +106,7 @@ def assemble_sets(ctx: _lib.Context, sets, logger=None, budget_bytes: Optional[i
 
     batch, used = [], 0
     for i, rs in enumerate(sets):
-        c = _set_cost(rs, bool(params is not None and params.kmer_table))
+        c = _set_cost(rs, bool(params is not None and params.kmer_table), bool(params is not None and params.kmer_filter))
         if batch and used + c > budget_bytes:
             run_or_split(batch)
             batch, used = [], 0
@@ -112,14 +118,17 @@ def assemble_sets(ctx: _lib.Context, sets, logger=None, budget_bytes: Optional[i
 
 
 def assembly(out_dir: str, cpu: int = 10, threads: int = 8, data_type: int = 0, logger=None, ctx: Optional[_lib.Context] = None,
-             device: int = 0, skip_existing: bool = True, kmer_table: bool = False, partial_charge: bool = False) -> Dict[str, int]:
+             device: int = 0, skip_existing: bool = True, kmer_table: bool = False, partial_charge: bool = False, kmer_filter: bool = False) -> Dict[str, int]:
     """3_assembly.py:28-41.  cpu/threads are accepted for CLI compatibility (the GPU batch replaces both).
     kmer_table: run hifiasm's k-mer count table per read set first (fsv_asm_params.kmer_table): a set whose count histogram has no
     coverage peak is left as hifiasm leaves it -- no contig, status bit 128 -- instead of being assembled
+    kmer_filter: hifiasm's high-count k-mer filter in every sketch (fsv_asm_params.kmer_filter): a k-mer that occurs 5 x the coverage peak
+    times or more in its read set is no minimizer candidate; implies kmer_table, whose filter list it takes
     partial_charge: hifiasm's non_trim_error_rate (fsv_asm_params.partial_charge): an unmatched window beside a matched one costs an overlap
     what two extension alignments leave uncovered, not its whole length; HiFi read sets only (the wide-band profiles refuse it)"""
     if partial_charge and data_type != 0:
         raise ValueError("partial_charge applies to HiFi read sets (data_type 0) only: the CLR / ONT profiles use thresholds above 31")
+    kmer_table = kmer_table or kmer_filter
     logger = logger or setup_logging("3_ASSEMBLY", out_dir)
     regions_dir = os.path.join(out_dir, "regions")
     fas = find_read_sets(regions_dir, data_type)
@@ -139,6 +148,7 @@ def assembly(out_dir: str, cpu: int = 10, threads: int = 8, data_type: int = 0, 
         try:
             params = ctx.clr_asm_params() if data_type == 1 else ctx.ont_asm_params()
             params.kmer_table = int(bool(kmer_table))
+            params.kmer_filter = int(bool(kmer_filter))
             per_set = assemble_sets(ctx, sets, logger, params=params)
         finally:
             if own:
@@ -171,6 +181,7 @@ def assembly(out_dir: str, cpu: int = 10, threads: int = 8, data_type: int = 0, 
         try:
             params = ctx.default_asm_params()
             params.kmer_table = int(bool(kmer_table))
+            params.kmer_filter = int(bool(kmer_filter))
             params.partial_charge = int(bool(partial_charge))
             per_set = assemble_sets(ctx, sets, logger, set_flags=[_lib.SET_UNPHASED if 'unphased' in os.path.basename(f) else 0 for f in fas],
                                     params=params if kmer_table or partial_charge else None)

@@ -84,6 +84,13 @@ struct AsmWs {
     // filter list of the last stage and -- for a batch of several chunks -- of all its chunks, in set order
     Dev<unsigned long long> km_keys, km_flt, km_flt_all; Dev<uint32_t> km_cnt, km_hist, km_cursor, km_err; Dev<uint64_t> km_tab_off, km_flt_off;
     Dev<int32_t> km_cutoff; Dev<KmerTile> km_tiles;
+    // kmer_filter = 1 (and the stage hooks fsv_sketch_reads_filtered / fsv_kmer_index): the sets' filter sets that the sketch kernels probe
+    // (k_flt_build: keys back to back, n_sets + 1 slot offsets), the set of every read, a caller's lists on the device; flt: the view a
+    // sketch launch takes -- nothing when no set has a slot
+    Dev<unsigned long long> fs_keys, fs_list; Dev<uint64_t> fs_off, fs_list_off; Dev<uint32_t> fs_read_set;
+    SketchFilter flt;
+    // what the last fsv_assemble_batch with kmer_filter = 1 left: per set the figures of hifiasm's first ha_pt_gen (peak_hom: its hom_cov)
+    std::vector<fsv_kmer_index_set> ki_last; double ki_ms = 0; bool ki_valid = false;
     // partial_charge = 1 (charge_stage): two extension tasks and results per window task at fixed slots, the slots in use, the overlaps
     // waiting for their verdict, the two list lengths, the stage's counters (fsv_charge_stats' five, summed over the chunk's rounds)
     Dev<fsv_wtask> ext_tasks; Dev<fsv_wext> ext_res; Dev<uint32_t> ext_list, charge_list, charge_n; Dev<unsigned long long> charge_ct;
@@ -114,7 +121,7 @@ struct AsmWs {
                        tasks3, res3, src3, bnd_flag, bnd_list, bnd_patch, bnd_bytes, changed, pair_read, wide_list, cols, tmp, gwin_off, gwin_read, sk_ends, sk_low, sk_high,
                        hits, hits_packed, set_hits, ovl_prev, exact_flag, inexact_list, upair_base, upair_tab, upair_tab_sw, ovl_c, gwin_tab, cwin, cwin_len, warn, thr_tab,
                        pieces, contig_out, new_len, unpack_off, km_keys, km_flt, km_flt_all, km_cnt, km_hist, km_cursor, km_err, km_tab_off, km_flt_off, km_cutoff, km_tiles,
-                       ext_tasks, ext_res, ext_list, charge_list, charge_n, charge_ct);
+                       fs_keys, fs_list, fs_off, fs_list_off, fs_read_set, ext_tasks, ext_res, ext_list, charge_list, charge_n, charge_ct);
     }
 };
 
@@ -266,7 +273,8 @@ int overlap_stage(fsv_ctx *ctx, AsmWs &W, const Round &R, bool final_pass)
     TRY(ensure(ctx, W.ovl, std::max(1u, B.n_pairs)));
     TRY(ensure(ctx, W.ovl_c, std::max(1u, B.n_pairs)));
     W.kt.begin(ctx, PASS_WINDOWS, KN_SKETCH, 0);    // bytes: filled in from the round's counters (minimizers produced, bases sketched)
-    TRY(launch_sketch(ctx, W, SketchJob{R.store, B.n_reads, G.word_off[B.n_reads], G.max_words, w, P.k, P.hpc, nullptr, w, false, only_changed}));
+    TRY(launch_sketch(ctx, W, SketchJob{R.store, B.n_reads, G.word_off[B.n_reads], G.max_words, w, P.k, P.hpc, nullptr, w, false, only_changed,
+                                     P.kmer_filter ? W.flt : SketchFilter{}}));   // (every round and the final pass: the one filter of the raw reads, as ha_flt_tab)
     W.kt.end(ctx);
     // the sort in k_uniq holds a read's minimizers in LDS (16 B per entry): one instantiation for lists up to 1 024 entries (many
     // reads per CU), one for longer ones; each launch skips the reads of the other size class, so the host need not know the
@@ -404,6 +412,7 @@ extern "C" void fsv_asm_default_params(fsv_asm_params *p)
     p->bw_ec = 20; p->bw_final = 0; p->min_contig_reads = 4;
     p->win_rate_pm = 40; p->k_cap = FSV_K_MAX; p->accept_err_pm = 30; p->bw_rechain = 1; p->w_later = 0; p->partition = 1; p->second_round = 1; p->ins_dag = 1;
     p->min_anchors_final = 1; p->min_ovlp_final = 1; p->graph_layout = 1; p->junction_cigars = 1;
+    p->kmer_filter = 0;
     p->kmer_table = 0;
     p->partial_charge = 0;
 }
@@ -1366,8 +1375,9 @@ struct KmerClock {
 // The stage on the caller's read sets: sketch at (w, k, hpc) into W.mz, count per set, histogram, verdict (host: the histograms are 16 KB
 // a set), filter list.  out: n_sets records.  hist / flt_hash + flt_off: optional host copies (see fsv_kmer_table).  Leaves the filter
 // list in W.km_flt with the offsets in flt_off_out, and adds the launches' time to *ms.
+// sketch_flt (the index of hifiasm's ha_pt_gen): the sketch takes these filter sets, and no filter list is made of what it counts.
 static int kmer_stage(fsv_ctx *ctx, AsmWs &W, const fsv_readsets *sets, int w, int k, int hpc, fsv_kmer_set *out, uint64_t *hist, uint64_t *flt_hash,
-                      uint64_t flt_cap, uint64_t *flt_off, std::vector<uint64_t> &flt_off_out, double *ms)
+                      uint64_t flt_cap, uint64_t *flt_off, std::vector<uint64_t> &flt_off_out, double *ms, const SketchFilter *sketch_flt = nullptr)
 {
     const uint32_t n_reads = sets->n_reads, n_sets = sets->n_sets;
     flt_off_out.assign((size_t)n_sets + 1, 0);
@@ -1398,7 +1408,8 @@ static int kmer_stage(fsv_ctx *ctx, AsmWs &W, const fsv_readsets *sets, int w, i
         TRY(ensure(ctx, W.mz, G.mz_off[n_reads]));
         TRY(ensure(ctx, W.mz_cnt, n_reads));
         clock.mark();
-        TRY(launch_sketch(ctx, W, SketchJob{sets->store_dev, n_reads, G.word_off[n_reads], G.max_words, w, k, hpc, nullptr, w, false, nullptr}));
+        TRY(launch_sketch(ctx, W, SketchJob{sets->store_dev, n_reads, G.word_off[n_reads], G.max_words, w, k, hpc, nullptr, w, false, nullptr,
+                                         sketch_flt ? *sketch_flt : SketchFilter{}}));
         clock.mark();
         // the tables are sized from what the sketch emitted
         std::vector<uint32_t> cnt(n_reads);
@@ -1450,7 +1461,7 @@ static int kmer_stage(fsv_ctx *ctx, AsmWs &W, const fsv_readsets *sets, int w, i
         o.n_entries = entries[s];
         for (int c = 1; c < FSV_KMER_BINS; c++) if (c >= o.cutoff) o.n_filtered += h[c];
         for (int c = 2; c <= FSV_KMER_BINS - 2; c++) o.n_indexed += (uint64_t)c * h[c];
-        flt_off_out[s + 1] = flt_off_out[s] + o.n_filtered;
+        flt_off_out[s + 1] = flt_off_out[s] + (sketch_flt ? 0 : o.n_filtered);
     }
     const uint64_t n_flt = flt_off_out[n_sets];
     if (n_flt) {
@@ -1479,6 +1490,68 @@ static int kmer_stage(fsv_ctx *ctx, AsmWs &W, const fsv_readsets *sets, int w, i
             FSV_HIP(ctx, hipStreamSynchronize(ctx->stream));
         }
         for (uint32_t s = 0; s < n_sets; s++) std::sort(flt_hash + flt_off[s], flt_hash + flt_off[s + 1]);
+    }
+    return FSV_OK;
+}
+
+// The sets' filter sets for the sketch kernels (k_sketch.h), from filter lists on the device: set s's keys are list[list_off[s] ..
+// list_off[s + 1]), any order, duplicates allowed.  skip (or null / empty): sets with a non-zero entry get no slots -- their reads are
+// sketched unfiltered.  Leaves the view in W.flt -- nothing when no set has a slot: every launch then runs the kernels without the
+// filter -- and adds the build's time to *ms.
+static int build_filter_sets(fsv_ctx *ctx, AsmWs &W, const fsv_readsets *sets, const unsigned long long *list, const std::vector<uint64_t> &list_off,
+                             const std::vector<uint8_t> *skip, double *ms)
+{
+    const uint32_t n_sets = sets->n_sets, n_reads = sets->n_reads;
+    W.flt = SketchFilter{};
+    std::vector<uint64_t> set_off((size_t)n_sets + 1, 0);
+    for (uint32_t s = 0; s < n_sets; s++)
+        set_off[s + 1] = set_off[s] + ((skip && !skip->empty() && (*skip)[s]) ? 0 : flt_set_slots(list_off[s + 1] - list_off[s]));
+    const uint64_t total = set_off[n_sets], n_keys = list_off[n_sets];
+    if (!total || !n_reads) return FSV_OK;
+    if (n_keys >= (1ull << 39)) return fsv_fail(ctx, FSV_EUNSUP, "filter lists too long for one pass; split the batch");
+    std::vector<uint32_t> read_set(n_reads);
+    for (uint32_t s = 0; s < n_sets; s++) for (uint32_t r = sets->set_start[s]; r < sets->set_start[s + 1]; r++) read_set[r] = s;
+    TRY(ensure(ctx, W.fs_keys, total));
+    TRY(upload(ctx, W.fs_off, set_off));
+    TRY(upload(ctx, W.fs_list_off, list_off));
+    TRY(upload(ctx, W.fs_read_set, read_set));
+    TRY(ensure(ctx, W.km_err, 1));
+    TRY(zero(ctx, W.km_err, 1));
+    KmerClock clock(ctx);
+    clock.mark();
+    FSV_HIP(ctx, hipMemsetAsync(W.fs_keys.p, 0xff, total * sizeof(unsigned long long), ctx->stream));   // every slot FSV_KMER_EMPTY
+    FSV_LAUNCH(ctx, ctx->stream, k_flt_build, dim3((uint32_t)((n_keys + 255) / 256)), dim3(256), 0, list, W.fs_list_off.p, W.fs_off.p, n_sets, W.fs_keys.p, W.km_err.p);
+    clock.mark();
+    uint32_t err = 0;
+    TRY(download(ctx, &err, W.km_err, 1));
+    FSV_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (err) return fsv_fail(ctx, FSV_EINTERNAL, "k-mer filter: a filter set ran full");
+    if (ms) *ms += clock.ms();
+    W.flt = SketchFilter{W.fs_keys.p, W.fs_off.p, W.fs_read_set.p};
+    return FSV_OK;
+}
+
+// hifiasm's first ha_pt_gen (htab.cpp:952-998) on the caller's sets: the sketch at (w, k, hpc) through the filter sets in W.flt, counted
+// with the count table's own kernels.  out: n_sets records; hist: n_sets x 4096 or null.  A skipped set (see build_filter_sets) is one
+// hifiasm filters every k-mer of: the index of nothing.
+static int index_stage(fsv_ctx *ctx, AsmWs &W, const fsv_readsets *sets, int w, int k, int hpc, const std::vector<uint8_t> *skip, fsv_kmer_index_set *out,
+                       uint64_t *hist, double *ms)
+{
+    std::vector<fsv_kmer_set> v(sets->n_sets);
+    std::vector<uint64_t> off;
+    const SketchFilter flt = W.flt;
+    TRY(kmer_stage(ctx, W, sets, w, k, hpc, v.data(), hist, nullptr, 0, nullptr, off, ms, &flt));
+    std::vector<int64_t> none(FSV_KMER_BINS, 0);
+    for (uint32_t s = 0; s < sets->n_sets; s++) {
+        fsv_kmer_index_set &o = out[s];
+        memset(&o, 0, sizeof(o));
+        if (skip && !skip->empty() && (*skip)[s]) {
+            o.peak_hom = fsv_kmer_peaks_hd(none.data(), FSV_KMER_BINS, FSV_KMER_START, &o.peak_het, &o.low_i, &o.max_i);
+            if (hist) memset(hist + (size_t)s * FSV_KMER_BINS, 0, FSV_KMER_BINS * sizeof(uint64_t));
+            continue;
+        }
+        o.n_entries = v[s].n_entries; o.n_distinct = v[s].n_distinct; o.n_indexed = v[s].n_indexed;
+        o.low_i = v[s].low_i; o.max_i = v[s].max_i; o.peak_hom = v[s].peak_hom; o.peak_het = v[s].peak_het;
     }
     return FSV_OK;
 }
@@ -1512,6 +1585,34 @@ static int fsv_kmer_table_impl(fsv_ctx *ctx, const fsv_readsets *sets, int32_t w
     W.n_reads = 0; W.cur_store = nullptr;     // (the workspace's read tables are this call's now: nothing for fsv_asm_fetch_reads)
     std::vector<uint64_t> off;
     return kmer_stage(ctx, W, sets, w, k, hpc ? 1 : 0, out, hist, flt_hash, flt_cap, flt_off, off, nullptr);
+}
+
+static int fsv_kmer_index_impl(fsv_ctx *ctx, const fsv_readsets *sets, int32_t w, int32_t k, int32_t hpc, fsv_kmer_set *table, fsv_kmer_index_set *index,
+                               uint64_t *hist)
+{
+    if (!ctx || !sets || !sets->store_dev || !sets->word_off || !sets->read_len || !sets->set_start || !table || !index) return FSV_EINVAL;
+    TRY(check_sketch_scheme(ctx, w, k));
+    TRY(check_set_start(ctx, sets));
+    FSV_HIP(ctx, hipSetDevice(ctx->device));
+    AsmWs &W = *ws_get(ctx);
+    W.n_reads = 0; W.cur_store = nullptr;     // (the workspace's read tables are this call's now: nothing for fsv_asm_fetch_reads)
+    std::vector<uint64_t> off;
+    TRY(kmer_stage(ctx, W, sets, 1, k, hpc ? 1 : 0, table, nullptr, nullptr, 0, nullptr, off, nullptr));
+    // (a set without a peak has cutoff -5: its list holds every k-mer, its sketch comes out empty)
+    TRY(build_filter_sets(ctx, W, sets, W.km_flt.p, off, nullptr, nullptr));
+    const int rc = index_stage(ctx, W, sets, w, k, hpc ? 1 : 0, nullptr, index, hist, nullptr);
+    W.flt = SketchFilter{};
+    return rc;
+}
+
+static int fsv_asm_last_kmer_index_impl(const fsv_ctx *ctx, fsv_kmer_index_set *out, uint32_t n_sets, double *ms)
+{
+    if (!ctx || !ctx->asm_ws || (!out && n_sets)) return FSV_EINVAL;
+    const AsmWs &W = *(const AsmWs *)ctx->asm_ws;
+    if (!W.ki_valid || W.ki_last.size() != n_sets) return FSV_EINVAL;
+    if (n_sets) memcpy(out, W.ki_last.data(), (size_t)n_sets * sizeof(fsv_kmer_index_set));
+    if (ms) *ms = W.ki_ms;
+    return FSV_OK;
 }
 
 static int fsv_asm_last_kmer_table_impl(const fsv_ctx *ctx, fsv_kmer_set *out, uint32_t n_sets, double *ms)
@@ -1550,6 +1651,14 @@ static int kmer_stage_of_chunk(fsv_ctx *ctx, AsmWs &W, const fsv_readsets *sets,
     for (uint32_t s = 0; s < sets->n_sets; s++) W.km_last_flt_off.push_back(have + off[s + 1]);
     W.km_last.insert(W.km_last.end(), v.begin(), v.end());
     W.km_last_flt = W.km_flt_all.p;
+    if (P.kmer_filter) {
+        // the chunk's filter sets, which every sketch of its rounds and of its final pass takes; sets without a peak stay as they are
+        // (kmer_table leaves them alone).  Then hifiasm's first ha_pt_gen: the filtered sketch at w, counted
+        TRY(build_filter_sets(ctx, W, sets, W.km_flt.p, off, &low, &W.ki_ms));
+        std::vector<fsv_kmer_index_set> idx(sets->n_sets);
+        TRY(index_stage(ctx, W, sets, P.w, P.k, P.hpc ? 1 : 0, &low, idx.data(), nullptr, &W.ki_ms));
+        W.ki_last.insert(W.ki_last.end(), idx.begin(), idx.end());
+    }
     return FSV_OK;
 }
 
@@ -1612,8 +1721,10 @@ static int assemble_chunk(fsv_ctx *ctx, const fsv_readsets *sets, const fsv_asm_
 
 // Work a set brings: its window-task bound (every read's windows against every other read) and its ordered pairs.
 // kmer_bytes: what the k-mer count table stage would hold for the set -- a table slot (12 B) for at least twice its bases, the filter
-// list when every k-mer is filtered (8 B a base), its histogram.
-static void set_cost(const fsv_readsets *sets, uint32_t s, uint64_t &tasks, uint64_t &pairs, uint64_t &bases, uint64_t &kmer_bytes)
+// list when every k-mer is filtered (8 B a base), its histogram.  flt_bytes: the set's filter set with kmer_filter = 1 -- 8 B a slot for at
+// least twice its filtered keys; a filtered key occurs 5 x peak_hom times or more and no peak lies below FSV_KMER_START + 1, so a thirtieth
+// of the bases bounds them (a set without a peak gets no filter set)
+static void set_cost(const fsv_readsets *sets, uint32_t s, uint64_t &tasks, uint64_t &pairs, uint64_t &bases, uint64_t &kmer_bytes, uint64_t &flt_bytes)
 {
     const uint64_t ns = sets->set_start[s + 1] - sets->set_start[s];
     uint64_t nw = 0; bases = 0;
@@ -1621,6 +1732,7 @@ static void set_cost(const fsv_readsets *sets, uint32_t s, uint64_t &tasks, uint
     tasks = ns > 1 ? nw * (ns - 1) : 0;
     pairs = ns > 1 ? ns * (ns - 1) : 0;
     kmer_bytes = kmer_table_slots(bases) * 12ull + bases * 8ull + FSV_KMER_BINS * 4ull;
+    flt_bytes = flt_set_slots(bases / 30 + 1) * 8ull;
 }
 
 static int check_asm_params(fsv_ctx *ctx, const fsv_asm_params &P)
@@ -1630,6 +1742,8 @@ static int check_asm_params(fsv_ctx *ctx, const fsv_asm_params &P)
     if (P.k_cap < 1 || P.k_cap > FSV_K_WIDE || P.win_rate_pm < 1 || (int)(FSV_WINDOW * (P.win_rate_pm / 1000.0)) > P.k_cap || P.accept_err_pm < 0 || P.accept_err_pm > 1000 ||
         P.w_later < 0 || P.w_later > 64)
         return fsv_fail(ctx, FSV_EINVAL, "fsv_asm_params error model out of range (k_cap <= 95, 375 x win_rate_pm / 1000 <= k_cap)");
+    if (P.kmer_filter && !P.kmer_table)
+        return fsv_fail(ctx, FSV_EINVAL, "kmer_filter = 1 needs kmer_table = 1: the filter is the list the k-mer count table stage leaves");
     if (P.partial_charge && P.k_cap > FSV_K_MAX)
         return fsv_fail(ctx, FSV_EINVAL, "partial_charge needs k_cap <= 31 (FSV_K_MAX): the charge is not restated for the wide-band profiles");
     return FSV_OK;
@@ -1647,6 +1761,7 @@ static int fsv_assemble_batch_impl(fsv_ctx *ctx, const fsv_readsets *sets, const
     out->n_contigs = 0; out->off[0] = 0;
     // what the k-mer count table stage leaves on the context belongs to this call from here on (its chunks add to it)
     W.km_last.clear(); W.km_last_flt_off.assign(1, 0); W.km_last_flt = nullptr; W.km_ms = 0; W.km_valid = false;
+    W.flt = SketchFilter{}; W.ki_last.clear(); W.ki_ms = 0; W.ki_valid = false;
     W.charge_last = fsv_charge_stats{}; W.charge_valid = false;
     for (auto e : W.charge_ev) (void)hipEventDestroy(e);     // (left by a call that failed half-way)
     W.charge_ev.clear();
@@ -1675,9 +1790,10 @@ static int fsv_assemble_batch_impl(fsv_ctx *ctx, const fsv_readsets *sets, const
     {
         uint64_t tk = 0, pr = 0, bs = 0, km = 0;
         for (uint32_t s = 0; s < sets->n_sets; s++) {
-            uint64_t t1, p1, b1, k1;
-            set_cost(sets, s, t1, p1, b1, k1);
+            uint64_t t1, p1, b1, k1, f1;
+            set_cost(sets, s, t1, p1, b1, k1, f1);
             if (!P.kmer_table) k1 = 0;
+            if (P.kmer_filter) k1 += f1;
             if (t1 >= (1ull << 31) || p1 >= (1ull << 31) || b1 + b1 / 4 >= (1ull << 32)) return fsv_fail(ctx, FSV_EUNSUP, "a single read set exceeds the 2^31 window-task / pair bound");
             const bool over = tk + t1 >= (1ull << 31) || pr + p1 >= (1ull << 31) || (bs + b1) + (bs + b1) / 4 >= (1ull << 32) ||     /* minimizer slots: one per base + slack, 32-bit offsets */
                               (double)(tk + t1) * (P.second_round ? 400.0 : 200.0) + (double)(pr + p1) * 200.0 + (double)(bs + b1) * (P.second_round ? 52.0 : 48.0) +
@@ -1687,7 +1803,7 @@ static int fsv_assemble_batch_impl(fsv_ctx *ctx, const fsv_readsets *sets, const
         }
         cut.push_back(sets->n_sets);
     }
-    if (cut.size() == 2) { TRY(assemble_chunk(ctx, sets, P, out)); W.km_valid = P.kmer_table != 0; W.charge_valid = P.partial_charge != 0; return FSV_OK; }
+    if (cut.size() == 2) { TRY(assemble_chunk(ctx, sets, P, out)); W.km_valid = P.kmer_table != 0; W.ki_valid = P.kmer_filter != 0; W.charge_valid = P.partial_charge != 0; return FSV_OK; }
     fsv_asm_stats total; memset(&total, 0, sizeof(total));
     uint64_t used = 0; uint32_t nc = 0;
     std::vector<uint64_t> all_off{0};
@@ -1740,6 +1856,7 @@ static int fsv_assemble_batch_impl(fsv_ctx *ctx, const fsv_readsets *sets, const
     out->n_contigs = nc;
     W.stats = total;
     W.km_valid = P.kmer_table != 0;
+    W.ki_valid = P.kmer_filter != 0;
     W.charge_valid = P.partial_charge != 0;
     W.n_reads = 0; W.cur_store = nullptr;        // fsv_asm_fetch_reads serves single-pass batches only
     ctx->last_contigs_dev = nc ? W.contig_all.p : nullptr;
@@ -1765,10 +1882,19 @@ static int fsv_asm_fetch_reads_impl(fsv_ctx *ctx, char *seq, uint64_t seq_cap, u
     return fsv_d2h(ctx, seq, d_out.p, o[n_reads]);
 }
 
+// flt_hash / flt_off: fsv_sketch_reads_filtered's per-set lists, or null (fsv_sketch_reads, or a caller without lists)
 static int fsv_sketch_reads_impl(fsv_ctx *ctx, const fsv_readsets *sets, int32_t w, int32_t k, int32_t hpc, int32_t variant, fsv_mz *out_mz,
-                                uint64_t out_cap, uint64_t *out_off)
+                                uint64_t out_cap, uint64_t *out_off, const uint64_t *flt_hash = nullptr, const uint64_t *flt_off = nullptr)
 {
     if (!ctx || !sets || !sets->store_dev || !sets->word_off || !sets->read_len || !out_mz || !out_off) return FSV_EINVAL;
+    if (flt_hash) {
+        if (!flt_off || !sets->set_start) return fsv_fail(ctx, FSV_EINVAL, "fsv_sketch_reads_filtered: flt_hash goes with flt_off and set_start");
+        TRY(check_set_start(ctx, sets));
+        if (flt_off[0] != 0) return fsv_fail(ctx, FSV_EINVAL, "fsv_sketch_reads_filtered: flt_off starts at 0");
+        for (uint32_t s = 0; s < sets->n_sets; s++) if (flt_off[s + 1] < flt_off[s]) return fsv_fail(ctx, FSV_EINVAL, "fsv_sketch_reads_filtered: flt_off not monotone");
+        for (uint64_t i = 0; i < flt_off[sets->n_sets]; i++)
+            if (flt_hash[i] == FSV_KMER_EMPTY) return fsv_fail(ctx, FSV_EINVAL, "fsv_sketch_reads_filtered: UINT64_MAX is the dummy hash, not a k-mer");
+    }
     if (k < 1 || k > 63 || w < 1) return fsv_fail(ctx, FSV_EINVAL, "1 <= k <= 63, 1 <= w");
     // the position-parallel kernel's LDS tile holds w <= 255 (as the aligner uses it); the replay kernel keeps w deque slots per lane
     if ((k & 1) && variant != 1) { if (w > 255) return fsv_fail(ctx, FSV_EINVAL, "w <= 255 (position-parallel kernel: odd k, variant 0)"); }
@@ -1793,8 +1919,17 @@ static int fsv_sketch_reads_impl(fsv_ctx *ctx, const fsv_readsets *sets, int32_t
     TRY(zero(ctx, W.warn, B.n_reads));
     TRY(ensure(ctx, W.mz, G.mz_off[B.n_reads]));
     TRY(ensure(ctx, W.mz_cnt, B.n_reads));
+    W.flt = SketchFilter{};
+    if (flt_hash && flt_off[sets->n_sets]) {    // the caller's lists -> the filter sets, as kmer_stage_of_chunk builds them from the stage's list
+        const std::vector<uint64_t> list_off(flt_off, flt_off + sets->n_sets + 1);
+        TRY(ensure(ctx, W.fs_list, list_off.back()));
+        FSV_HIP(ctx, hipMemcpyAsync(W.fs_list.p, flt_hash, list_off.back() * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
+        TRY(build_filter_sets(ctx, W, sets, W.fs_list.p, list_off, nullptr, nullptr));
+    }
+    const SketchFilter flt = W.flt;
+    W.flt = SketchFilter{};
     // variant 1: the replay kernel for an odd k as well (by itself the launch picks the kernel by the parity of k)
-    TRY(launch_sketch(ctx, W, SketchJob{sets->store_dev, B.n_reads, G.word_off[B.n_reads], G.max_words, w, k, hpc, nullptr, w, variant == 1, nullptr}));
+    TRY(launch_sketch(ctx, W, SketchJob{sets->store_dev, B.n_reads, G.word_off[B.n_reads], G.max_words, w, k, hpc, nullptr, w, variant == 1, nullptr, flt}));
     std::vector<uint32_t> cnt(B.n_reads);
     TRY(download(ctx, cnt.data(), W.mz_cnt, B.n_reads));
     FSV_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -1832,6 +1967,7 @@ static int fsv_asm_overlaps_impl(fsv_ctx *ctx, const fsv_readsets *sets, const f
     memset(&W.stats, 0, sizeof(W.stats));
     W.kt.reset();
     W.n_reads = 0; W.cur_store = nullptr;     // (nothing here for fsv_asm_fetch_reads)
+    W.flt = SketchFilter{};                   // (the hook runs no k-mer count table stage: kmer_filter finds nothing to take)
     Round R(P);
     TRY(prepare_batch(ctx, W, sets, R));
     const Batch &B = R.B;
@@ -1883,6 +2019,23 @@ extern "C" int fsv_sketch_reads(fsv_ctx *ctx, const fsv_readsets *sets, int32_t 
                                 uint64_t out_cap, uint64_t *out_off)
 {
     FSV_GUARD(ctx, fsv_sketch_reads_impl(ctx, sets, w, k, hpc, variant, out_mz, out_cap, out_off));
+}
+
+extern "C" int fsv_sketch_reads_filtered(fsv_ctx *ctx, const fsv_readsets *sets, int32_t w, int32_t k, int32_t hpc, int32_t variant, fsv_mz *out_mz,
+                                        uint64_t out_cap, uint64_t *out_off, const uint64_t *flt_hash, const uint64_t *flt_off)
+{
+    FSV_GUARD(ctx, fsv_sketch_reads_impl(ctx, sets, w, k, hpc, variant, out_mz, out_cap, out_off, flt_hash, flt_off));
+}
+
+extern "C" int fsv_kmer_index(fsv_ctx *ctx, const fsv_readsets *sets, int32_t w, int32_t k, int32_t hpc, fsv_kmer_set *table, fsv_kmer_index_set *index,
+                              uint64_t *hist)
+{
+    FSV_GUARD(ctx, fsv_kmer_index_impl(ctx, sets, w, k, hpc, table, index, hist));
+}
+
+extern "C" int fsv_asm_last_kmer_index(const fsv_ctx *ctx, fsv_kmer_index_set *out, uint32_t n_sets, double *ms)
+{
+    FSV_GUARD((fsv_ctx *)nullptr, fsv_asm_last_kmer_index_impl(ctx, out, n_sets, ms));
 }
 
 extern "C" int fsv_kmer_peaks(const int64_t *hist, int32_t n_cnt, int32_t start_cnt, int32_t *peak_het, int32_t *low_i, int32_t *max_i)

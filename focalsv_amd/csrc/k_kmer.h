@@ -63,7 +63,9 @@ FSV_KMER_HD inline int fsv_kmer_cutoff(int peak_hom)
 #if defined(__HIPCC__)
 #include "fsv_internal.h"
 
-#define FSV_KMER_EMPTY (~0ull)     // no key: hifiasm's dummy hash, which the sketch never emits
+#ifndef FSV_KMER_EMPTY
+#define FSV_KMER_EMPTY (~0ull)     // no key: hifiasm's dummy hash, which the sketch never emits (k_sketch.h has the same line)
+#endif
 #define FSV_KMER_MIN_SLOTS 1024u   // smallest table
 #define FSV_KMER_TILE 4096u        // slots a block of k_kmer_hist / k_kmer_filter walks
 #define FSV_KMER_E_FULL 1u         // error flags: a table had no free slot; a filter segment was too short
@@ -149,6 +151,42 @@ __global__ __launch_bounds__(256) void k_kmer_filter(const KmerTile *__restrict_
         const uint32_t o = atomicAdd(&cursor[t.set], 1u);
         if (o < seg_len) flt[seg + o] = key; else atomicOr(err, FSV_KMER_E_FLT);
     }
+}
+
+// slots of a set's filter set (what the sketch kernels probe, k_sketch.h): a power of two, at least twice its filtered keys; none
+// for a set with an empty filter, whose reads then probe nothing
+inline uint64_t flt_set_slots(uint64_t keys)
+{
+    if (keys == 0) return 0;
+    uint64_t n = 2;
+    while (n < 2 * keys) n <<= 1;
+    return n;
+}
+
+// One thread per key of the sets' filter lists (flt, segments [flt_off[s], flt_off[s + 1]), any order, duplicates allowed): the key is
+// claimed in its set's slots [set_off[s], set_off[s + 1]) of `keys` -- all FSV_KMER_EMPTY before the launch -- as k_kmer_insert claims
+// one: linear probing from the same bits, a 64-bit compare-and-swap against the empty value.  The probe is bounded by the set's size;
+// a set that ran full (the host sized it wrongly) or a list that holds the empty value raises FSV_KMER_E_FULL.  A set whose slot range
+// is empty while its list is not is one the host leaves unfiltered: its keys are passed over.
+__global__ __launch_bounds__(256) void k_flt_build(const unsigned long long *__restrict__ flt, const uint64_t *__restrict__ flt_off,
+                                                   const uint64_t *__restrict__ set_off, uint32_t n_sets, unsigned long long *keys, uint32_t *err)
+{
+    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= flt_off[n_sets]) return;
+    uint32_t lo = 0, hi = n_sets;              // the set whose segment holds key i: the last s with flt_off[s] <= i
+    while (hi - lo > 1) { const uint32_t mid = lo + (hi - lo) / 2; if (flt_off[mid] <= i) lo = mid; else hi = mid; }
+    const uint64_t base = set_off[lo], size = set_off[lo + 1] - base, mask = size - 1;
+    const unsigned long long h = flt[i];
+    if (size == 0) return;                    // a set the host gave no slots (left unfiltered) takes no keys
+    if (h == FSV_KMER_EMPTY) { atomicOr(err, FSV_KMER_E_FULL); return; }
+    uint64_t slot = (h ^ (h >> 29)) & mask;
+    for (uint64_t probe = 0; probe < size; probe++) {
+        unsigned long long cur = keys[base + slot];
+        if (cur == FSV_KMER_EMPTY) { cur = atomicCAS(&keys[base + slot], FSV_KMER_EMPTY, h); if (cur == FSV_KMER_EMPTY) cur = h; }
+        if (cur == h) return;
+        slot = (slot + 1) & mask;
+    }
+    atomicOr(err, FSV_KMER_E_FULL);
 }
 
 } // namespace

@@ -21,6 +21,34 @@ __device__ __forceinline__ uint64_t mix64(uint64_t key)
     return key;
 }
 
+// ------------------------------------------------------------------------------------------------ the high-count k-mer filter
+// hifiasm's ha_ft_isflt inside ha_sketch (sketch.cpp:89): an entry whose hash is in its read set's filter set is the dummy entry -- it
+// keeps its slot in the window and is never a candidate.  One open-addressed set of 8-byte keys per read set, back to back in HBM
+// (k_flt_build, k_kmer.h): set s owns slots [off[s], off[s + 1]), a power of two or none; a free slot holds FSV_KMER_EMPTY; linear
+// probing from the bits k_kmer_insert starts at.  The filter is a template parameter of the two sketch kernels: without it the view
+// is an empty struct and the kernels are the code they were.
+#ifndef FSV_KMER_EMPTY
+#define FSV_KMER_EMPTY (~0ull)     // no key: hifiasm's dummy hash, which the sketch never emits
+#endif
+template <bool FLT> struct FltView {};
+template <> struct FltView<true> { const unsigned long long *keys; const uint64_t *off; const uint32_t *read_set; };
+struct SketchFilter { const unsigned long long *keys = nullptr; const uint64_t *off = nullptr; const uint32_t *read_set = nullptr; };   // host side; keys == nullptr: no filter
+
+// is h a key of the set in slots [base, base + size), size a power of two?  The sets are at most half full, so a probe ends at a free
+// slot after a step or two; it is bounded by the set's size all the same.
+__device__ __forceinline__ bool flt_has(const unsigned long long *__restrict__ keys, uint64_t base, uint64_t size, uint64_t h)
+{
+    const uint64_t mask = size - 1;
+    uint64_t slot = (h ^ (h >> 29)) & mask;
+    for (uint64_t probe = 0; probe < size; probe++) {
+        const unsigned long long cur = keys[base + slot];
+        if (cur == h) return true;
+        if (cur == FSV_KMER_EMPTY) return false;
+        slot = (slot + 1) & mask;
+    }
+    return false;
+}
+
 // One wavefront per read.  The minimizer recurrence is sequential, but what it emits at a position only depends on
 // the w entries around it (and on the k HPC bases behind them), so every lane replays the recurrence over its own 1/64
 // of the read plus a warm-up of w+k+4 homopolymer runs in front and w+2 runs behind, and keeps only the minimizers whose
@@ -43,11 +71,12 @@ struct WordCache { // sequential base access through one cached 16-base word
     __device__ __forceinline__ uint32_t get(int i) { const int wi = i >> 4; if (wi != idx) { w = p[wi]; idx = wi; } return (w >> ((i & 15) << 1)) & 3u; }
 };
 
+template <bool FLT>
 __global__ __launch_bounds__(64) void k_sketch(const uint32_t *__restrict__ store, const uint32_t *__restrict__ word_off,
                                                const int32_t *__restrict__ read_len, const uint32_t *__restrict__ mz_off,
                                                fsv_mz *__restrict__ mz, uint32_t *__restrict__ mz_cnt, uint32_t n_reads, int w, int k,
                                                int hpc, uint32_t *__restrict__ warn, const uint8_t *__restrict__ w_per_read, int w_max,
-                                               uint32_t lds_words)
+                                               uint32_t lds_words, const FltView<FLT> F)
 {
     extern __shared__ __attribute__((aligned(16))) uint8_t s_dyn[];
     const int lane = threadIdx.x;
@@ -58,6 +87,8 @@ __global__ __launch_bounds__(64) void k_sketch(const uint32_t *__restrict__ stor
     const uint32_t cap = mz_off[r + 1] - mz_off[r];
     fsv_mz *out = mz + mz_off[r];
     if (w_per_read) w = w_per_read[r];
+    [[maybe_unused]] uint64_t fbase = 0, fsize = 0;   // the read set's filter set (no slots: no probe)
+    if constexpr (FLT) { const uint32_t fs = F.read_set[r]; fbase = F.off[fs]; fsize = F.off[fs + 1] - fbase; }
     uint64_t *d_hash = (uint64_t *)s_dyn;                               // [w_max][64]
     uint32_t *s_words = (uint32_t *)(d_hash + (size_t)w_max * 64);      // [lds_words]
     uint32_t *d_ps = s_words + lds_words;                               // [w_max][64]   pos << 8 | span
@@ -138,6 +169,7 @@ __global__ __launch_bounds__(64) void k_sketch(const uint32_t *__restrict__ stor
             cur_h = z ? mix64(km2) + mix64(km3) : mix64(km0) + mix64(km1);
             cur_ps = ((uint32_t)i << 8) | (uint32_t)span;
             cur_rev = (uint32_t)z;
+            if constexpr (FLT) if (fsize && flt_has(F.keys, fbase, fsize, cur_h)) { cur_h = NONE; cur_ps = 0; cur_rev = 0; }   // a filtered k-mer: the dummy, in its slot
         }
         const int tcur = l & 0x3fff; // entry time, modulo 2^14 (windows are at most 64 entries long)
         // expire what has left the window of the last w entries
@@ -326,12 +358,13 @@ __global__ __launch_bounds__(256) void k_uniq_walk(fsv_mz *__restrict__ mz, cons
 // Equivalent to the monotone-deque replay in k_sketch (which stays for even k); both are checked against the oracle.
 #define SKF_T 1024
 #define SKF_V ((SKF_T + 2 * 256 + 255) / 256)   // elements of the doubling passes per thread
+template <bool FLT>
 __global__ __launch_bounds__(256) void k_sketch_fast(const uint32_t *__restrict__ store, const uint32_t *__restrict__ word_off,
                                                      const int32_t *__restrict__ read_len, const uint32_t *__restrict__ mz_off,
                                                      fsv_mz *__restrict__ mz, uint32_t *__restrict__ mz_cnt, uint32_t n_reads, int w, int k,
                                                      int hpc, uint32_t *__restrict__ warn, const uint8_t *__restrict__ w_per_read,
                                                      uint32_t *__restrict__ sc_ends, uint32_t *__restrict__ sc_low, uint32_t *__restrict__ sc_high,
-                                                     const uint32_t *__restrict__ only_changed)
+                                                     const uint32_t *__restrict__ only_changed, const FltView<FLT> F)
 {
     __shared__ uint64_t s_h[SKF_T + 2 * 256];   // w <= 255
     __shared__ uint64_t s_wmin[SKF_T + 2 * 256];
@@ -349,6 +382,8 @@ __global__ __launch_bounds__(256) void k_sketch_fast(const uint32_t *__restrict_
     const uint32_t cap = mz_off[r + 1] - mz_off[r];
     fsv_mz *out = mz + mz_off[r];
     if (w_per_read) w = w_per_read[r];
+    [[maybe_unused]] uint64_t fbase = 0, fsize = 0;   // the read set's filter set (no slots: no probe)
+    if constexpr (FLT) { const uint32_t fs = F.read_set[r]; fbase = F.off[fs]; fsize = F.off[fs + 1] - fbase; }
     if (tid == 0) mz_cnt[r] = 0;   // (the first emit comes after several barriers)
     uint32_t *ends = sc_ends + (size_t)woff * 16;          // entry -> index of the run's last base
     uint32_t *low = sc_low + woff + r, *high = sc_high + woff + r; // bit planes of the compressed bases (zeroed by the host)
@@ -426,7 +461,11 @@ __global__ __launch_bounds__(256) void k_sketch_fast(const uint32_t *__restrict_
         const uint64_t r0 = ~lo & kmask, r1 = ~hi & kmask;
         const int z = f1 < r1 ? 0 : 1;
         if (z_out) *z_out = z;
-        return mix64(z ? r0 : f0) + mix64(z ? r1 : f1);   // the strand is chosen first: two hashes per entry, not four
+        const uint64_t h = mix64(z ? r0 : f0) + mix64(z ? r1 : f1);   // the strand is chosen first: two hashes per entry, not four
+        // a filtered k-mer is the dummy, in its slot.  The probe's first load goes out as soon as the hash exists and hits a set of a few
+        // KB that every block of the read set walks (L2); emit() comes through here too, so what it writes has passed the filter
+        if constexpr (FLT) if (fsize && flt_has(F.keys, fbase, fsize, h)) return NONE;
+        return h;
     };
     auto emit = [&](int p) {
         int z = 0;
@@ -524,6 +563,7 @@ struct SketchJob {
     int w, k, hpc; const uint8_t *wper; int w_max;        // a window per read (or null) and the largest of them
     bool replay;                                          // k_sketch for an odd k as well
     const uint32_t *only_changed;                         // odd k: reads with a zero here keep their list and their count
+    SketchFilter flt = {};                                // the read sets' filter sets, or nothing (the aligner, fsv_sketch_reads)
 };
 template <class Ws> int launch_sketch(fsv_ctx *ctx, Ws &W, const SketchJob &J)
 {
@@ -536,14 +576,24 @@ template <class Ws> int launch_sketch(fsv_ctx *ctx, Ws &W, const SketchJob &J)
         TRY(ensure_each(ctx, plane, W.sk_low, W.sk_high));
         TRY(zero(ctx, W.sk_low, plane));
         TRY(zero(ctx, W.sk_high, plane));
-        FSV_LAUNCH(ctx, ctx->stream, k_sketch_fast, dim3(J.n_reads), dim3(256), 0, J.store, W.word_off.p, W.len.p, W.mz_off.p, W.mz.p, W.mz_cnt.p,
-                   J.n_reads, J.w, J.k, J.hpc, W.warn.p, J.wper, W.sk_ends.p, W.sk_low.p, W.sk_high.p, J.only_changed);
+        if (J.flt.keys)
+            FSV_LAUNCH(ctx, ctx->stream, k_sketch_fast<true>, dim3(J.n_reads), dim3(256), 0, J.store, W.word_off.p, W.len.p, W.mz_off.p, W.mz.p, W.mz_cnt.p,
+                       J.n_reads, J.w, J.k, J.hpc, W.warn.p, J.wper, W.sk_ends.p, W.sk_low.p, W.sk_high.p, J.only_changed, FltView<true>{J.flt.keys, J.flt.off, J.flt.read_set});
+        else
+            FSV_LAUNCH(ctx, ctx->stream, k_sketch_fast<false>, dim3(J.n_reads), dim3(256), 0, J.store, W.word_off.p, W.len.p, W.mz_off.p, W.mz.p, W.mz_cnt.p,
+                       J.n_reads, J.w, J.k, J.hpc, W.warn.p, J.wper, W.sk_ends.p, W.sk_low.p, W.sk_high.p, J.only_changed, FltView<false>{});
     } else {
         const uint32_t lds_words = J.max_words < 8192u ? J.max_words : 8192u;
         const size_t lds = sketch_lds_bytes(J.w_max, lds_words);
-        FSV_HIP(ctx, hipFuncSetAttribute((const void *)k_sketch, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        FSV_LAUNCH(ctx, ctx->stream, k_sketch, dim3(J.n_reads), dim3(64), lds, J.store, W.word_off.p, W.len.p, W.mz_off.p, W.mz.p, W.mz_cnt.p,
-                   J.n_reads, J.w, J.k, J.hpc, W.warn.p, J.wper, J.w_max, lds_words);
+        if (J.flt.keys) {
+            FSV_HIP(ctx, hipFuncSetAttribute((const void *)k_sketch<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            FSV_LAUNCH(ctx, ctx->stream, k_sketch<true>, dim3(J.n_reads), dim3(64), lds, J.store, W.word_off.p, W.len.p, W.mz_off.p, W.mz.p, W.mz_cnt.p,
+                       J.n_reads, J.w, J.k, J.hpc, W.warn.p, J.wper, J.w_max, lds_words, FltView<true>{J.flt.keys, J.flt.off, J.flt.read_set});
+        } else {
+            FSV_HIP(ctx, hipFuncSetAttribute((const void *)k_sketch<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            FSV_LAUNCH(ctx, ctx->stream, k_sketch<false>, dim3(J.n_reads), dim3(64), lds, J.store, W.word_off.p, W.len.p, W.mz_off.p, W.mz.p, W.mz_cnt.p,
+                       J.n_reads, J.w, J.k, J.hpc, W.warn.p, J.wper, J.w_max, lds_words, FltView<false>{});
+        }
     }
     return FSV_OK;
 }

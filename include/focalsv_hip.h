@@ -178,6 +178,12 @@ typedef struct fsv_asm_params {
                                * for every set that is not flagged FSV_SET_UNPHASED; 0: best-buddy chains (ONT profile, unphased sets) */
     int32_t junction_cigars;  /* 1 (default): the haplotype partition reads the ~50 columns on each side of a window junction off the re-aligned
                                * junction cigar, as hifiasm does (calculate_boundary_cigars, Correct.cpp:2310; markSNP_advance :5054); 0: window cigars */
+    int32_t kmer_filter;      /* 0 (default in all three profiles): off.  1 (needs kmer_table = 1, else FSV_EINVAL): hifiasm's high-count k-mer filter in
+                               * every sketch of the assembly (ha_ft_isflt in ha_sketch, sketch.cpp:89; every round and the final pass take the one
+                               * filter of the raw reads): a k-mer on its set's filter list keeps its slot in the window but is no candidate.  Sets
+                               * flagged FSV_W_LOW_COV are left alone as with kmer_table alone.  The figures of hifiasm's first ha_pt_gen on the
+                               * filtered sketch stay on the context: fsv_asm_last_kmer_index.  (In front of kmer_table: the struct ends with
+                               * kmer_table, partial_charge, which tests/test_partial_charge_abi.py pins.) */
     int32_t kmer_table;       /* 0 (default in all three profiles): off.  1: hifiasm's k-mer count table per read set before round 0 (ha_ft_gen, htab.cpp:917;
                                * see fsv_kmer_table) at (w = 1, k, hpc) -- a set whose count histogram has no coverage peak is left as hifiasm leaves
                                * it: reads uncorrected, no contig, FSV_W_LOW_COV | FSV_W_NO_LAYOUT; every other set is assembled as with 0 */
@@ -309,6 +315,15 @@ int fsv_asm_overlaps(fsv_ctx *ctx, const fsv_readsets *sets, const fsv_asm_param
 int fsv_sketch_reads(fsv_ctx *ctx, const fsv_readsets *sets, int32_t w, int32_t k, int32_t hpc, int32_t variant,
                      fsv_mz *out_mz, uint64_t out_cap, uint64_t *out_off);
 
+/* The same through the sets' high-count k-mer filters (ha_sketch with hf != 0, sketch.cpp:89) -- the stage hook of kmer_filter = 1: the
+ * filter sets are built from the caller's lists by the launch code fsv_assemble_batch runs, and every read of set s (sets->set_start, sets->n_sets)
+ * is sketched against list s = flt_hash[flt_off[s] .. flt_off[s + 1]) (n_sets + 1 offsets from 0), as fsv_kmer_table hands them out.  A listed
+ * k-mer keeps its slot in the window and is never reported; a window of listed k-mers reports nothing.  The lists need not be sorted and may
+ * repeat a hash; UINT64_MAX in a list is FSV_EINVAL.  flt_hash == NULL, or lists that are all empty: the bytes of fsv_sketch_reads.  The
+ * (w, k, variant) limits are those of fsv_sketch_reads. */
+int fsv_sketch_reads_filtered(fsv_ctx *ctx, const fsv_readsets *sets, int32_t w, int32_t k, int32_t hpc, int32_t variant,
+                              fsv_mz *out_mz, uint64_t out_cap, uint64_t *out_off, const uint64_t *flt_hash, const uint64_t *flt_off);
+
 /* ---- k-mer count table of a read set (ha_ft_gen / ha_analyze_count, htab.cpp:917-950, hist.cpp:15-96) ----------
  * Keys: the 64-bit hash of every entry the sketch emits for (w, k, hpc) -- with w = 1 every k-mer ha_sketch accepts, both strands
  * counted together.  Count: occurrences over all reads of the set, saturating at 4095.  hist[c]: distinct keys with count c. */
@@ -331,6 +346,24 @@ int fsv_kmer_table(fsv_ctx *ctx, const fsv_readsets *sets, int32_t w, int32_t k,
 /* verdicts of the last fsv_assemble_batch with kmer_table = 1 on this context, all chunks, in set order (n_sets: that call's; FSV_EINVAL
  * otherwise, or when that call ran with kmer_table = 0); ms: the stage's summed kernel time */
 int fsv_asm_last_kmer_table(const fsv_ctx *ctx, fsv_kmer_set *out, uint32_t n_sets, double *ms);
+
+/* ---- the minimizer index figures of a read set (hifiasm's first ha_pt_gen, htab.cpp:952-998) ----------
+ * The count table at (w = 1, k, hpc), its filter list, the sketch at (w, k, hpc) through that filter, and the count table's kernels on what
+ * that sketch emits. */
+typedef struct fsv_kmer_index_set {     /* one read set */
+    uint64_t n_entries, n_distinct;     /* entries of the filtered sketch; distinct minimizers (hifiasm: "counted") */
+    uint64_t n_indexed;                 /* sum of c x hist[c], c = 2..4094 (hifiasm: "indexed" positions) */
+    int32_t  low_i, max_i;              /* the histogram's lowest point and highest peak (-1: none) */
+    int32_t  peak_hom, peak_het;        /* peak_hom: hifiasm's hom_cov from round 0 on; -1: none */
+} fsv_kmer_index_set;                   /* 40 bytes */
+/* per-set on the caller's read sets; (w, k) as fsv_kmer_table takes them.  table / index: n_sets records each; hist: the index histograms,
+ * n_sets x 4096 uint64, or NULL.  A set without a peak in its table has cutoff -5: every k-mer is filtered and its index is that of nothing
+ * (counts 0, no peak), as hifiasm logs. */
+int fsv_kmer_index(fsv_ctx *ctx, const fsv_readsets *sets, int32_t w, int32_t k, int32_t hpc,
+                   fsv_kmer_set *table, fsv_kmer_index_set *index, uint64_t *hist);
+/* the index figures of round 0 of the last fsv_assemble_batch with kmer_filter = 1 on this context, all chunks, in set order (n_sets: that
+ * call's; FSV_EINVAL otherwise, or when that call ran with kmer_filter = 0); ms: the summed kernel time of the filter-set build and the index */
+int fsv_asm_last_kmer_index(const fsv_ctx *ctx, fsv_kmer_index_set *out, uint32_t n_sets, double *ms);
 
 /* ---- partial charge of unmatched windows (non_trim_error_rate, Correct.cpp:725-845; fsv_asm_params.partial_charge) ----------
  * The extension alignment (Reserve_Banded_BPM_Extension, Levenshtein_distance.h:14-205): K5's recurrence, and after every column the

@@ -18,6 +18,9 @@ parser.add_argument('--data_type', '-d', type=int, help="HIFI = 0 or CLR = 1 dat
 parser.add_argument('--device', type=int, default=0, help="GPU index (extension)")
 parser.add_argument('--kmer-table', action='store_true',
                     help="hifiasm's k-mer count table per read set first: a set without a coverage peak yields no contig, as in hifiasm (extension; default off)")
+parser.add_argument('--kmer-filter', action='store_true',
+                    help="hifiasm's high-count k-mer filter in every minimizer sketch: a k-mer that occurs 5 x the coverage peak times or more in its "
+                         "read set is no minimizer candidate (implies --kmer-table; extension; default off)")
 parser.add_argument('--partial-charge', action='store_true',
                     help="hifiasm's non_trim_error_rate: an unmatched window beside a matched one is charged what two extension alignments leave "
                          "uncovered, not its whole length (HiFi only; extension; default off)")
@@ -28,8 +31,8 @@ if __name__ == "__main__":
     logger.info("Starting assembly process (MI355X)")
     if args.data_type != 0:
         logger.warning("CLR/ONT read sets go through the same GPU assembler (the reference uses Flye/Shasta there)")
-    st = assembly(args.out_dir, args.num_cpus, args.num_threads, args.data_type, logger, device=args.device, kmer_table=args.kmer_table,
-                  partial_charge=args.partial_charge)
+    st = assembly(args.out_dir, args.num_cpus, args.num_threads, args.data_type, logger, device=args.device, kmer_table=args.kmer_table or args.kmer_filter,
+                  partial_charge=args.partial_charge, kmer_filter=args.kmer_filter)
     bad = {k: v for k, v in st.items() if v}
     if bad:
         logger.warning(f"read sets with a non-zero status: {bad}")
