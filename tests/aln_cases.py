@@ -173,6 +173,49 @@ def cigar_head_cases():
     return out
 
 
+# the planted blocks of dp_class_cases as (reference bases, contig bases): what each event's DP covers at the least
+DP_CLASS_BLOCKS = ((100, 0), (1000, 1200), (5000, 600), (3300, 3500), (0, 2000))
+
+
+def _unlike(rng, n, x):
+    """n random bases to replace the block x with nothing to pair at the junctions.  The alignment is the new bases as an insertion,
+    then x as a deletion; a first or last base like x's, or a tail that is a head of x, would pair there for free and shorten both."""
+    while True:
+        y = rnd(rng, n)
+        if y[0] != x[0] and y[-1] != x[-1] and not any(y[-k:] == x[:k] for k in range(1, 33)):
+            return y
+
+
+def dp_class_cases():
+    """one contig, forward and reverse-complemented, whose five events between unique flanks of 6-8 kb take the four kernels of the
+    event DP (aln.hip: nw_class) in one batch: a 100-base deletion (class 0: a short query), 1 000 reference bases replaced by 1 200
+    unrelated ones (class 1), 5 000 replaced by 600 (class 1 with more than 4 096 target bases: its ring wraps), 3 300 replaced by
+    3 500 (class 2: a query above 3 072, about 12 M cells, below max_cells) and a 2 000-base insertion (class 3: a short target
+    side).  A replacement comes out as an insertion next to a deletion; the new bases are drawn so that nothing pairs at its junctions, so
+    both have the planted lengths."""
+    rng = np.random.default_rng(49)
+    F = [rnd(rng, n) for n in (6000, 7000, 8000, 6500, 7500, 6700)]
+    X = [rnd(rng, n) for n, _ in DP_CLASS_BLOCKS[:4]]
+    Y = [b""] + [_unlike(rng, m, x) for (_, m), x in zip(DP_CLASS_BLOCKS[1:4], X[1:])]
+    ins = rnd(rng, DP_CLASS_BLOCKS[4][1])
+    ref = F[0] + X[0] + F[1] + X[1] + F[2] + X[2] + F[3] + X[3] + F[4] + F[5]
+    hap = F[0] + F[1] + Y[1] + F[2] + Y[2] + F[3] + Y[3] + F[4] + ins + F[5]
+    truth, rpos, hpos = [], 0, 0
+    for k in range(4):
+        rpos += len(F[k])
+        hpos += len(F[k])
+        if Y[k]:
+            truth.append(("INS", left_ins(hap, hpos, len(Y[k]), rpos), len(Y[k])))
+        # a deletion behind its insertion has no M run in front to move through: it stays at the block's first base
+        truth.append(("DEL", rpos if Y[k] else left_del(ref, rpos, len(X[k])), len(X[k])))
+        rpos += len(X[k])
+        hpos += len(Y[k])
+    rpos += len(F[4])
+    hpos += len(F[4])
+    truth.append(("INS", left_ins(hap, hpos, len(ins), rpos), len(ins)))
+    return [Case("dp-classes-+", ref, hap, truth, strands=[0]), Case("dp-classes--", ref, synth.revcomp(hap), truth, strands=[1])]
+
+
 def check_case(case, recs):
     """recs: the records of the contig (dicts with ref_start, rev, cigar): every planted SV within 1 bp with its exact length,
     nothing else; the expected number of records and their strands"""

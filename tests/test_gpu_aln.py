@@ -235,3 +235,25 @@ def test_mixed_seed_windows_in_one_batch(ctx):
         for (c, g), got in zip(cases, by):
             A.check_case(c, got)
             _same_records(got, O.align_contig_multi(c.hap, c.ref, po), (k, c.name))
+
+
+def test_all_four_dp_lanes_in_one_batch(ctx):
+    """aln_cases.dp_class_cases, both strands, next to two contigs of cigar_head_cases in ONE fsv_align_batch call: run_nw has
+    tasks in all four size classes at once -- class 0 on the context's stream, the others forked onto the side streams and joined --
+    and every task's out_idx / cg_off / bt_off must survive the reordering by class.  Records bit-identical to the oracle's;
+    no event went round the DP as a box (n_boxes == 0), and dp_cells holds at least the planted blocks of both strands."""
+    from tests import aln_cases as A
+    heads = A.cigar_head_cases()
+    cases = A.dp_class_cases() + [heads[2], heads[8]]
+    refs = [cases[0].ref, heads[0].ref]
+    assert cases[1].ref == refs[0] and heads[2].ref == heads[8].ref == refs[1]
+    rec, cigar, status = ctx.align_batch([c.hap for c in cases], [0, 0, 1, 1], refs)
+    assert list(status) == [0, 0, 0, 0]
+    by = _records_by_contig(rec, cigar, len(cases))
+    for c, got in zip(cases, by):
+        _same_records(got, O.align_contig_multi(c.hap, c.ref), c.name)
+    for c, got in zip(cases[:2], by):
+        A.check_case(c, got)
+    st = ctx.aln_stats()
+    assert st["n_boxes"] == 0
+    assert st["dp_cells"] >= 2 * sum(t * q for t, q in A.DP_CLASS_BLOCKS), st

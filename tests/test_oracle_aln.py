@@ -176,3 +176,17 @@ def test_reference_windows_with_n_runs():
     for case in A.n_window_cases():
         recs = O.align_contig_multi(case.hap, case.ref)
         A.check_case(case, recs)
+
+
+def test_one_contig_with_an_event_for_every_dp_class():
+    """aln_cases.dp_class_cases: five events between unique flanks, one record per strand with exactly these gaps -- a 100-base
+    deletion, two replacements and a third of 3 300 by 3 500 bases as an insertion in front of a deletion, a 2 000-base insertion.
+    The GPU test runs both strands in one batch: each of the four DP kernels gets an event of each."""
+    from tests import aln_cases as A
+    cases = A.dp_class_cases()
+    assert [len(c.ref) for c in cases] == [51100, 51100] and cases[1].hap == synth.revcomp(cases[0].hap)
+    for case in cases:
+        recs = O.align_contig_multi(case.hap, case.ref)
+        A.check_case(case, recs)
+        gaps = [(op, n) for op, n in recs[0]["cigar"] if op != 0]
+        assert gaps == [(2, 100), (1, 1200), (2, 1000), (1, 600), (2, 5000), (1, 3500), (2, 3300), (1, 2000)], (case.name, gaps)
