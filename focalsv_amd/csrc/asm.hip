@@ -52,6 +52,19 @@ struct Span {
     void stop() { kt.end(ctx, idx); }
 };
 
+// HIP-event time of a few spans on a stream: mark() where a span starts and where it ends, ms() once the stream has passed them all
+// (the host reads counts back between the spans, or the chunk has ended).  It owns its events: clear(), or the destructor, destroys them.
+struct EventClock {
+    std::vector<hipEvent_t> ev;
+    EventClock() = default;
+    EventClock(const EventClock &) = delete;
+    EventClock &operator=(const EventClock &) = delete;
+    ~EventClock() { clear(); }
+    int mark(fsv_ctx *ctx) { hipEvent_t e; FSV_HIP(ctx, hipEventCreate(&e)); ev.push_back(e); FSV_HIP(ctx, hipEventRecord(e, ctx->stream)); return FSV_OK; }
+    double ms() const { double t = 0; for (size_t i = 0; i + 1 < ev.size(); i += 2) { float x = 0; if (hipEventElapsedTime(&x, ev[i], ev[i + 1]) == hipSuccess) t += x; } return t; }
+    void clear() { for (auto e : ev) (void)hipEventDestroy(e); ev.clear(); }
+};
+
 // per-round block of device counters (one 64-byte slot per correction round + one for the final pass, zeroed once per batch and
 // read back with the round's one synchronisation or at the end): u32 indices
 enum { CT_TASKS = 0, CT_OVERFLOW = 1, CT_DP = 2, CT_INEXACT = 3, CT_COLS_LO = 4, CT_COLS_HI = 5, CT_DP_WIDE = 6, CT_DP_SB = 7, CT_DP_GEN = 8, CT_DP_XW = 9,
@@ -63,6 +76,41 @@ enum { CT_TASKS = 0, CT_OVERFLOW = 1, CT_DP = 2, CT_INEXACT = 3, CT_COLS_LO = 4,
        CT_SLOT = 24 };      // even: the 64-bit sums stay aligned in every slot
 
 template <class... Ts> size_t cap_sum(const Ts &...b) { return (b.cap + ... + 0); }
+
+// ---- the opt-in stages: each one's buffers and what the last fsv_assemble_batch left of it (reset() when a call begins; valid: set when it
+// ---- ends, see AsmWs::mark_valid), with held() as the stage's share of AsmWs::held()
+// kmer_table = 1, the k-mer count table stage (k_kmer.h): one open-addressed table per set back to back (keys, counts), the sets' histograms,
+// the filter list of the last stage and -- for a batch of several chunks -- of all its chunks, in set order
+struct KmerTableState {
+    Dev<unsigned long long> keys, flt, flt_all; Dev<uint32_t> cnt, hist, cursor, err; Dev<uint64_t> tab_off, flt_off;
+    Dev<int32_t> cutoff; Dev<KmerTile> tiles;
+    // per set its verdict (peak_hom is hifiasm's hom_cov), and its segment [last_flt_off[s], last_flt_off[s + 1]) of the filter list on the
+    // device (flt_all, unordered inside a set); ms: the stage's launches, all chunks
+    std::vector<fsv_kmer_set> last; std::vector<uint64_t> last_flt_off{0}; double ms = 0; bool valid = false;
+    size_t held() const { return cap_sum(keys, flt, flt_all, cnt, hist, cursor, err, tab_off, flt_off, cutoff, tiles); }
+    void reset() { last.clear(); last_flt_off.assign(1, 0); ms = 0; valid = false; }
+};
+// kmer_filter = 1 (and the stage hooks fsv_sketch_reads_filtered / fsv_kmer_index): the sets' filter sets that the sketch kernels probe
+// (k_flt_build: keys back to back, n_sets + 1 slot offsets), the set of every read, a caller's lists on the device; view: what a sketch
+// launch takes -- nothing when no set has a slot
+struct FilterState {
+    Dev<unsigned long long> keys, list; Dev<uint64_t> off, list_off; Dev<uint32_t> read_set;
+    SketchFilter view;
+    // per set the figures of hifiasm's first ha_pt_gen (peak_hom: its hom_cov); ms: the filter-set builds and the index, all chunks
+    std::vector<fsv_kmer_index_set> last; double ms = 0; bool valid = false;
+    size_t held() const { return cap_sum(keys, list, off, list_off, read_set); }
+    void reset() { view = SketchFilter{}; last.clear(); ms = 0; valid = false; }
+};
+// partial_charge = 1 (charge_stage): two extension tasks and results per window task at fixed slots, the slots in use, the overlaps waiting
+// for their verdict, the two list lengths, the stage's counters (fsv_charge_stats' five, summed over the chunk's rounds)
+struct ChargeState {
+    Dev<fsv_wtask> ext_tasks; Dev<fsv_wext> ext_res; Dev<uint32_t> ext_list, list, n; Dev<unsigned long long> ct;
+    EventClock clock;          // start / end of every charge_stage of the chunk, resolved when the chunk ends (charge_collect)
+    fsv_charge_stats last{};   // all chunks
+    bool valid = false;
+    size_t held() const { return cap_sum(ext_tasks, ext_res, ext_list, list, n, ct); }
+    void reset() { clock.clear(); last = fsv_charge_stats{}; valid = false; }   // (clock: marks of a call that failed half-way)
+};
 
 struct AsmWs {
     Dev<uint32_t> store[2], word_off, set_start, read_set, pair_base, upair_base, pair_read, mz_off, mz_cnt, counters, warn, set_cols, changed, read_dirty,
@@ -80,26 +128,9 @@ struct AsmWs {
     Dev<uint64_t> cols;          // k_path_dp's column scratch: 64-bit columns, or 32-bit ones in the same bytes
     Dev<unsigned long long> tmp; // cycle stamps of the diagnostic runs
     Dev<uint8_t> cov3, bnd_bytes, exact_flag, cwin, thr_tab; Dev<uint16_t> cwin_len; Dev<char> contig_out, contig_all;
-    // the k-mer count table stage (k_kmer.h): one open-addressed table per set back to back (keys, counts), the sets' histograms, the
-    // filter list of the last stage and -- for a batch of several chunks -- of all its chunks, in set order
-    Dev<unsigned long long> km_keys, km_flt, km_flt_all; Dev<uint32_t> km_cnt, km_hist, km_cursor, km_err; Dev<uint64_t> km_tab_off, km_flt_off;
-    Dev<int32_t> km_cutoff; Dev<KmerTile> km_tiles;
-    // kmer_filter = 1 (and the stage hooks fsv_sketch_reads_filtered / fsv_kmer_index): the sets' filter sets that the sketch kernels probe
-    // (k_flt_build: keys back to back, n_sets + 1 slot offsets), the set of every read, a caller's lists on the device; flt: the view a
-    // sketch launch takes -- nothing when no set has a slot
-    Dev<unsigned long long> fs_keys, fs_list; Dev<uint64_t> fs_off, fs_list_off; Dev<uint32_t> fs_read_set;
-    SketchFilter flt;
-    // what the last fsv_assemble_batch with kmer_filter = 1 left: per set the figures of hifiasm's first ha_pt_gen (peak_hom: its hom_cov)
-    std::vector<fsv_kmer_index_set> ki_last; double ki_ms = 0; bool ki_valid = false;
-    // partial_charge = 1 (charge_stage): two extension tasks and results per window task at fixed slots, the slots in use, the overlaps
-    // waiting for their verdict, the two list lengths, the stage's counters (fsv_charge_stats' five, summed over the chunk's rounds)
-    Dev<fsv_wtask> ext_tasks; Dev<fsv_wext> ext_res; Dev<uint32_t> ext_list, charge_list, charge_n; Dev<unsigned long long> charge_ct;
-    std::vector<hipEvent_t> charge_ev;   // start / end of every charge_stage of the chunk, resolved when the chunk ends
-    fsv_charge_stats charge_last{};      // the last fsv_assemble_batch's, all chunks
-    bool charge_valid = false;
-    // what the last fsv_assemble_batch with kmer_table = 1 left for the follow-up stages: per set its verdict (peak_hom is hifiasm's hom_cov),
-    // and its segment [km_last_flt_off[s], km_last_flt_off[s + 1]) of the filter list on the device (km_last_flt, unordered inside a set)
-    std::vector<fsv_kmer_set> km_last; std::vector<uint64_t> km_last_flt_off; const unsigned long long *km_last_flt = nullptr; double km_ms = 0; bool km_valid = false;
+    KmerTableState km;   // kmer_table = 1
+    FilterState fs;      // kmer_filter = 1
+    ChargeState ch;      // partial_charge = 1
     std::vector<uint32_t> h_store;   // the corrected reads of the sets whose layout compares bases (kept between calls: no 96 MB zero-fill a step)
     int occ_sb = 0, occ_fr[3] = {0, 0, 0}, occ_wide = 0;   // blocks per CU of the persistent K6 kernels (hipOccupancyMaxActiveBlocksPerMultiprocessor: asked once)
     ChainArgs last_chain;   // arguments of the last k_chain launch (the final pass re-chains a few pairs with another bandwidth)
@@ -120,9 +151,12 @@ struct AsmWs {
                        site_cursor, redo, site_lists, read_dirty, cov3, lb, sr_store, brel_off, tasks2, res2, paths2, idx2, bc_idx, bc_rec, bc_win, left_list, fix_list,
                        tasks3, res3, src3, bnd_flag, bnd_list, bnd_patch, bnd_bytes, changed, pair_read, wide_list, cols, tmp, gwin_off, gwin_read, sk_ends, sk_low, sk_high,
                        hits, hits_packed, set_hits, ovl_prev, exact_flag, inexact_list, upair_base, upair_tab, upair_tab_sw, ovl_c, gwin_tab, cwin, cwin_len, warn, thr_tab,
-                       pieces, contig_out, new_len, unpack_off, km_keys, km_flt, km_flt_all, km_cnt, km_hist, km_cursor, km_err, km_tab_off, km_flt_off, km_cutoff, km_tiles,
-                       fs_keys, fs_list, fs_off, fs_list_off, fs_read_set, ext_tasks, ext_res, ext_list, charge_list, charge_n, charge_ct);
+                       pieces, contig_out, new_len, unpack_off) + km.held() + fs.held() + ch.held();
     }
+    // the opt-in stages' state between two calls of fsv_assemble_batch: forgotten when a call begins, valid when it ends well.  stages_ran:
+    // false for a call that returned before its first chunk (no set, or no read and no kmer_table) -- the k-mer getters then go on refusing
+    void reset_stages() { km.reset(); fs.reset(); ch.reset(); }
+    void mark_valid(const fsv_asm_params &P, bool stages_ran) { km.valid = stages_ran && P.kmer_table; fs.valid = stages_ran && P.kmer_filter; ch.valid = P.partial_charge != 0; }
 };
 
 void ws_free(fsv_ctx *ctx)
@@ -130,7 +164,6 @@ void ws_free(fsv_ctx *ctx)
     AsmWs *w = (AsmWs *)ctx->asm_ws;
     if (!w) return;
     if (w->h_pin) (void)hipHostFree(w->h_pin);
-    for (auto e : w->charge_ev) (void)hipEventDestroy(e);
     delete w;
     ctx->asm_ws = nullptr;
 }
@@ -274,7 +307,7 @@ int overlap_stage(fsv_ctx *ctx, AsmWs &W, const Round &R, bool final_pass)
     TRY(ensure(ctx, W.ovl_c, std::max(1u, B.n_pairs)));
     W.kt.begin(ctx, PASS_WINDOWS, KN_SKETCH, 0);    // bytes: filled in from the round's counters (minimizers produced, bases sketched)
     TRY(launch_sketch(ctx, W, SketchJob{R.store, B.n_reads, G.word_off[B.n_reads], G.max_words, w, P.k, P.hpc, nullptr, w, false, only_changed,
-                                     P.kmer_filter ? W.flt : SketchFilter{}}));   // (every round and the final pass: the one filter of the raw reads, as ha_flt_tab)
+                                     P.kmer_filter ? W.fs.view : SketchFilter{}}));   // (every round and the final pass: the one filter of the raw reads, as ha_flt_tab)
     W.kt.end(ctx);
     // the sort in k_uniq holds a read's minimizers in LDS (16 B per entry): one instantiation for lists up to 1 024 entries (many
     // reads per CU), one for longer ones; each launch skips the reads of the other size class, so the host need not know the
@@ -682,10 +715,10 @@ static int fsv_bpm_extensions_impl(fsv_ctx *ctx, const uint32_t *store, size_t s
     TRY(ensure(ctx, d_store, store_words + 16));
     TRY(zero(ctx, d_store, store_words + 16));
     FSV_HIP(ctx, hipMemcpyAsync(d_store.p, store, store_words * 4, hipMemcpyHostToDevice, ctx->stream));
-    TRY(upload(ctx, W.ext_tasks, t));
-    TRY(ensure(ctx, W.ext_res, n_tasks));
-    TRY(launch_bpm_ext(ctx, d_store.p, W.ext_tasks.p, nullptr, nullptr, n_tasks, k_cap, W.ext_res.p, nullptr));
-    TRY(download(ctx, out, W.ext_res, n_tasks));
+    TRY(upload(ctx, W.ch.ext_tasks, t));
+    TRY(ensure(ctx, W.ch.ext_res, n_tasks));
+    TRY(launch_bpm_ext(ctx, d_store.p, W.ch.ext_tasks.p, nullptr, nullptr, n_tasks, k_cap, W.ch.ext_res.p, nullptr));
+    TRY(download(ctx, out, W.ch.ext_res, n_tasks));
     FSV_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return FSV_OK;
 }
@@ -694,8 +727,8 @@ static int fsv_asm_last_charge_impl(const fsv_ctx *ctx, fsv_charge_stats *out)
 {
     if (!ctx || !out || !ctx->asm_ws) return FSV_EINVAL;
     const AsmWs &W = *(const AsmWs *)ctx->asm_ws;
-    if (!W.charge_valid) return FSV_EINVAL;
-    *out = W.charge_last;
+    if (!W.ch.valid) return FSV_EINVAL;
+    *out = W.ch.last;
     return FSV_OK;
 }
 
@@ -714,7 +747,7 @@ extern "C" int fsv_asm_last_stats(const fsv_ctx *ctx, fsv_asm_stats *out)
 // the batch's tables on the device, the geometry of round 0, zeroed counters
 static int prepare_batch(fsv_ctx *ctx, AsmWs &W, const fsv_readsets *sets, Round &R)
 {
-    // (set_start spans [0, n_reads] and is monotone: fsv_assemble_batch_impl has checked)
+    // (set_start, the read lengths and the word offsets are in range: the entry points have checked -- check_readsets)
     const fsv_asm_params &P = R.P; Batch &B = R.B;
     B.n_reads = sets->n_reads;
     R.set_flags = sets->set_flags;   // (FSV_SET_UNPHASED only picks the layout: the haplotype partition runs for every read of every set, as in hifiasm)
@@ -740,7 +773,6 @@ static int prepare_batch(fsv_ctx *ctx, AsmWs &W, const fsv_readsets *sets, Round
     B.upair_base[B.n_sets] = (uint32_t)(np / 2); B.n_upairs = (uint32_t)(np / 2);
     std::vector<int32_t> &len = R.len;
     len.assign(sets->read_len, sets->read_len + B.n_reads);
-    for (uint32_t r = 0; r < B.n_reads; r++) if (len[r] < 1 || len[r] >= (1 << 24)) return fsv_fail(ctx, FSV_EUNSUP, "read length must be in [1, 2^24)");
 
     std::vector<uint8_t> thr(FSV_WINDOW + 1);
     for (int i = 0; i <= FSV_WINDOW; i++) thr[i] = thr_for_len_host(i, P.win_rate_pm);
@@ -769,10 +801,7 @@ static int prepare_batch(fsv_ctx *ctx, AsmWs &W, const fsv_readsets *sets, Round
     }
     TRY(make_geometry(ctx, B, len, R.G, P.w, &R.mz_fixed));
     // round 0 reads the caller's store through the caller's word offsets
-    for (uint32_t r = 0; r <= B.n_reads; r++) {
-        if (sets->word_off[r] >= (1ull << 32)) return fsv_fail(ctx, FSV_EUNSUP, "store larger than 2^32 words; split the batch");
-        R.G.word_off[r] = (uint32_t)sets->word_off[r];
-    }
+    for (uint32_t r = 0; r <= B.n_reads; r++) R.G.word_off[r] = (uint32_t)sets->word_off[r];
     R.store = sets->store_dev;
     R.wide_bands = P.k_cap > FSV_K_MAX;
     for (uint32_t r = 0; r < B.n_reads; r++) { R.reads_in_bytes += (uint64_t)(len[r] + 3) / 4; if (len[r] >= 65536) R.short_reads = false; }
@@ -810,21 +839,21 @@ static int charge_stage(fsv_ctx *ctx, AsmWs &W, const Round &R)
 {
     const fsv_asm_params &P = R.P; const Batch &B = R.B;
     const uint32_t ext_cap = 2u * R.task_cap;      // (task_cap < 2^31: begin_round)
-    TRY(ensure_each(ctx, ext_cap, W.ext_tasks, W.ext_res, W.ext_list));
-    TRY(ensure(ctx, W.charge_list, (size_t)B.n_pairs + 4));
-    TRY(ensure(ctx, W.charge_n, 2));
-    TRY(zero(ctx, W.charge_n, 2));
+    ChargeState &S = W.ch;
+    TRY(ensure_each(ctx, ext_cap, S.ext_tasks, S.ext_res, S.ext_list));
+    TRY(ensure(ctx, S.list, (size_t)B.n_pairs + 4));
+    TRY(ensure(ctx, S.n, 2));
+    TRY(zero(ctx, S.n, 2));
     ChargeArgs A;
     A.ovl = W.ovl.p; A.n_pairs = B.n_pairs; A.tasks = W.tasks.p; A.res = W.res.p; A.paths = W.paths.p; A.ovl_c = W.ovl_c.p;
-    A.ext_tasks = W.ext_tasks.p; A.ext_res = W.ext_res.p; A.ext_list = W.ext_list.p; A.n_ext = W.charge_n.p;
-    A.ovl_list = W.charge_list.p; A.n_ovl = W.charge_n.p + 1; A.stats = W.charge_ct.p;
+    A.ext_tasks = S.ext_tasks.p; A.ext_res = S.ext_res.p; A.ext_list = S.ext_list.p; A.n_ext = S.n.p;
+    A.ovl_list = S.list.p; A.n_ovl = S.n.p + 1; A.stats = S.ct.p;
     A.k_cap = P.k_cap; A.accept_err_pm = P.accept_err_pm;
-    auto mark = [&]() -> int { hipEvent_t e; FSV_HIP(ctx, hipEventCreate(&e)); W.charge_ev.push_back(e); FSV_HIP(ctx, hipEventRecord(e, ctx->stream)); return FSV_OK; };
-    TRY(mark());
+    TRY(S.clock.mark(ctx));
     FSV_LAUNCH(ctx, ctx->stream, k_charge_tasks, dim3(fsv_grid_for(B.n_pairs, 64)), dim3(64), 0, A);
-    TRY(launch_bpm_ext(ctx, R.store, W.ext_tasks.p, W.ext_list.p, W.charge_n.p, ext_cap, P.k_cap, W.ext_res.p, W.charge_ct.p + CH_EXT));
+    TRY(launch_bpm_ext(ctx, R.store, S.ext_tasks.p, S.ext_list.p, S.n.p, ext_cap, P.k_cap, S.ext_res.p, S.ct.p + CH_EXT));
     FSV_LAUNCH(ctx, ctx->stream, k_charge_accept, dim3(fsv_grid_for(B.n_pairs, 64)), dim3(64), 0, A);
-    TRY(mark());
+    TRY(S.clock.mark(ctx));
     return FSV_OK;
 }
 
@@ -1362,185 +1391,277 @@ static void fill_stats(AsmWs &W, const Round &R, const Final &F)
     }
 }
 
-// ---- the k-mer count table stage (k_kmer.h) --------------------------------------------------------------------------------------
-// HIP-event time of the stage's launches: a few spans on the stream (the host reads counts back between them), summed at the end
-struct KmerClock {
-    fsv_ctx *ctx; std::vector<hipEvent_t> ev;
-    explicit KmerClock(fsv_ctx *c) : ctx(c) {}
-    ~KmerClock() { for (auto e : ev) (void)hipEventDestroy(e); }
-    void mark() { hipEvent_t e; if (hipEventCreate(&e) == hipSuccess) { (void)hipEventRecord(e, ctx->stream); ev.push_back(e); } }
-    double ms() const { double t = 0; for (size_t i = 0; i + 1 < ev.size(); i += 2) { float x = 0; if (hipEventElapsedTime(&x, ev[i], ev[i + 1]) == hipSuccess) t += x; } return t; }
-};
+// a chunk's statistics join those of the chunks before it (the junction-cigar counts of fsv_asm_stats are a single chunk's: never summed)
+static void add_stats(fsv_asm_stats &total, const fsv_asm_stats &st)
+{
+    total.n_pairs += st.n_pairs; total.n_overlaps += st.n_overlaps; total.n_windows += st.n_windows; total.n_windows_matched += st.n_windows_matched;
+    total.n_paths += st.n_paths; total.n_path_dp += st.n_path_dp; total.dp_columns += st.dp_columns; total.algo_bytes += st.algo_bytes;
+    total.n_exact_overlaps += st.n_exact_overlaps; total.n_inexact_candidates += st.n_inexact_candidates; total.n_path_fr += st.n_path_fr;
+    total.ms_sketch += st.ms_sketch; total.ms_chain += st.ms_chain; total.ms_verify += st.ms_verify; total.ms_path += st.ms_path;
+    total.ms_consensus += st.ms_consensus; total.ms_final += st.ms_final; total.ms_total += st.ms_total;
+    total.n_kernels = st.n_kernels;
+    for (uint32_t k = 0; k < st.n_kernels; k++) {
+        memcpy(total.kernels[k].name, st.kernels[k].name, sizeof(st.kernels[k].name));
+        total.kernels[k].ms += st.kernels[k].ms; total.kernels[k].launches += st.kernels[k].launches; total.kernels[k].algo_bytes += st.kernels[k].algo_bytes;
+    }
+}
 
-// The stage on the caller's read sets: sketch at (w, k, hpc) into W.mz, count per set, histogram, verdict (host: the histograms are 16 KB
-// a set), filter list.  out: n_sets records.  hist / flt_hash + flt_off: optional host copies (see fsv_kmer_table).  Leaves the filter
-// list in W.km_flt with the offsets in flt_off_out, and adds the launches' time to *ms.
-// sketch_flt (the index of hifiasm's ha_pt_gen): the sketch takes these filter sets, and no filter list is made of what it counts.
-static int kmer_stage(fsv_ctx *ctx, AsmWs &W, const fsv_readsets *sets, int w, int k, int hpc, fsv_kmer_set *out, uint64_t *hist, uint64_t *flt_hash,
-                      uint64_t flt_cap, uint64_t *flt_off, std::vector<uint64_t> &flt_off_out, double *ms, const SketchFilter *sketch_flt = nullptr)
+// ---- the caller's read sets: checked once per entry point, staged once for a sketch-only job ------------------------------------------
+// the pointers an entry needs (without them it returns FSV_EINVAL and no message)
+static bool readsets_present(const fsv_readsets *sets, bool with_sets)
+{
+    return sets && sets->store_dev && sets->word_off && sets->read_len && (!with_sets || sets->set_start);
+}
+
+// The values of the caller's read sets, before anything is launched.  RS_SETS: set_start spans [0, n_reads] and is monotone; RS_LEN: every
+// read length in [1, 2^24); RS_WORD_OFF: every word offset below 2^32 (the kernels take 32-bit ones).  What runs behind an entry point
+// (prepare_batch, kmer_stage, stage_sketch_reads) assumes all three.
+enum { RS_SETS = 1, RS_LEN = 2, RS_WORD_OFF = 4, RS_ALL = RS_SETS | RS_LEN | RS_WORD_OFF };
+static int check_readsets(fsv_ctx *ctx, const fsv_readsets *sets, unsigned what)
 {
     const uint32_t n_reads = sets->n_reads, n_sets = sets->n_sets;
-    flt_off_out.assign((size_t)n_sets + 1, 0);
-    std::vector<uint64_t> entries(n_sets, 0);
-    std::vector<uint32_t> h_hist((size_t)n_sets * FSV_KMER_BINS, 0u);
-    std::vector<uint64_t> tab_off((size_t)n_sets + 1, 0);
-    std::vector<KmerTile> tiles;
-    KmerClock clock(ctx);
-    if (n_reads) {
-        Batch B;
-        B.n_reads = n_reads; B.n_sets = 1; B.set_start = {0u, n_reads};
-        std::vector<int32_t> len(sets->read_len, sets->read_len + n_reads);
-        for (uint32_t r = 0; r < n_reads; r++) if (len[r] < 1 || len[r] >= (1 << 24)) return fsv_fail(ctx, FSV_EUNSUP, "read length must be in [1, 2^24)");
-        Geometry G;
-        TRY(make_geometry(ctx, B, len, G, w));
-        for (uint32_t r = 0; r <= n_reads; r++) {
-            if (sets->word_off[r] >= (1ull << 32)) return fsv_fail(ctx, FSV_EUNSUP, "store larger than 2^32 words; split the batch");
-            G.word_off[r] = (uint32_t)sets->word_off[r];
-        }
-        std::vector<uint32_t> read_set(n_reads);
-        for (uint32_t s = 0; s < n_sets; s++) for (uint32_t r = sets->set_start[s]; r < sets->set_start[s + 1]; r++) read_set[r] = s;
-        TRY(upload(ctx, W.word_off, G.word_off));
-        TRY(upload(ctx, W.len, len));
-        TRY(upload(ctx, W.mz_off, G.mz_off));
-        TRY(upload(ctx, W.read_set, read_set));
-        TRY(ensure(ctx, W.warn, n_reads));
-        TRY(zero(ctx, W.warn, n_reads));
-        TRY(ensure(ctx, W.mz, G.mz_off[n_reads]));
-        TRY(ensure(ctx, W.mz_cnt, n_reads));
-        clock.mark();
-        TRY(launch_sketch(ctx, W, SketchJob{sets->store_dev, n_reads, G.word_off[n_reads], G.max_words, w, k, hpc, nullptr, w, false, nullptr,
-                                         sketch_flt ? *sketch_flt : SketchFilter{}}));
-        clock.mark();
-        // the tables are sized from what the sketch emitted
-        std::vector<uint32_t> cnt(n_reads);
-        TRY(download(ctx, cnt.data(), W.mz_cnt, n_reads));
-        FSV_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        for (uint32_t r = 0; r < n_reads; r++) entries[read_set[r]] += std::min<uint32_t>(cnt[r], G.mz_off[r + 1] - G.mz_off[r]);
-        for (uint32_t s = 0; s < n_sets; s++) {
-            const uint64_t slots = kmer_table_slots(entries[s]), tile = std::min<uint64_t>(slots, FSV_KMER_TILE);
-            tab_off[s + 1] = tab_off[s] + slots;
-            for (uint64_t f = 0; f < slots; f += tile) tiles.push_back(KmerTile{s, (uint32_t)tile, f});
-        }
-        if (tiles.size() >= (1ull << 31)) return fsv_fail(ctx, FSV_EUNSUP, "k-mer tables too large for one pass; split the batch");
+    if (what & RS_SETS) {
+        if (n_sets == 0 ? n_reads != 0 : (sets->set_start[0] != 0 || sets->set_start[n_sets] != n_reads)) return fsv_fail(ctx, FSV_EINVAL, "set_start must span [0, n_reads]");
+        for (uint32_t s = 0; s < n_sets; s++) if (sets->set_start[s + 1] < sets->set_start[s]) return fsv_fail(ctx, FSV_EINVAL, "set_start not monotone");
     }
-    const uint64_t total_slots = tab_off[n_sets];
-    TRY(ensure(ctx, W.km_err, 1));
-    TRY(zero(ctx, W.km_err, 1));
-    TRY(ensure(ctx, W.km_cursor, std::max(1u, n_sets)));
-    TRY(zero(ctx, W.km_cursor, std::max(1u, n_sets)));
-    TRY(upload(ctx, W.km_tab_off, tab_off));
-    uint32_t err = 0;
-    if (total_slots) {
-        TRY(ensure(ctx, W.km_keys, total_slots));
-        TRY(ensure(ctx, W.km_cnt, total_slots));
-        TRY(ensure(ctx, W.km_hist, h_hist.size()));
-        TRY(upload(ctx, W.km_tiles, tiles));
-        clock.mark();
-        FSV_HIP(ctx, hipMemsetAsync(W.km_keys.p, 0xff, total_slots * sizeof(unsigned long long), ctx->stream));   // every slot FSV_KMER_EMPTY
-        TRY(zero(ctx, W.km_cnt, total_slots));
-        TRY(zero(ctx, W.km_hist, h_hist.size()));
-        FSV_LAUNCH(ctx, ctx->stream, k_kmer_insert, dim3(n_reads), dim3(256), 0, W.mz.p, W.mz_off.p, W.mz_cnt.p, W.read_set.p, W.km_tab_off.p, W.km_keys.p, W.km_cnt.p,
-                   n_reads, W.km_err.p);
-        FSV_LAUNCH(ctx, ctx->stream, k_kmer_hist, dim3((uint32_t)tiles.size()), dim3(256), 0, W.km_tiles.p, W.km_tab_off.p, W.km_keys.p, W.km_cnt.p, W.km_hist.p);
-        clock.mark();
-        TRY(download(ctx, h_hist.data(), W.km_hist, h_hist.size()));
-        TRY(download(ctx, &err, W.km_err, 1));
-        FSV_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        if (err) return fsv_fail(ctx, FSV_EINTERNAL, "k-mer count table: a set's table ran full");
-    }
-    // the verdict per set, and the filter segments the histogram promises
-    std::vector<int32_t> cutoff(n_sets);
-    std::vector<int64_t> h64(FSV_KMER_BINS);
-    for (uint32_t s = 0; s < n_sets; s++) {
-        const uint32_t *h = h_hist.data() + (size_t)s * FSV_KMER_BINS;
-        fsv_kmer_set &o = out[s];
-        memset(&o, 0, sizeof(o));
-        for (int c = 0; c < FSV_KMER_BINS; c++) { h64[c] = h[c]; o.n_distinct += h[c]; if (hist) hist[(size_t)s * FSV_KMER_BINS + c] = h[c]; }
-        o.peak_hom = fsv_kmer_peaks_hd(h64.data(), FSV_KMER_BINS, FSV_KMER_START, &o.peak_het, &o.low_i, &o.max_i);
-        o.cutoff = cutoff[s] = fsv_kmer_cutoff(o.peak_hom);
-        o.n_entries = entries[s];
-        for (int c = 1; c < FSV_KMER_BINS; c++) if (c >= o.cutoff) o.n_filtered += h[c];
-        for (int c = 2; c <= FSV_KMER_BINS - 2; c++) o.n_indexed += (uint64_t)c * h[c];
-        flt_off_out[s + 1] = flt_off_out[s] + (sketch_flt ? 0 : o.n_filtered);
-    }
-    const uint64_t n_flt = flt_off_out[n_sets];
-    if (n_flt) {
-        std::vector<uint32_t> cursor(n_sets);
-        TRY(ensure(ctx, W.km_flt, n_flt));
-        TRY(upload(ctx, W.km_cutoff, cutoff));
-        TRY(upload(ctx, W.km_flt_off, flt_off_out));
-        clock.mark();
-        FSV_LAUNCH(ctx, ctx->stream, k_kmer_filter, dim3((uint32_t)tiles.size()), dim3(256), 0, W.km_tiles.p, W.km_tab_off.p, W.km_keys.p, W.km_cnt.p, W.km_cutoff.p,
-                   W.km_flt_off.p, W.km_cursor.p, W.km_flt.p, W.km_err.p);
-        clock.mark();
-        TRY(download(ctx, cursor.data(), W.km_cursor, n_sets));
-        TRY(download(ctx, &err, W.km_err, 1));
-        FSV_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        for (uint32_t s = 0; s < n_sets; s++) if (cursor[s] != out[s].n_filtered) err |= FSV_KMER_E_FLT;
-        if (err) return fsv_fail(ctx, FSV_EINTERNAL, "k-mer count table: the filter pass and the histogram disagree");
-    } else {
-        FSV_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    }
-    if (ms) *ms += clock.ms();
-    if (flt_off) {
-        memcpy(flt_off, flt_off_out.data(), ((size_t)n_sets + 1) * sizeof(uint64_t));
-        if (n_flt > flt_cap) return fsv_fail(ctx, FSV_ECAP, "fsv_kmer_table: flt_hash too small");
-        if (n_flt) {
-            FSV_HIP(ctx, hipMemcpyAsync(flt_hash, W.km_flt.p, n_flt * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
-            FSV_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        }
-        for (uint32_t s = 0; s < n_sets; s++) std::sort(flt_hash + flt_off[s], flt_hash + flt_off[s + 1]);
-    }
+    if (what & RS_LEN)
+        for (uint32_t r = 0; r < n_reads; r++) if (sets->read_len[r] < 1 || sets->read_len[r] >= (1 << 24)) return fsv_fail(ctx, FSV_EUNSUP, "read length must be in [1, 2^24)");
+    if ((what & RS_WORD_OFF) && n_reads)
+        for (uint32_t r = 0; r <= n_reads; r++) if (sets->word_off[r] >= (1ull << 32)) return fsv_fail(ctx, FSV_EUNSUP, "store larger than 2^32 words; split the batch");
     return FSV_OK;
 }
 
+// the set of every read of the caller's sets
+static std::vector<uint32_t> read_set_of(const fsv_readsets *sets)
+{
+    std::vector<uint32_t> read_set(sets->n_reads);
+    for (uint32_t s = 0; s < sets->n_sets; s++) for (uint32_t r = sets->set_start[s]; r < sets->set_start[s + 1]; r++) read_set[r] = s;
+    return read_set;
+}
+
+// The reads of a sketch-only job (fsv_sketch_reads, the k-mer stages) on the device: all of them as one set with its geometry at window w
+// (G), read through the caller's word offsets; word_off, len, mz_off -- and read_set, when given -- uploaded, warn zeroed, room for mz and
+// mz_cnt.  (lengths and word offsets in range: check_readsets)
+static int stage_sketch_reads(fsv_ctx *ctx, AsmWs &W, const fsv_readsets *sets, int w, const std::vector<uint32_t> *read_set, Geometry &G)
+{
+    const uint32_t n_reads = sets->n_reads;
+    Batch B;
+    B.n_reads = n_reads; B.n_sets = 1; B.set_start = {0u, n_reads};
+    const std::vector<int32_t> len(sets->read_len, sets->read_len + n_reads);
+    TRY(make_geometry(ctx, B, len, G, w));
+    for (uint32_t r = 0; r <= n_reads; r++) G.word_off[r] = (uint32_t)sets->word_off[r];
+    TRY(upload(ctx, W.word_off, G.word_off));
+    TRY(upload(ctx, W.len, len));
+    TRY(upload(ctx, W.mz_off, G.mz_off));
+    if (read_set) TRY(upload(ctx, W.read_set, *read_set));
+    TRY(ensure(ctx, W.warn, n_reads));
+    TRY(zero(ctx, W.warn, n_reads));
+    TRY(ensure(ctx, W.mz, G.mz_off[n_reads]));
+    TRY(ensure(ctx, W.mz_cnt, n_reads));
+    return FSV_OK;
+}
+
+// n elements of src (device) behind the `have` elements b holds, on the context's stream.  A buffer too small for them (and `slack` more)
+// is replaced by one of twice what it must hold, min_elems at least, that keeps the contents: one synchronisation when it grows, none otherwise
+template <class T> int append_on_device(fsv_ctx *ctx, Dev<T> &b, size_t have, const T *src, size_t n, size_t slack = 0, size_t min_elems = 0)
+{
+    if (!n) return FSV_OK;
+    if (b.cap < (have + n + slack) * sizeof(T)) {
+        Dev<T> bigger;
+        TRY(ensure(ctx, bigger, std::max((have + n) * 2, min_elems)));
+        if (have) FSV_HIP(ctx, hipMemcpyAsync(bigger.p, b.p, have * sizeof(T), hipMemcpyDeviceToDevice, ctx->stream));
+        FSV_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        b.swap(bigger);      // (the old allocation goes with `bigger`)
+    }
+    FSV_HIP(ctx, hipMemcpyAsync(b.p + have, src, n * sizeof(T), hipMemcpyDeviceToDevice, ctx->stream));
+    return FSV_OK;
+}
+
+// ---- the k-mer count table stage (k_kmer.h) --------------------------------------------------------------------------------------
+// The stage on the caller's read sets: sketch at (w, k, hpc) into W.mz, count per set, histogram, verdict (host: the histograms are 16 KB
+// a set), filter list.
+struct KmerJob {
+    const fsv_readsets *sets; int w, k, hpc;
+    const SketchFilter *sketch_flt;   // (the index of hifiasm's ha_pt_gen) the sketch takes these filter sets, and no filter list is made of what it counts; or null
+    double *ms;                       // the launches' HIP-event time is added here; or null
+};
+struct KmerResult {
+    std::vector<fsv_kmer_set> sets;   // the verdicts
+    std::vector<uint32_t> hist;       // n_sets x FSV_KMER_BINS
+    std::vector<uint64_t> flt_off;    // set s's keys: [flt_off[s], flt_off[s + 1]) of the filter list the stage leaves in W.km.flt (unordered)
+};
+// what the stage's pieces hand on; the clock's spans lie between the host's read-backs
+struct KmerRun {
+    const KmerJob &J; KmerResult &R; EventClock clock;
+    std::vector<uint64_t> entries, tab_off; std::vector<KmerTile> tiles; std::vector<int32_t> cutoff;
+};
+
+// the sketch, and the tables sized from what it emitted
+static int kmer_sketch(fsv_ctx *ctx, AsmWs &W, KmerRun &K)
+{
+    const KmerJob &J = K.J; const fsv_readsets *sets = J.sets;
+    const uint32_t n_reads = sets->n_reads, n_sets = sets->n_sets;
+    K.entries.assign(n_sets, 0); K.tab_off.assign((size_t)n_sets + 1, 0);
+    if (!n_reads) return FSV_OK;
+    const std::vector<uint32_t> read_set = read_set_of(sets);
+    Geometry G;
+    TRY(stage_sketch_reads(ctx, W, sets, J.w, &read_set, G));
+    TRY(K.clock.mark(ctx));
+    TRY(launch_sketch(ctx, W, SketchJob{sets->store_dev, n_reads, G.word_off[n_reads], G.max_words, J.w, J.k, J.hpc, nullptr, J.w, false, nullptr,
+                                     J.sketch_flt ? *J.sketch_flt : SketchFilter{}}));
+    TRY(K.clock.mark(ctx));
+    std::vector<uint32_t> cnt(n_reads);
+    TRY(download(ctx, cnt.data(), W.mz_cnt, n_reads));
+    FSV_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    for (uint32_t r = 0; r < n_reads; r++) K.entries[read_set[r]] += std::min<uint32_t>(cnt[r], G.mz_off[r + 1] - G.mz_off[r]);
+    for (uint32_t s = 0; s < n_sets; s++) {
+        const uint64_t slots = kmer_table_slots(K.entries[s]), tile = std::min<uint64_t>(slots, FSV_KMER_TILE);
+        K.tab_off[s + 1] = K.tab_off[s] + slots;
+        for (uint64_t f = 0; f < slots; f += tile) K.tiles.push_back(KmerTile{s, (uint32_t)tile, f});
+    }
+    if (K.tiles.size() >= (1ull << 31)) return fsv_fail(ctx, FSV_EUNSUP, "k-mer tables too large for one pass; split the batch");
+    return FSV_OK;
+}
+
+// the sets' tables filled, their histograms on the host
+static int kmer_count(fsv_ctx *ctx, AsmWs &W, KmerRun &K)
+{
+    KmerTableState &S = W.km;
+    const uint32_t n_reads = K.J.sets->n_reads, n_sets = K.J.sets->n_sets;
+    const uint64_t total_slots = K.tab_off[n_sets];
+    std::vector<uint32_t> &h_hist = K.R.hist;
+    h_hist.assign((size_t)n_sets * FSV_KMER_BINS, 0u);
+    TRY(ensure(ctx, S.err, 1));
+    TRY(zero(ctx, S.err, 1));
+    TRY(ensure(ctx, S.cursor, std::max(1u, n_sets)));
+    TRY(zero(ctx, S.cursor, std::max(1u, n_sets)));
+    TRY(upload(ctx, S.tab_off, K.tab_off));
+    if (!total_slots) return FSV_OK;
+    TRY(ensure(ctx, S.keys, total_slots));
+    TRY(ensure(ctx, S.cnt, total_slots));
+    TRY(ensure(ctx, S.hist, h_hist.size()));
+    TRY(upload(ctx, S.tiles, K.tiles));
+    TRY(K.clock.mark(ctx));
+    FSV_HIP(ctx, hipMemsetAsync(S.keys.p, 0xff, total_slots * sizeof(unsigned long long), ctx->stream));   // every slot FSV_KMER_EMPTY
+    TRY(zero(ctx, S.cnt, total_slots));
+    TRY(zero(ctx, S.hist, h_hist.size()));
+    FSV_LAUNCH(ctx, ctx->stream, k_kmer_insert, dim3(n_reads), dim3(256), 0, W.mz.p, W.mz_off.p, W.mz_cnt.p, W.read_set.p, S.tab_off.p, S.keys.p, S.cnt.p, n_reads, S.err.p);
+    FSV_LAUNCH(ctx, ctx->stream, k_kmer_hist, dim3((uint32_t)K.tiles.size()), dim3(256), 0, S.tiles.p, S.tab_off.p, S.keys.p, S.cnt.p, S.hist.p);
+    TRY(K.clock.mark(ctx));
+    uint32_t err = 0;
+    TRY(download(ctx, h_hist.data(), S.hist, h_hist.size()));
+    TRY(download(ctx, &err, S.err, 1));
+    FSV_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (err) return fsv_fail(ctx, FSV_EINTERNAL, "k-mer count table: a set's table ran full");
+    return FSV_OK;
+}
+
+// the verdict per set, and the filter segments the histogram promises
+static void kmer_verdicts(KmerRun &K)
+{
+    const uint32_t n_sets = K.J.sets->n_sets;
+    K.R.sets.resize(n_sets); K.cutoff.resize(n_sets); K.R.flt_off.assign((size_t)n_sets + 1, 0);
+    std::vector<int64_t> h64(FSV_KMER_BINS);
+    for (uint32_t s = 0; s < n_sets; s++) {
+        const uint32_t *h = K.R.hist.data() + (size_t)s * FSV_KMER_BINS;
+        fsv_kmer_set &o = K.R.sets[s];
+        memset(&o, 0, sizeof(o));
+        for (int c = 0; c < FSV_KMER_BINS; c++) { h64[c] = h[c]; o.n_distinct += h[c]; }
+        o.peak_hom = fsv_kmer_peaks_hd(h64.data(), FSV_KMER_BINS, FSV_KMER_START, &o.peak_het, &o.low_i, &o.max_i);
+        o.cutoff = K.cutoff[s] = fsv_kmer_cutoff(o.peak_hom);
+        o.n_entries = K.entries[s];
+        for (int c = 1; c < FSV_KMER_BINS; c++) if (c >= o.cutoff) o.n_filtered += h[c];
+        for (int c = 2; c <= FSV_KMER_BINS - 2; c++) o.n_indexed += (uint64_t)c * h[c];
+        K.R.flt_off[s + 1] = K.R.flt_off[s] + (K.J.sketch_flt ? 0 : o.n_filtered);
+    }
+}
+
+// the filter list: every set's keys at or above its cutoff into its segment of W.km.flt; the stage's last wait for the stream either way
+static int kmer_filter_list(fsv_ctx *ctx, AsmWs &W, KmerRun &K)
+{
+    KmerTableState &S = W.km;
+    const uint32_t n_sets = K.J.sets->n_sets;
+    const uint64_t n_flt = K.R.flt_off[n_sets];
+    if (!n_flt) { FSV_HIP(ctx, hipStreamSynchronize(ctx->stream)); return FSV_OK; }
+    std::vector<uint32_t> cursor(n_sets);
+    TRY(ensure(ctx, S.flt, n_flt));
+    TRY(upload(ctx, S.cutoff, K.cutoff));
+    TRY(upload(ctx, S.flt_off, K.R.flt_off));
+    TRY(K.clock.mark(ctx));
+    FSV_LAUNCH(ctx, ctx->stream, k_kmer_filter, dim3((uint32_t)K.tiles.size()), dim3(256), 0, S.tiles.p, S.tab_off.p, S.keys.p, S.cnt.p, S.cutoff.p, S.flt_off.p, S.cursor.p,
+               S.flt.p, S.err.p);
+    TRY(K.clock.mark(ctx));
+    uint32_t err = 0;
+    TRY(download(ctx, cursor.data(), S.cursor, n_sets));
+    TRY(download(ctx, &err, S.err, 1));
+    FSV_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    for (uint32_t s = 0; s < n_sets; s++) if (cursor[s] != K.R.sets[s].n_filtered) err |= FSV_KMER_E_FLT;
+    if (err) return fsv_fail(ctx, FSV_EINTERNAL, "k-mer count table: the filter pass and the histogram disagree");
+    return FSV_OK;
+}
+
+// (the caller's sets have been checked: check_readsets)
+static int kmer_stage(fsv_ctx *ctx, AsmWs &W, const KmerJob &J, KmerResult &R)
+{
+    KmerRun K{J, R};
+    TRY(kmer_sketch(ctx, W, K));
+    TRY(kmer_count(ctx, W, K));
+    kmer_verdicts(K);
+    TRY(kmer_filter_list(ctx, W, K));
+    if (J.ms) *J.ms += K.clock.ms();
+    return FSV_OK;
+}
+
+// a result's histograms as the callers of fsv_kmer_table / fsv_kmer_index take them: n_sets x FSV_KMER_BINS 64-bit counts
+static void widen_hist(const KmerResult &R, uint64_t *hist) { for (size_t i = 0; i < R.hist.size(); i++) hist[i] = R.hist[i]; }
+
 // The sets' filter sets for the sketch kernels (k_sketch.h), from filter lists on the device: set s's keys are list[list_off[s] ..
 // list_off[s + 1]), any order, duplicates allowed.  skip (or null / empty): sets with a non-zero entry get no slots -- their reads are
-// sketched unfiltered.  Leaves the view in W.flt -- nothing when no set has a slot: every launch then runs the kernels without the
+// sketched unfiltered.  Leaves the view in W.fs.view -- nothing when no set has a slot: every launch then runs the kernels without the
 // filter -- and adds the build's time to *ms.
 static int build_filter_sets(fsv_ctx *ctx, AsmWs &W, const fsv_readsets *sets, const unsigned long long *list, const std::vector<uint64_t> &list_off,
                              const std::vector<uint8_t> *skip, double *ms)
 {
     const uint32_t n_sets = sets->n_sets, n_reads = sets->n_reads;
-    W.flt = SketchFilter{};
+    FilterState &S = W.fs;
+    S.view = SketchFilter{};
     std::vector<uint64_t> set_off((size_t)n_sets + 1, 0);
     for (uint32_t s = 0; s < n_sets; s++)
         set_off[s + 1] = set_off[s] + ((skip && !skip->empty() && (*skip)[s]) ? 0 : flt_set_slots(list_off[s + 1] - list_off[s]));
     const uint64_t total = set_off[n_sets], n_keys = list_off[n_sets];
     if (!total || !n_reads) return FSV_OK;
     if (n_keys >= (1ull << 39)) return fsv_fail(ctx, FSV_EUNSUP, "filter lists too long for one pass; split the batch");
-    std::vector<uint32_t> read_set(n_reads);
-    for (uint32_t s = 0; s < n_sets; s++) for (uint32_t r = sets->set_start[s]; r < sets->set_start[s + 1]; r++) read_set[r] = s;
-    TRY(ensure(ctx, W.fs_keys, total));
-    TRY(upload(ctx, W.fs_off, set_off));
-    TRY(upload(ctx, W.fs_list_off, list_off));
-    TRY(upload(ctx, W.fs_read_set, read_set));
-    TRY(ensure(ctx, W.km_err, 1));
-    TRY(zero(ctx, W.km_err, 1));
-    KmerClock clock(ctx);
-    clock.mark();
-    FSV_HIP(ctx, hipMemsetAsync(W.fs_keys.p, 0xff, total * sizeof(unsigned long long), ctx->stream));   // every slot FSV_KMER_EMPTY
-    FSV_LAUNCH(ctx, ctx->stream, k_flt_build, dim3((uint32_t)((n_keys + 255) / 256)), dim3(256), 0, list, W.fs_list_off.p, W.fs_off.p, n_sets, W.fs_keys.p, W.km_err.p);
-    clock.mark();
+    TRY(ensure(ctx, S.keys, total));
+    TRY(upload(ctx, S.off, set_off));
+    TRY(upload(ctx, S.list_off, list_off));
+    TRY(upload(ctx, S.read_set, read_set_of(sets)));
+    TRY(ensure(ctx, W.km.err, 1));
+    TRY(zero(ctx, W.km.err, 1));
+    EventClock clock;
+    TRY(clock.mark(ctx));
+    FSV_HIP(ctx, hipMemsetAsync(S.keys.p, 0xff, total * sizeof(unsigned long long), ctx->stream));   // every slot FSV_KMER_EMPTY
+    FSV_LAUNCH(ctx, ctx->stream, k_flt_build, dim3((uint32_t)((n_keys + 255) / 256)), dim3(256), 0, list, S.list_off.p, S.off.p, n_sets, S.keys.p, W.km.err.p);
+    TRY(clock.mark(ctx));
     uint32_t err = 0;
-    TRY(download(ctx, &err, W.km_err, 1));
+    TRY(download(ctx, &err, W.km.err, 1));
     FSV_HIP(ctx, hipStreamSynchronize(ctx->stream));
     if (err) return fsv_fail(ctx, FSV_EINTERNAL, "k-mer filter: a filter set ran full");
     if (ms) *ms += clock.ms();
-    W.flt = SketchFilter{W.fs_keys.p, W.fs_off.p, W.fs_read_set.p};
+    S.view = SketchFilter{S.keys.p, S.off.p, S.read_set.p};
     return FSV_OK;
 }
 
-// hifiasm's first ha_pt_gen (htab.cpp:952-998) on the caller's sets: the sketch at (w, k, hpc) through the filter sets in W.flt, counted
+// hifiasm's first ha_pt_gen (htab.cpp:952-998) on the caller's sets: the sketch at (w, k, hpc) through the filter sets in W.fs.view, counted
 // with the count table's own kernels.  out: n_sets records; hist: n_sets x 4096 or null.  A skipped set (see build_filter_sets) is one
 // hifiasm filters every k-mer of: the index of nothing.
 static int index_stage(fsv_ctx *ctx, AsmWs &W, const fsv_readsets *sets, int w, int k, int hpc, const std::vector<uint8_t> *skip, fsv_kmer_index_set *out,
                        uint64_t *hist, double *ms)
 {
-    std::vector<fsv_kmer_set> v(sets->n_sets);
-    std::vector<uint64_t> off;
-    const SketchFilter flt = W.flt;
-    TRY(kmer_stage(ctx, W, sets, w, k, hpc, v.data(), hist, nullptr, 0, nullptr, off, ms, &flt));
+    const SketchFilter flt = W.fs.view;
+    KmerResult R;
+    TRY(kmer_stage(ctx, W, KmerJob{sets, w, k, hpc, &flt, ms}, R));
+    if (hist) widen_hist(R, hist);
+    const std::vector<fsv_kmer_set> &v = R.sets;
     std::vector<int64_t> none(FSV_KMER_BINS, 0);
     for (uint32_t s = 0; s < sets->n_sets; s++) {
         fsv_kmer_index_set &o = out[s];
@@ -1565,43 +1686,50 @@ static int check_sketch_scheme(fsv_ctx *ctx, int w, int k)
     return FSV_OK;
 }
 
-static int check_set_start(fsv_ctx *ctx, const fsv_readsets *sets)
-{
-    if (sets->n_sets == 0) return sets->n_reads == 0 ? FSV_OK : fsv_fail(ctx, FSV_EINVAL, "set_start must span [0, n_reads]");
-    if (sets->set_start[0] != 0 || sets->set_start[sets->n_sets] != sets->n_reads) return fsv_fail(ctx, FSV_EINVAL, "set_start must span [0, n_reads]");
-    for (uint32_t s = 0; s < sets->n_sets; s++) if (sets->set_start[s + 1] < sets->set_start[s]) return fsv_fail(ctx, FSV_EINVAL, "set_start not monotone");
-    return FSV_OK;
-}
-
 static int fsv_kmer_table_impl(fsv_ctx *ctx, const fsv_readsets *sets, int32_t w, int32_t k, int32_t hpc, fsv_kmer_set *out, uint64_t *hist,
                                uint64_t *flt_hash, uint64_t flt_cap, uint64_t *flt_off)
 {
-    if (!ctx || !sets || !sets->store_dev || !sets->word_off || !sets->read_len || !sets->set_start || !out) return FSV_EINVAL;
+    if (!ctx || !readsets_present(sets, true) || !out) return FSV_EINVAL;
     if ((flt_hash == nullptr) != (flt_off == nullptr)) return fsv_fail(ctx, FSV_EINVAL, "fsv_kmer_table: flt_hash and flt_off go together");
     TRY(check_sketch_scheme(ctx, w, k));
-    TRY(check_set_start(ctx, sets));
+    TRY(check_readsets(ctx, sets, RS_ALL));
     FSV_HIP(ctx, hipSetDevice(ctx->device));
     AsmWs &W = *ws_get(ctx);
     W.n_reads = 0; W.cur_store = nullptr;     // (the workspace's read tables are this call's now: nothing for fsv_asm_fetch_reads)
-    std::vector<uint64_t> off;
-    return kmer_stage(ctx, W, sets, w, k, hpc ? 1 : 0, out, hist, flt_hash, flt_cap, flt_off, off, nullptr);
+    const uint32_t n_sets = sets->n_sets;
+    KmerResult R;
+    TRY(kmer_stage(ctx, W, KmerJob{sets, w, k, hpc ? 1 : 0, nullptr, nullptr}, R));
+    if (n_sets) memcpy(out, R.sets.data(), (size_t)n_sets * sizeof(fsv_kmer_set));
+    if (hist) widen_hist(R, hist);
+    if (!flt_off) return FSV_OK;
+    // the caller's copy of the filter list: every set's segment in ascending order
+    const uint64_t n_flt = R.flt_off[n_sets];
+    memcpy(flt_off, R.flt_off.data(), ((size_t)n_sets + 1) * sizeof(uint64_t));
+    if (n_flt > flt_cap) return fsv_fail(ctx, FSV_ECAP, "fsv_kmer_table: flt_hash too small");
+    if (n_flt) {
+        FSV_HIP(ctx, hipMemcpyAsync(flt_hash, W.km.flt.p, n_flt * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+        FSV_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    for (uint32_t s = 0; s < n_sets; s++) std::sort(flt_hash + flt_off[s], flt_hash + flt_off[s + 1]);
+    return FSV_OK;
 }
 
 static int fsv_kmer_index_impl(fsv_ctx *ctx, const fsv_readsets *sets, int32_t w, int32_t k, int32_t hpc, fsv_kmer_set *table, fsv_kmer_index_set *index,
                                uint64_t *hist)
 {
-    if (!ctx || !sets || !sets->store_dev || !sets->word_off || !sets->read_len || !sets->set_start || !table || !index) return FSV_EINVAL;
+    if (!ctx || !readsets_present(sets, true) || !table || !index) return FSV_EINVAL;
     TRY(check_sketch_scheme(ctx, w, k));
-    TRY(check_set_start(ctx, sets));
+    TRY(check_readsets(ctx, sets, RS_ALL));
     FSV_HIP(ctx, hipSetDevice(ctx->device));
     AsmWs &W = *ws_get(ctx);
     W.n_reads = 0; W.cur_store = nullptr;     // (the workspace's read tables are this call's now: nothing for fsv_asm_fetch_reads)
-    std::vector<uint64_t> off;
-    TRY(kmer_stage(ctx, W, sets, 1, k, hpc ? 1 : 0, table, nullptr, nullptr, 0, nullptr, off, nullptr));
+    KmerResult R;
+    TRY(kmer_stage(ctx, W, KmerJob{sets, 1, k, hpc ? 1 : 0, nullptr, nullptr}, R));
+    if (sets->n_sets) memcpy(table, R.sets.data(), (size_t)sets->n_sets * sizeof(fsv_kmer_set));
     // (a set without a peak has cutoff -5: its list holds every k-mer, its sketch comes out empty)
-    TRY(build_filter_sets(ctx, W, sets, W.km_flt.p, off, nullptr, nullptr));
+    TRY(build_filter_sets(ctx, W, sets, W.km.flt.p, R.flt_off, nullptr, nullptr));
     const int rc = index_stage(ctx, W, sets, w, k, hpc ? 1 : 0, nullptr, index, hist, nullptr);
-    W.flt = SketchFilter{};
+    W.fs.view = SketchFilter{};
     return rc;
 }
 
@@ -1609,9 +1737,9 @@ static int fsv_asm_last_kmer_index_impl(const fsv_ctx *ctx, fsv_kmer_index_set *
 {
     if (!ctx || !ctx->asm_ws || (!out && n_sets)) return FSV_EINVAL;
     const AsmWs &W = *(const AsmWs *)ctx->asm_ws;
-    if (!W.ki_valid || W.ki_last.size() != n_sets) return FSV_EINVAL;
-    if (n_sets) memcpy(out, W.ki_last.data(), (size_t)n_sets * sizeof(fsv_kmer_index_set));
-    if (ms) *ms = W.ki_ms;
+    if (!W.fs.valid || W.fs.last.size() != n_sets) return FSV_EINVAL;
+    if (n_sets) memcpy(out, W.fs.last.data(), (size_t)n_sets * sizeof(fsv_kmer_index_set));
+    if (ms) *ms = W.fs.ms;
     return FSV_OK;
 }
 
@@ -1619,9 +1747,9 @@ static int fsv_asm_last_kmer_table_impl(const fsv_ctx *ctx, fsv_kmer_set *out, u
 {
     if (!ctx || !ctx->asm_ws || (!out && n_sets)) return FSV_EINVAL;
     const AsmWs &W = *(const AsmWs *)ctx->asm_ws;
-    if (!W.km_valid || W.km_last.size() != n_sets) return FSV_EINVAL;
-    if (n_sets) memcpy(out, W.km_last.data(), (size_t)n_sets * sizeof(fsv_kmer_set));
-    if (ms) *ms = W.km_ms;
+    if (!W.km.valid || W.km.last.size() != n_sets) return FSV_EINVAL;
+    if (n_sets) memcpy(out, W.km.last.data(), (size_t)n_sets * sizeof(fsv_kmer_set));
+    if (ms) *ms = W.km.ms;
     return FSV_OK;
 }
 
@@ -1629,50 +1757,41 @@ static int fsv_asm_last_kmer_table_impl(const fsv_ctx *ctx, fsv_kmer_set *out, u
 // chunks before left on the context (fsv_assemble_batch_impl cleared it); low[s] = 1 for the sets without a peak.
 static int kmer_stage_of_chunk(fsv_ctx *ctx, AsmWs &W, const fsv_readsets *sets, const fsv_asm_params &P, std::vector<uint8_t> &low)
 {
-    std::vector<fsv_kmer_set> v(sets->n_sets);
-    std::vector<uint64_t> off;
-    TRY(kmer_stage(ctx, W, sets, 1, P.k, P.hpc ? 1 : 0, v.data(), nullptr, nullptr, 0, nullptr, off, &W.km_ms));
+    KmerTableState &S = W.km;
+    KmerResult R;
+    TRY(kmer_stage(ctx, W, KmerJob{sets, 1, P.k, P.hpc ? 1 : 0, nullptr, &S.ms}, R));
+    const std::vector<fsv_kmer_set> &v = R.sets;
+    const std::vector<uint64_t> &off = R.flt_off;
     low.assign(sets->n_sets, 0);
     bool any = false;
     for (uint32_t s = 0; s < sets->n_sets; s++) if (v[s].peak_hom < 0) { low[s] = 1; any = true; }
     if (!any) low.clear();
     // the filter list of the chunks so far, back to back on the device
-    const uint64_t have = W.km_last_flt_off.back(), add = off.back();
-    if (add) {
-        if (W.km_flt_all.cap < (have + add) * sizeof(unsigned long long)) {
-            Dev<unsigned long long> bigger;
-            TRY(ensure(ctx, bigger, (have + add) * 2));
-            if (have) FSV_HIP(ctx, hipMemcpyAsync(bigger.p, W.km_flt_all.p, have * sizeof(unsigned long long), hipMemcpyDeviceToDevice, ctx->stream));
-            FSV_HIP(ctx, hipStreamSynchronize(ctx->stream));
-            W.km_flt_all.swap(bigger);
-        }
-        FSV_HIP(ctx, hipMemcpyAsync(W.km_flt_all.p + have, W.km_flt.p, add * sizeof(unsigned long long), hipMemcpyDeviceToDevice, ctx->stream));
-    }
-    for (uint32_t s = 0; s < sets->n_sets; s++) W.km_last_flt_off.push_back(have + off[s + 1]);
-    W.km_last.insert(W.km_last.end(), v.begin(), v.end());
-    W.km_last_flt = W.km_flt_all.p;
+    const uint64_t have = S.last_flt_off.back();
+    TRY(append_on_device(ctx, S.flt_all, have, S.flt.p, off.back()));
+    for (uint32_t s = 0; s < sets->n_sets; s++) S.last_flt_off.push_back(have + off[s + 1]);
+    S.last.insert(S.last.end(), v.begin(), v.end());
     if (P.kmer_filter) {
         // the chunk's filter sets, which every sketch of its rounds and of its final pass takes; sets without a peak stay as they are
         // (kmer_table leaves them alone).  Then hifiasm's first ha_pt_gen: the filtered sketch at w, counted
-        TRY(build_filter_sets(ctx, W, sets, W.km_flt.p, off, &low, &W.ki_ms));
+        TRY(build_filter_sets(ctx, W, sets, S.flt.p, off, &low, &W.fs.ms));
         std::vector<fsv_kmer_index_set> idx(sets->n_sets);
-        TRY(index_stage(ctx, W, sets, P.w, P.k, P.hpc ? 1 : 0, &low, idx.data(), nullptr, &W.ki_ms));
-        W.ki_last.insert(W.ki_last.end(), idx.begin(), idx.end());
+        TRY(index_stage(ctx, W, sets, P.w, P.k, P.hpc ? 1 : 0, &low, idx.data(), nullptr, &W.fs.ms));
+        W.fs.last.insert(W.fs.last.end(), idx.begin(), idx.end());
     }
     return FSV_OK;
 }
 
-// the chunk's charge counters and stage time join the call's (W.charge_last)
+// the chunk's charge counters and stage time join the call's (W.ch.last)
 static int charge_collect(fsv_ctx *ctx, AsmWs &W)
 {
     unsigned long long h[8] = {0};
-    TRY(download(ctx, h, W.charge_ct, 8));
+    TRY(download(ctx, h, W.ch.ct, 8));
     FSV_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    fsv_charge_stats &c = W.charge_last;
+    fsv_charge_stats &c = W.ch.last;
     c.n_overlaps += h[CH_OVERLAPS]; c.n_windows += h[CH_WINDOWS]; c.n_ext += h[CH_EXT]; c.n_accepted += h[CH_ACCEPTED]; c.n_flipped += h[CH_FLIPPED];
-    for (size_t i = 0; i + 1 < W.charge_ev.size(); i += 2) { float ms = 0; if (hipEventElapsedTime(&ms, W.charge_ev[i], W.charge_ev[i + 1]) == hipSuccess) c.ms += ms; }
-    for (auto e : W.charge_ev) (void)hipEventDestroy(e);
-    W.charge_ev.clear();
+    c.ms += W.ch.clock.ms();
+    W.ch.clock.clear();
     return FSV_OK;
 }
 
@@ -1686,13 +1805,16 @@ static int assemble_chunk(fsv_ctx *ctx, const fsv_readsets *sets, const fsv_asm_
     out->off[0] = 0;
     for (uint32_t s = 0; s < sets->n_sets; s++) out->set_status[s] = 0;
     if (sets->n_sets == 0) return FSV_OK;
+    // (the second level fsv_assemble_batch calls check_readsets from -- here, not at the entry: a chunk's offsets count from its first read, and
+    // a store beyond 2^32 words that is cut so that every chunk stays below is served)
+    TRY(check_readsets(ctx, sets, RS_WORD_OFF));
     if (P.kmer_table) {
         TRY(kmer_stage_of_chunk(ctx, W, sets, P, R.low_cov));
         for (uint32_t s = 0; s < sets->n_sets; s++) if (!R.low_cov.empty() && R.low_cov[s]) out->set_status[s] = FSV_W_LOW_COV | FSV_W_NO_LAYOUT;
     }
     if (sets->n_reads == 0) return FSV_OK;
     TRY(prepare_batch(ctx, W, sets, R));
-    if (P.partial_charge) { TRY(ensure(ctx, W.charge_ct, 8)); TRY(zero(ctx, W.charge_ct, 8)); }
+    if (P.partial_charge) { TRY(ensure(ctx, W.ch.ct, 8)); TRY(zero(ctx, W.ch.ct, 8)); }
     for (R.round = 0; R.round < P.n_rounds; R.round++) {
         TRY(begin_round(ctx, W, R));
         TRY(overlap_stage(ctx, W, R, false));
@@ -1751,7 +1873,7 @@ static int check_asm_params(fsv_ctx *ctx, const fsv_asm_params &P)
 
 static int fsv_assemble_batch_impl(fsv_ctx *ctx, const fsv_readsets *sets, const fsv_asm_params *params, fsv_contigs *out)
 {
-    if (!ctx || !sets || !out || !sets->store_dev || !sets->word_off || !sets->read_len || !sets->set_start) return FSV_EINVAL;
+    if (!ctx || !readsets_present(sets, true) || !out) return FSV_EINVAL;
     if (!out->seq || !out->off || !out->set || !out->n_reads || !out->set_status) return FSV_EINVAL;
     fsv_asm_params P;
     if (params) P = *params; else fsv_asm_default_params(&P);
@@ -1759,16 +1881,11 @@ static int fsv_assemble_batch_impl(fsv_ctx *ctx, const fsv_readsets *sets, const
     FSV_HIP(ctx, hipSetDevice(ctx->device));
     AsmWs &W = *ws_get(ctx);
     out->n_contigs = 0; out->off[0] = 0;
-    // what the k-mer count table stage leaves on the context belongs to this call from here on (its chunks add to it)
-    W.km_last.clear(); W.km_last_flt_off.assign(1, 0); W.km_last_flt = nullptr; W.km_ms = 0; W.km_valid = false;
-    W.flt = SketchFilter{}; W.ki_last.clear(); W.ki_ms = 0; W.ki_valid = false;
-    W.charge_last = fsv_charge_stats{}; W.charge_valid = false;
-    for (auto e : W.charge_ev) (void)hipEventDestroy(e);     // (left by a call that failed half-way)
-    W.charge_ev.clear();
+    // what the opt-in stages leave on the context belongs to this call from here on (its chunks add to it)
+    W.reset_stages();
     // (without reads a kmer_table call still goes on: every set gets its verdict -- no k-mer, no peak)
-    if (sets->n_sets == 0 || (sets->n_reads == 0 && !P.kmer_table)) { for (uint32_t s = 0; s < sets->n_sets; s++) out->set_status[s] = 0; memset(&W.stats, 0, sizeof(W.stats)); W.charge_valid = P.partial_charge != 0; return FSV_OK; }
-    if (sets->set_start[0] != 0 || sets->set_start[sets->n_sets] != sets->n_reads) return fsv_fail(ctx, FSV_EINVAL, "set_start must span [0, n_reads]");
-    for (uint32_t s = 0; s < sets->n_sets; s++) if (sets->set_start[s + 1] < sets->set_start[s]) return fsv_fail(ctx, FSV_EINVAL, "set_start not monotone");
+    if (sets->n_sets == 0 || (sets->n_reads == 0 && !P.kmer_table)) { for (uint32_t s = 0; s < sets->n_sets; s++) out->set_status[s] = 0; memset(&W.stats, 0, sizeof(W.stats)); W.mark_valid(P, false); return FSV_OK; }
+    TRY(check_readsets(ctx, sets, RS_SETS | RS_LEN));   // (the word offsets: per chunk, assemble_chunk)
     // Read sets are independent, so a batch that is too large for one pass -- 32-bit pair / task / offset indices, or a workspace
     // beyond the budget (FSV_ASM_BUDGET_GB, default 40 % of the device's memory: ~200 B per window task (400 with the second consensus pass), ~200 B per read pair,
     // ~48 B per base) -- is cut into runs of consecutive sets that go through one after the other; the caller sees one call.
@@ -1803,7 +1920,7 @@ static int fsv_assemble_batch_impl(fsv_ctx *ctx, const fsv_readsets *sets, const
         }
         cut.push_back(sets->n_sets);
     }
-    if (cut.size() == 2) { TRY(assemble_chunk(ctx, sets, P, out)); W.km_valid = P.kmer_table != 0; W.ki_valid = P.kmer_filter != 0; W.charge_valid = P.partial_charge != 0; return FSV_OK; }
+    if (cut.size() == 2) { TRY(assemble_chunk(ctx, sets, P, out)); W.mark_valid(P, true); return FSV_OK; }
     fsv_asm_stats total; memset(&total, 0, sizeof(total));
     uint64_t used = 0; uint32_t nc = 0;
     std::vector<uint64_t> all_off{0};
@@ -1828,36 +1945,14 @@ static int fsv_assemble_batch_impl(fsv_ctx *ctx, const fsv_readsets *sets, const
         for (uint32_t i = 0; i < part.n_contigs; i++) { out->set[nc + i] += s0; out->off[nc + i + 1] += used; }
         // the contigs stay on the device for the aligner (fsv_align_batch(contig_seq = NULL)): gather the chunks' contigs in one buffer
         const uint64_t bytes = part.n_contigs ? out->off[nc + part.n_contigs] - used : 0;
-        if (bytes) {
-            if (W.contig_all.cap < used + bytes + 16) {
-                Dev<char> bigger;
-                TRY(ensure(ctx, bigger, std::max<uint64_t>((used + bytes) * 2, 1u << 20)));
-                if (used) FSV_HIP(ctx, hipMemcpyAsync(bigger.p, W.contig_all.p, used, hipMemcpyDeviceToDevice, ctx->stream));
-                FSV_HIP(ctx, hipStreamSynchronize(ctx->stream));
-                W.contig_all.swap(bigger);      // (the old allocation goes with `bigger`)
-            }
-            FSV_HIP(ctx, hipMemcpyAsync(W.contig_all.p + used, W.contig_out.p, bytes, hipMemcpyDeviceToDevice, ctx->stream));
-        }
+        TRY(append_on_device(ctx, W.contig_all, used, W.contig_out.p, bytes, 16, 1u << 20));
         used += bytes; nc += part.n_contigs;
-        // statistics: sums over the chunks
-        const fsv_asm_stats &st = W.stats;
-        total.n_pairs += st.n_pairs; total.n_overlaps += st.n_overlaps; total.n_windows += st.n_windows; total.n_windows_matched += st.n_windows_matched;
-        total.n_paths += st.n_paths; total.n_path_dp += st.n_path_dp; total.dp_columns += st.dp_columns; total.algo_bytes += st.algo_bytes;
-        total.n_exact_overlaps += st.n_exact_overlaps; total.n_inexact_candidates += st.n_inexact_candidates; total.n_path_fr += st.n_path_fr;
-        total.ms_sketch += st.ms_sketch; total.ms_chain += st.ms_chain; total.ms_verify += st.ms_verify; total.ms_path += st.ms_path;
-        total.ms_consensus += st.ms_consensus; total.ms_final += st.ms_final; total.ms_total += st.ms_total;
-        total.n_kernels = st.n_kernels;
-        for (uint32_t k = 0; k < st.n_kernels; k++) {
-            memcpy(total.kernels[k].name, st.kernels[k].name, sizeof(st.kernels[k].name));
-            total.kernels[k].ms += st.kernels[k].ms; total.kernels[k].launches += st.kernels[k].launches; total.kernels[k].algo_bytes += st.kernels[k].algo_bytes;
-        }
+        add_stats(total, W.stats);
     }
     FSV_HIP(ctx, hipStreamSynchronize(ctx->stream));
     out->n_contigs = nc;
     W.stats = total;
-    W.km_valid = P.kmer_table != 0;
-    W.ki_valid = P.kmer_filter != 0;
-    W.charge_valid = P.partial_charge != 0;
+    W.mark_valid(P, true);
     W.n_reads = 0; W.cur_store = nullptr;        // fsv_asm_fetch_reads serves single-pass batches only
     ctx->last_contigs_dev = nc ? W.contig_all.p : nullptr;
     ctx->last_contig_off.assign(out->off, out->off + nc + 1);
@@ -1886,10 +1981,10 @@ static int fsv_asm_fetch_reads_impl(fsv_ctx *ctx, char *seq, uint64_t seq_cap, u
 static int fsv_sketch_reads_impl(fsv_ctx *ctx, const fsv_readsets *sets, int32_t w, int32_t k, int32_t hpc, int32_t variant, fsv_mz *out_mz,
                                 uint64_t out_cap, uint64_t *out_off, const uint64_t *flt_hash = nullptr, const uint64_t *flt_off = nullptr)
 {
-    if (!ctx || !sets || !sets->store_dev || !sets->word_off || !sets->read_len || !out_mz || !out_off) return FSV_EINVAL;
+    if (!ctx || !readsets_present(sets, false) || !out_mz || !out_off) return FSV_EINVAL;
     if (flt_hash) {
         if (!flt_off || !sets->set_start) return fsv_fail(ctx, FSV_EINVAL, "fsv_sketch_reads_filtered: flt_hash goes with flt_off and set_start");
-        TRY(check_set_start(ctx, sets));
+        TRY(check_readsets(ctx, sets, RS_SETS));
         if (flt_off[0] != 0) return fsv_fail(ctx, FSV_EINVAL, "fsv_sketch_reads_filtered: flt_off starts at 0");
         for (uint32_t s = 0; s < sets->n_sets; s++) if (flt_off[s + 1] < flt_off[s]) return fsv_fail(ctx, FSV_EINVAL, "fsv_sketch_reads_filtered: flt_off not monotone");
         for (uint64_t i = 0; i < flt_off[sets->n_sets]; i++)
@@ -1902,39 +1997,28 @@ static int fsv_sketch_reads_impl(fsv_ctx *ctx, const fsv_readsets *sets, int32_t
     FSV_HIP(ctx, hipSetDevice(ctx->device));
     AsmWs &W = *ws_get(ctx);
     W.kt.reset();
-    Batch B;
-    B.n_reads = sets->n_reads; B.n_sets = 1; B.n_pairs = 0;
-    B.set_start = {0u, B.n_reads};
+    const uint32_t n_reads = sets->n_reads;
     out_off[0] = 0;
-    if (B.n_reads == 0) return FSV_OK;
-    std::vector<int32_t> len(sets->read_len, sets->read_len + B.n_reads);
-    for (uint32_t r = 0; r < B.n_reads; r++) if (len[r] < 1 || len[r] >= (1 << 24)) return fsv_fail(ctx, FSV_EUNSUP, "read length must be in [1, 2^24)");
+    if (n_reads == 0) return FSV_OK;
+    TRY(check_readsets(ctx, sets, RS_LEN | RS_WORD_OFF));
     Geometry G;
-    TRY(make_geometry(ctx, B, len, G, w));
-    for (uint32_t r = 0; r <= B.n_reads; r++) G.word_off[r] = (uint32_t)sets->word_off[r];
-    TRY(upload(ctx, W.word_off, G.word_off));
-    TRY(upload(ctx, W.len, len));
-    TRY(upload(ctx, W.mz_off, G.mz_off));
-    TRY(ensure(ctx, W.warn, B.n_reads));
-    TRY(zero(ctx, W.warn, B.n_reads));
-    TRY(ensure(ctx, W.mz, G.mz_off[B.n_reads]));
-    TRY(ensure(ctx, W.mz_cnt, B.n_reads));
-    W.flt = SketchFilter{};
+    TRY(stage_sketch_reads(ctx, W, sets, w, nullptr, G));
+    W.fs.view = SketchFilter{};
     if (flt_hash && flt_off[sets->n_sets]) {    // the caller's lists -> the filter sets, as kmer_stage_of_chunk builds them from the stage's list
         const std::vector<uint64_t> list_off(flt_off, flt_off + sets->n_sets + 1);
-        TRY(ensure(ctx, W.fs_list, list_off.back()));
-        FSV_HIP(ctx, hipMemcpyAsync(W.fs_list.p, flt_hash, list_off.back() * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
-        TRY(build_filter_sets(ctx, W, sets, W.fs_list.p, list_off, nullptr, nullptr));
+        TRY(ensure(ctx, W.fs.list, list_off.back()));
+        FSV_HIP(ctx, hipMemcpyAsync(W.fs.list.p, flt_hash, list_off.back() * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
+        TRY(build_filter_sets(ctx, W, sets, W.fs.list.p, list_off, nullptr, nullptr));
     }
-    const SketchFilter flt = W.flt;
-    W.flt = SketchFilter{};
+    const SketchFilter flt = W.fs.view;
+    W.fs.view = SketchFilter{};
     // variant 1: the replay kernel for an odd k as well (by itself the launch picks the kernel by the parity of k)
-    TRY(launch_sketch(ctx, W, SketchJob{sets->store_dev, B.n_reads, G.word_off[B.n_reads], G.max_words, w, k, hpc, nullptr, w, variant == 1, nullptr, flt}));
-    std::vector<uint32_t> cnt(B.n_reads);
-    TRY(download(ctx, cnt.data(), W.mz_cnt, B.n_reads));
+    TRY(launch_sketch(ctx, W, SketchJob{sets->store_dev, n_reads, G.word_off[n_reads], G.max_words, w, k, hpc, nullptr, w, variant == 1, nullptr, flt}));
+    std::vector<uint32_t> cnt(n_reads);
+    TRY(download(ctx, cnt.data(), W.mz_cnt, n_reads));
     FSV_HIP(ctx, hipStreamSynchronize(ctx->stream));
     uint64_t tot = 0;
-    for (uint32_t r = 0; r < B.n_reads; r++) {
+    for (uint32_t r = 0; r < n_reads; r++) {
         const uint32_t c = std::min<uint32_t>(cnt[r], G.mz_off[r + 1] - G.mz_off[r]);
         if (tot + c > out_cap) return fsv_fail(ctx, FSV_ECAP, "out_mz too small");
         FSV_HIP(ctx, hipMemcpyAsync(out_mz + tot, W.mz.p + G.mz_off[r], (size_t)c * sizeof(fsv_mz), hipMemcpyDeviceToHost, ctx->stream));
@@ -1942,7 +2026,7 @@ static int fsv_sketch_reads_impl(fsv_ctx *ctx, const fsv_readsets *sets, int32_t
         out_off[r + 1] = tot;
     }
     FSV_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    for (uint32_t r = 0; r < B.n_reads; r++)
+    for (uint32_t r = 0; r < n_reads; r++)
         std::sort(out_mz + out_off[r], out_mz + out_off[r + 1], [](const fsv_mz &a, const fsv_mz &b) { return a.pos < b.pos; });
     return FSV_OK;
 }
@@ -1953,21 +2037,20 @@ static int fsv_asm_overlaps_impl(fsv_ctx *ctx, const fsv_readsets *sets, const f
                                  uint32_t n_rechain, fsv_ovl *ovl, uint64_t ovl_cap, uint32_t *pair_base, fsv_wtask *tasks, uint64_t task_cap,
                                  uint32_t *n_tasks, uint32_t *overflow, uint32_t *warn)
 {
-    if (!ctx || !sets || !sets->store_dev || !sets->word_off || !sets->read_len || !sets->set_start || !pair_base || !n_tasks || !overflow || !warn) return FSV_EINVAL;
+    if (!ctx || !readsets_present(sets, true) || !pair_base || !n_tasks || !overflow || !warn) return FSV_EINVAL;
     if (pass < 0 || pass > 2 || (n_rechain && (pass != 2 || !rechain)) || (ovl_cap && !ovl) || (task_cap && !tasks)) return fsv_fail(ctx, FSV_EINVAL, "fsv_asm_overlaps: pass is 0, 1 or 2; a pair list goes with pass 2");
     fsv_asm_params P;
     if (params) P = *params; else fsv_asm_default_params(&P);
     TRY(check_asm_params(ctx, P));
     if (pass > 0) P.n_rounds = 0;     // a final pass with no round before it: every read is sketched, no verdict of an earlier round
     if (sets->n_reads == 0 || sets->n_sets == 0) return fsv_fail(ctx, FSV_EINVAL, "fsv_asm_overlaps: no reads");
-    if (sets->set_start[0] != 0 || sets->set_start[sets->n_sets] != sets->n_reads) return fsv_fail(ctx, FSV_EINVAL, "set_start must span [0, n_reads]");
-    for (uint32_t s = 0; s < sets->n_sets; s++) if (sets->set_start[s + 1] < sets->set_start[s]) return fsv_fail(ctx, FSV_EINVAL, "set_start not monotone");
+    TRY(check_readsets(ctx, sets, RS_ALL));
     FSV_HIP(ctx, hipSetDevice(ctx->device));
     AsmWs &W = *ws_get(ctx);
     memset(&W.stats, 0, sizeof(W.stats));
     W.kt.reset();
     W.n_reads = 0; W.cur_store = nullptr;     // (nothing here for fsv_asm_fetch_reads)
-    W.flt = SketchFilter{};                   // (the hook runs no k-mer count table stage: kmer_filter finds nothing to take)
+    W.fs.view = SketchFilter{};               // (the hook runs no k-mer count table stage: kmer_filter finds nothing to take)
     Round R(P);
     TRY(prepare_batch(ctx, W, sets, R));
     const Batch &B = R.B;

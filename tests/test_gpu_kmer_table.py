@@ -136,6 +136,51 @@ def test_verdicts_of_a_call_cut_into_chunks_come_in_set_order(ctx, lowcov, monke
     assert ms > 0.0
 
 
+def assemble_all_stages(ctx, sets, on):
+    """assemble_batch with kmer_table = kmer_filter = partial_charge = on -> (contigs per set, statuses, what the three getters say: the
+    records and the time of each, or the FsvError of a getter that refuses)"""
+    b = pack_sets(sets)
+    d = ctx.upload(b.words)
+    try:
+        p = ctx.default_asm_params()
+        p.kmer_table = p.kmer_filter = p.partial_charge = on
+        contigs, cset, _, status = ctx.assemble_batch(d, b.word_off, b.read_len, b.set_start, p)
+    finally:
+        ctx.dev_free(d)
+    left = []
+    for getter in (lambda: ctx.last_kmer_table(b.n_sets), lambda: ctx.last_kmer_index(b.n_sets), ctx.last_charge):
+        try:
+            left.append(getter())
+        except _lib.FsvError as e:
+            left.append(e)
+    return [[c for c, cs in zip(contigs, cset) if cs == s] for s in range(len(sets))], [int(x) for x in status], left
+
+
+def test_three_stages_of_a_call_cut_into_chunks(ctx, lowcov, monkeypatch):
+    """kmer_table, kmer_filter and partial_charge together on the six sets of the test above, whole and with every set in a chunk of its own
+    (fsv_asm_fetch_reads refusing proves the cut): the chunk loop with the filter sets, the appended filter list and the charge clock alive
+    at once leaves what the single pass leaves; a call with the three options off then leaves every getter refusing"""
+    _, all_sets = lowcov
+    sets = [all_sets[i] for i in (0, 1, 10, 11, 20, 21)]
+    n_reads = sum(len(s) for s in sets)
+    counters = ("n_overlaps", "n_windows", "n_ext", "n_accepted", "n_flipped")
+    whole, status_w, (table_w, index_w, charge_w) = assemble_all_stages(ctx, sets, 1)
+    ctx.fetch_reads(n_reads, sum(len(r) for s in sets for r in s) * 2 + 1024)       # (one pass: its reads are there)
+    monkeypatch.setenv("FSV_ASM_BUDGET_GB", "0.03")
+    cut, status_c, (table_c, index_c, charge_c) = assemble_all_stages(ctx, sets, 1)
+    with pytest.raises(_lib.FsvError) as e:
+        ctx.fetch_reads(n_reads, sum(len(r) for s in sets for r in s) * 2 + 1024)
+    assert e.value.code == _lib.EINVAL and "fsv_asm_fetch_reads" in str(e.value)
+    print("whole:", table_w[1], index_w[1], charge_w, "cut:", table_c[1], index_c[1], charge_c)
+    assert cut == whole and status_c == status_w
+    assert table_c[0].tobytes() == table_w[0].tobytes() and index_c[0].tobytes() == index_w[0].tobytes()
+    assert [charge_c[n] for n in counters] == [charge_w[n] for n in counters]
+    for ms in (table_w[1], index_w[1], charge_w["ms"], table_c[1], index_c[1], charge_c["ms"]):
+        assert ms > 0.0
+    _, _, left = assemble_all_stages(ctx, sets, 0)
+    assert [isinstance(x, _lib.FsvError) and x.code for x in left] == [_lib.EINVAL] * 3
+
+
 def edge_sets():
     rng = random.Random(5)
     rand = lambda n: "".join(rng.choice("ACGT") for _ in range(n)).encode()

@@ -290,3 +290,37 @@ def test_capacity_one_short_is_ecap(ctx):
         assert sum(len(g) for g in got) == need
         for c, g in zip(cases, got):
             assert _diff(g, _oracle(gp, c)) is None, (gp, variant, c["kind"], c["tag"])
+
+
+def _raw_sketch(ctx, store_dev, word_off, lens, w, k, hpc, cap=64):
+    """the C entry fsv_sketch_reads itself, the caller's word_off handed through as it is -> (rc, message, per-read minimizers)"""
+    word_off = np.ascontiguousarray(word_off, dtype=np.uint64)
+    ss = np.asarray([0, len(lens)], dtype=np.uint32)
+    rs = _lib.ReadSets(_lib.C.c_void_p(store_dev), _lib._ptr(word_off).value, _lib._ptr(lens).value, _lib._ptr(ss).value, len(lens), 1)
+    out = np.zeros(cap, dtype=_lib.MZ_DTYPE)
+    off = np.zeros(len(lens) + 1, dtype=np.uint64)
+    rc = ctx._lib.fsv_sketch_reads(ctx._h, _lib.C.byref(rs), w, k, hpc, 0, _lib._ptr(out), cap, _lib._ptr(off))
+    return rc, ctx._lib.fsv_last_error(ctx._h).decode(), [out[int(off[i]):int(off[i + 1])].copy() for i in range(len(lens))]
+
+
+def test_word_off_beyond_32_bits_is_refused(ctx):
+    """one read of 16 bases whose word_off array ends at 2^32: FSV_EUNSUP before anything is launched (no large allocation is needed: no word
+    is read), as fsv_assemble_batch and fsv_kmer_table answer; the same read at word_off [0, 1] afterwards, on the same context, gives the
+    oracle's sketch.  (Before the read-set checks were made one function the first call returned FSV_OK: 2^32 was cut to 32 bits, 0, and the
+    kernel sketched through the offsets [0, 0] -- for this one read the right words by accident.)"""
+    seq, (w, k, hpc) = "ACGTTGCATGGATCCA", (3, 5, 0)
+    words, off, lens = _lib.pack_reads([seq])
+    assert [int(x) for x in off] == [0, 1]
+    want = O.sketch(seq, w, k, hpc)
+    assert len(want) > 0
+    d = ctx.upload(words)
+    try:
+        rc, msg, got = _raw_sketch(ctx, d, [0, 1 << 32], lens, w, k, hpc)
+        print("word_off [0, 2^32]: rc", rc, repr(msg), [(int(m["hash"]), int(m["pos"])) for m in got[0]])
+        assert rc == _lib.EUNSUP and msg == "store larger than 2^32 words; split the batch", (rc, msg)
+        rc, msg, got = _raw_sketch(ctx, d, off, lens, w, k, hpc)
+        print("word_off [0, 1]: rc", rc, [(int(m["hash"]), int(m["pos"])) for m in got[0]])
+        assert rc == _lib.OK
+    finally:
+        ctx.dev_free(d)
+    assert _diff(got[0], want) is None
