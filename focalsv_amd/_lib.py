@@ -32,7 +32,7 @@ assert OVL_DTYPE.itemsize == 56
 class AsmParams(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("k", "w", "hpc", "n_rounds", "min_ovlp", "min_anchors", "lookback", "bw_ec", "bw_final",
                                          "min_contig_reads", "win_rate_pm", "k_cap", "accept_err_pm", "bw_rechain", "w_later", "partition", "second_round", "ins_dag",
-                                         "min_anchors_final", "min_ovlp_final", "graph_layout", "junction_cigars", "kmer_filter", "kmer_table", "partial_charge")]
+                                         "min_anchors_final", "min_ovlp_final", "graph_layout", "junction_cigars", "full_lists", "kmer_filter", "kmer_table", "partial_charge")]
 
 
 class ReadSets(C.Structure):
@@ -160,6 +160,8 @@ def load():
         "fsv_sketch_reads": (C.c_int, [vp, C.POINTER(ReadSets), C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, C.c_uint64, vp]),
         "fsv_asm_overlaps": (C.c_int, [vp, C.POINTER(ReadSets), C.POINTER(AsmParams), C.c_int32, vp, C.c_uint32, vp, C.c_uint64, vp, vp, C.c_uint64,
                                        u32p, u32p, vp]),
+        "fsv_asm_last_long_lists": (C.c_int, [vp, vp, vp]),
+        "fsv_read_index": (C.c_int, [vp, C.POINTER(ReadSets), C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, C.c_uint64, vp, vp]),
         "fsv_sketch_reads_filtered": (C.c_int, [vp, C.POINTER(ReadSets), C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, C.c_uint64, vp, vp, vp]),
         "fsv_kmer_index": (C.c_int, [vp, C.POINTER(ReadSets), C.c_int32, C.c_int32, C.c_int32, vp, vp, vp]),
         "fsv_asm_last_kmer_index": (C.c_int, [vp, vp, C.c_uint32, C.POINTER(C.c_double)]),
@@ -417,6 +419,20 @@ class Context:
         self.check(self._lib.fsv_sketch_reads(self._h, C.byref(rs), w, k, hpc, variant, _ptr(out), cap, _ptr(off)), "fsv_sketch_reads")
         return [out[int(off[i]):int(off[i + 1])].copy() for i in range(len(read_len))]
 
+    def read_index(self, store_dev, word_off, read_len, w=51, k=51, hpc=1, full_lists=0):
+        """fsv_read_index (test hook): per read the index the chain kernels see -- 2m entries, [0, m) by hash, [m, 2m) by position -- and the
+        reads' warning bits -> (list of structured arrays, warn[n_reads])"""
+        word_off = np.ascontiguousarray(word_off, dtype=np.uint64)
+        read_len = np.ascontiguousarray(read_len, dtype=np.int32)
+        ss = np.asarray([0, len(read_len)], dtype=np.uint32)
+        rs = ReadSets(C.c_void_p(store_dev), _ptr(word_off).value, _ptr(read_len).value, _ptr(ss).value, len(read_len), 1)
+        cap = 2 * int(read_len.sum()) + 64 * len(read_len) + 64
+        out = np.zeros(max(cap, 1), dtype=MZ_DTYPE)
+        off = np.zeros(len(read_len) + 1, dtype=np.uint64)
+        warn = np.zeros(max(1, len(read_len)), dtype=np.uint32)
+        self.check(self._lib.fsv_read_index(self._h, C.byref(rs), w, k, hpc, int(full_lists), _ptr(out), cap, _ptr(off), _ptr(warn)), "fsv_read_index")
+        return [out[int(off[i]):int(off[i + 1])].copy() for i in range(len(read_len))], warn[: len(read_len)]
+
     def sketch_reads_filtered(self, store_dev, word_off, read_len, set_start, filters, w=51, k=51, hpc=1, variant=0, out_cap=None):
         """fsv_sketch_reads_filtered: the sketch through the sets' high-count k-mer filters.  filters: one sequence of uint64 hashes per
         read set (any order, duplicates allowed), or None for no lists at all -> per read its minimizers, as sketch_reads"""
@@ -524,6 +540,9 @@ class Context:
         out = {n: getattr(st, n) for n, _ in AsmStats._fields_ if n not in ("kernels", "pad", "n_kernels")}
         out["kernels"] = {st.kernels[i].name.decode(): {"ms": st.kernels[i].ms, "launches": st.kernels[i].launches,
                                                         "algo_bytes": st.kernels[i].algo_bytes} for i in range(st.n_kernels)}
+        nr, np_ = C.c_uint64(0), C.c_uint64(0)      # full_lists = 1: what the two long-read kernels took (0, 0 otherwise)
+        self.check(self._lib.fsv_asm_last_long_lists(self._h, C.byref(nr), C.byref(np_)), "fsv_asm_last_long_lists")
+        out["n_long_list_reads"], out["n_spilled_pairs"] = int(nr.value), int(np_.value)
         return out
 
     def fetch_reads(self, n_reads, total_cap):

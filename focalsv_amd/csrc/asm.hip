@@ -18,10 +18,13 @@
 
 namespace {
 
-enum { KN_SKETCH, KN_UNIQ, KN_CHAIN, KN_BPM, KN_RESCUE, KN_PATH_FAST, KN_PATH_DP, KN_CONSENSUS, KN_REPACK, KN_EXACT, KN_STITCH, KN_PARTITION, KN_BND, KN_BND_CONS, KN_COUNT,
+enum { KN_SKETCH, KN_UNIQ, KN_CHAIN, KN_BPM, KN_RESCUE, KN_PATH_FAST, KN_PATH_DP, KN_CONSENSUS, KN_REPACK, KN_EXACT, KN_STITCH, KN_PARTITION, KN_BND, KN_BND_CONS,
+       KN_UNIQ_LONG, KN_CHAIN_SPILL,   // full_lists = 1: timed on their own, outside the k_uniq / k_chain groups
+       KN_COUNT,
        ST_SKETCH = KN_COUNT, ST_CHAIN, ST_VERIFY, ST_PATH, ST_CONSENSUS, ST_FINAL };
 const char *const kn_names[KN_COUNT] = {"k_sketch", "k_uniq", "k_chain", "k5_bpm", "k_rescue_accept", "k_path_fast", "k_path_dp", "k_consensus",
-                                        "k_repack", "k_exact", "k_stitch", "k_partition", "k_bnd_tasks", "k_bnd_consensus"};
+                                        "k_repack", "k_exact", "k_stitch", "k_partition", "k_bnd_tasks", "k_bnd_consensus", "k_uniq_long", "k_chain_spill"};
+static_assert(KN_COUNT <= FSV_MAX_KERNEL_STATS, "fsv_asm_stats holds every kernel's row");
 // the task lists of a round: its window tasks, the junction tasks of its second consensus pass, the junction cigars of its partition
 // (PASS_NONE: a list outside a batch -- fsv_bpm_paths).  Pass p of round r keeps its device counters in row p (n_rounds + 1) + r.
 enum { PASS_NONE = -1, PASS_WINDOWS, PASS_JUNCTIONS, PASS_BCIG, PASS_COUNT };
@@ -73,7 +76,10 @@ enum { CT_TASKS = 0, CT_OVERFLOW = 1, CT_DP = 2, CT_INEXACT = 3, CT_COLS_LO = 4,
        CT_DP_FR3 = 20,       // k_path_fr's lists by distance: CT_DP_SB16 (1), CT_DP (2), CT_DP_FR3 (3)
        CT_LEFT = 21,         // overlaps set aside for the left-extension rescue pass (k_left_rescue)
        CT_FIX = 22, CT_FIXED = 23,   // fix_boundary's candidates (k_path_fast) and the windows it moved
-       CT_SLOT = 24 };      // even: the 64-bit sums stay aligned in every slot
+       CT_SPILL = 24,        // full_lists = 1: pairs set aside for k_chain_spill (more anchors than the tile in use)
+       CT_SPILLED = 25,      // ... summed over the pass's launches (the re-chain starts the list again for either side)
+       CT_UQ_LONG = 26,      // full_lists = 1: reads whose list k_uniq_long indexed
+       CT_SLOT = 28 };      // even: the 64-bit sums stay aligned in every slot
 
 template <class... Ts> size_t cap_sum(const Ts &...b) { return (b.cap + ... + 0); }
 
@@ -125,6 +131,7 @@ struct AsmWs {
     Dev<fsv_mz> mz; Dev<fsv_ovl> ovl, ovl_prev; Dev<fsv_hit> hits, hits_packed; Dev<fsv_piece> pieces; Dev<BndPatch> bnd_patch;
     Dev<fsv_wtask> tasks, tasks2, tasks3; Dev<fsv_wres> res, res2, res3; Dev<fsv_wpath> paths, paths2;
     Dev<uint4> cols_sb, ovl_c, upair_tab, upair_tab_sw, gwin_tab, bc_rec; Dev<uint2> site_rec; Dev<int8_t> site_vec;
+    Dev<uint4> uq_ws, spill_list; Dev<uint8_t> spill_slab;   // full_lists = 1: k_uniq_long's merge buffers; the pairs set aside for k_chain_spill, its slabs
     Dev<uint64_t> cols;          // k_path_dp's column scratch: 64-bit columns, or 32-bit ones in the same bytes
     Dev<unsigned long long> tmp; // cycle stamps of the diagnostic runs
     Dev<uint8_t> cov3, bnd_bytes, exact_flag, cwin, thr_tab; Dev<uint16_t> cwin_len; Dev<char> contig_out, contig_all;
@@ -140,6 +147,7 @@ struct AsmWs {
     const uint32_t *cur_store = nullptr;
     uint32_t n_reads = 0;
     fsv_asm_stats stats;
+    uint64_t n_long_reads = 0, n_spilled_pairs = 0;   // full_lists = 1, last call, all rounds and chunks: lists k_uniq_long indexed, pairs k_chain_spill chained
     KTimes kt;
     void *h_pin = nullptr; size_t h_pin_cap = 0; // pinned host staging (exact hits)
     uint32_t *ct_of(int row) { return counters.p + (size_t)row * CT_SLOT; }   // a row of the counter block (valid until counters grows)
@@ -151,7 +159,7 @@ struct AsmWs {
                        site_cursor, redo, site_lists, read_dirty, cov3, lb, sr_store, brel_off, tasks2, res2, paths2, idx2, bc_idx, bc_rec, bc_win, left_list, fix_list,
                        tasks3, res3, src3, bnd_flag, bnd_list, bnd_patch, bnd_bytes, changed, pair_read, wide_list, cols, tmp, gwin_off, gwin_read, sk_ends, sk_low, sk_high,
                        hits, hits_packed, set_hits, ovl_prev, exact_flag, inexact_list, upair_base, upair_tab, upair_tab_sw, ovl_c, gwin_tab, cwin, cwin_len, warn, thr_tab,
-                       pieces, contig_out, new_len, unpack_off) + km.held() + fs.held() + ch.held();
+                       pieces, contig_out, new_len, unpack_off, uq_ws, spill_list, spill_slab) + km.held() + fs.held() + ch.held();
     }
     // the opt-in stages' state between two calls of fsv_assemble_batch: forgotten when a call begins, valid when it ends well.  stages_ran:
     // false for a call that returned before its first chunk (no set, or no read and no kmer_table) -- the k-mer getters then go on refusing
@@ -198,9 +206,12 @@ struct Geometry {
 
 // minimizer slots of a read: the worst case is one per base (inside a long homopolymer or a short-unit tandem repeat every
 // k-mer ties with the window minimum and ha_sketch reports all of them); 16 B x bases is 2 % of HBM for 256 regions
-static inline uint64_t mz_slots(int64_t len, int) { return (uint64_t)len + 64; }
+// full_lists = 1 with w <= 2: the index holds every unique minimizer twice, and with such a window more than half the bases can be one, so the
+// slot gets that room too (with larger windows 2m stays below len + 64, and the default path keeps the slots it had)
+static inline uint64_t mz_slots(int64_t len, int w, bool full_lists = false) { return (uint64_t)len + 64 + (full_lists && w <= 2 ? (uint64_t)len : 0); }
 
-int make_geometry(fsv_ctx *ctx, const Batch &B, const std::vector<int32_t> &len, Geometry &G, int mz_w = 51, const std::vector<uint32_t> *fixed_mz_off = nullptr)
+int make_geometry(fsv_ctx *ctx, const Batch &B, const std::vector<int32_t> &len, Geometry &G, int mz_w = 51, const std::vector<uint32_t> *fixed_mz_off = nullptr,
+                  bool full_lists = false)
 {
     G.word_off.assign(B.n_reads + 1, 0); G.mz_off.assign(B.n_reads + 1, 0); G.gwin_off.assign(B.n_reads + 1, 0);
     G.max_words = 1;
@@ -209,7 +220,7 @@ int make_geometry(fsv_ctx *ctx, const Batch &B, const std::vector<int32_t> &len,
         G.word_off[r] = (uint32_t)w; G.mz_off[r] = (uint32_t)m; G.gwin_off[r] = (uint32_t)g;
         w += (uint64_t)(len[r] + 15) / 16;
         G.max_words = std::max<uint32_t>(G.max_words, (uint32_t)((len[r] + 15) / 16));
-        m += mz_slots(len[r], mz_w);
+        m += mz_slots(len[r], mz_w, full_lists);
         g += (uint64_t)(len[r] + FSV_WINDOW - 1) / FSV_WINDOW;
     }
     if (w + 4 >= (1ull << 32) || m >= (1ull << 32) || g >= (1ull << 32)) return fsv_fail(ctx, FSV_EUNSUP, "batch too large for 32-bit offsets; split it");
@@ -282,6 +293,34 @@ int chain_wide_pairs(fsv_ctx *ctx, const ChainArgs &A, bool short_reads, uint32_
     return launch_chain(ctx, CHAIN_WIDE_LIST, short_reads, std::min<uint32_t>(n_upairs, 2u * (uint32_t)ctx->n_cu), AW, n_upairs);
 }
 
+// full_lists = 1: the pairs the launches above set aside because their anchors exceed the tile (A.spill_list), chained in HBM slabs and timed on
+// their own (KN_CHAIN_SPILL).  max_slot: the batch's longest minimizer slot; an index takes at most half of it and a pair has at most min(nq, nt)
+// anchors, so a slab holds max_slot / 2 + 64.  A small fixed grid: FSV_SPILL_GRID slabs of 32 B an anchor (1.8 MB each for a 100 kb read) stay in
+// L2 and are under a thousandth of the workspace budget.  The list's length is on the device only, so the launch is unconditional: with an
+// empty list every block reads the count and returns
+int chain_spilled_pairs(fsv_ctx *ctx, AsmWs &W, const ChainArgs &A, uint32_t n_upairs, uint32_t max_slot, uint32_t *ct)
+{
+    if (!A.spill_list) return FSV_OK;
+    const uint32_t grid = std::min<uint32_t>(std::max(1u, n_upairs), FSV_SPILL_GRID), slab_cap = max_slot / 2 + 64;
+    TRY(ensure(ctx, W.spill_slab, (size_t)grid * slab_cap * FSV_SPILL_BYTES));
+    const size_t it = W.kt.begin(ctx, KN_CHAIN_SPILL, 0);
+    FSV_LAUNCH(ctx, ctx->stream, k_chain_spill, dim3(grid), dim3(64), 0, A, W.spill_slab.p, slab_cap, ct + CT_SPILLED);
+    W.kt.end(ctx, it);
+    return FSV_OK;
+}
+static uint32_t longest_slot(const Geometry &G, uint32_t n_reads)
+{
+    uint32_t m = 64;
+    for (uint32_t r = 0; r < n_reads; r++) m = std::max(m, G.mz_off[r + 1] - G.mz_off[r]);
+    return m;
+}
+static uint32_t reads_above(const std::vector<int32_t> &len, int32_t bases)
+{
+    uint32_t n = 0;
+    for (int32_t l : len) n += l > bases;
+    return n;
+}
+
 // sketch + per-read index + chaining on the current store; fills ws.ovl (and, in a correction round, ws.tasks).  Nothing here waits
 // for the GPU: launches are sized from the read lengths the host already has, counts stay in the counter row R.ct.
 int overlap_stage(fsv_ctx *ctx, AsmWs &W, const Round &R, bool final_pass)
@@ -309,16 +348,14 @@ int overlap_stage(fsv_ctx *ctx, AsmWs &W, const Round &R, bool final_pass)
     TRY(launch_sketch(ctx, W, SketchJob{R.store, B.n_reads, G.word_off[B.n_reads], G.max_words, w, P.k, P.hpc, nullptr, w, false, only_changed,
                                      P.kmer_filter ? W.fs.view : SketchFilter{}}));   // (every round and the final pass: the one filter of the raw reads, as ha_flt_tab)
     W.kt.end(ctx);
-    // the sort in k_uniq holds a read's minimizers in LDS (16 B per entry): one instantiation for lists up to 1 024 entries (many
-    // reads per CU), one for longer ones; each launch skips the reads of the other size class, so the host need not know the
-    // longest list of the batch (round 1 read the counts back to choose)
     unsigned long long *mz_total = (unsigned long long *)(ct + CT_MZ_LO);
+    const uint32_t max_slot = P.full_lists ? longest_slot(G, B.n_reads) : 0u;
     W.kt.begin(ctx, PASS_WINDOWS, KN_UNIQ, 0);
-    FSV_LAUNCH(ctx, ctx->stream, k_uniq<1024>, dim3(B.n_reads), dim3(256), 0, W.mz.p, W.mz_off.p, W.mz_cnt.p, W.warn.p, only_changed, 0u, 1024u, mz_total);
-    if (G.max_words * 16u > 1024u)   // at most one minimizer per base: shorter reads cannot have a longer list
-        FSV_LAUNCH(ctx, ctx->stream, k_uniq_walk<FSV_UQ_MAX>, dim3(std::min<uint32_t>(B.n_reads, 2u * (uint32_t)ctx->n_cu)), dim3(256), 0, W.mz.p, W.mz_off.p,
-                   W.mz_cnt.p, W.warn.p, only_changed, 1024u, 0xffffffffu, mz_total, B.n_reads);
-    W.kt.end(ctx);
+    size_t t_long = 0; bool long_timed = false;
+    TRY(launch_uniq(ctx, W, UniqJob{B.n_reads, G.max_words, only_changed, mz_total, P.full_lists != 0, max_slot, P.full_lists ? reads_above(R.len, FSV_UQ_MAX) : 0u, ct + CT_UQ_LONG},
+                    [&] { W.kt.end(ctx); t_long = W.kt.begin(ctx, KN_UNIQ_LONG, 0); long_timed = true; }));   // (the long class: timed on its own)
+    if (long_timed) W.kt.end(ctx, t_long);
+    else W.kt.end(ctx);
     ts.stop();
     if (B.n_pairs == 0) return FSV_OK;
     Span tc(ctx, W.kt, ST_CHAIN);
@@ -340,6 +377,12 @@ int overlap_stage(fsv_ctx *ctx, AsmWs &W, const Round &R, bool final_pass)
         TRY(ensure(ctx, W.wide_list, (size_t)B.n_upairs + 4));
         A.wide_list = W.wide_list.p; A.n_wide = ct + CT_WIDE;
     }
+    // full_lists = 1: a pair with more anchors than the tile in use is set aside, not cut (the counter is the round's own and zeroed with its row)
+    A.spill_list = nullptr; A.n_spill = nullptr;
+    if (P.full_lists) {
+        TRY(ensure(ctx, W.spill_list, (size_t)B.n_upairs + 4));
+        A.spill_list = W.spill_list.p; A.n_spill = ct + CT_SPILL;
+    }
     A.stamps = nullptr;
     if (getenv("FSV_CHAIN_STAMPS")) {   // diagnostic: where a k_chain wave spends its cycles (never in a measured run)
         TRY(ensure(ctx, W.tmp, 16));
@@ -352,6 +395,7 @@ int overlap_stage(fsv_ctx *ctx, AsmWs &W, const Round &R, bool final_pass)
     TRY(launch_chain(ctx, CHAIN_CHUNKS, R.short_reads, n_chunks, A, B.n_upairs));
     if (A.wide_list) TRY(chain_wide_pairs(ctx, A, R.short_reads, B.n_upairs));
     W.kt.end(ctx);
+    TRY(chain_spilled_pairs(ctx, W, A, B.n_upairs, max_slot, ct));
     if (A.stamps) {
         unsigned long long h[16];
         TRY(download(ctx, h, W.tmp, 16));
@@ -445,6 +489,7 @@ extern "C" void fsv_asm_default_params(fsv_asm_params *p)
     p->bw_ec = 20; p->bw_final = 0; p->min_contig_reads = 4;
     p->win_rate_pm = 40; p->k_cap = FSV_K_MAX; p->accept_err_pm = 30; p->bw_rechain = 1; p->w_later = 0; p->partition = 1; p->second_round = 1; p->ins_dag = 1;
     p->min_anchors_final = 1; p->min_ovlp_final = 1; p->graph_layout = 1; p->junction_cigars = 1;
+    p->full_lists = 0;
     p->kmer_filter = 0;
     p->kmer_table = 0;
     p->partial_charge = 0;
@@ -795,7 +840,7 @@ static int prepare_batch(fsv_ctx *ctx, AsmWs &W, const fsv_readsets *sets, Round
     R.mz_fixed.assign(B.n_reads + 1, 0);
     {
         uint64_t m = 0;
-        for (uint32_t r = 0; r < B.n_reads; r++) { R.mz_fixed[r] = (uint32_t)m; m += mz_slots((int64_t)len[r] + len[r] / 8 + 64, P.w); }
+        for (uint32_t r = 0; r < B.n_reads; r++) { R.mz_fixed[r] = (uint32_t)m; m += mz_slots((int64_t)len[r] + len[r] / 8 + 64, P.w_later > 0 ? std::min(P.w, P.w_later) : P.w, P.full_lists != 0); }
         if (m >= (1ull << 32)) return fsv_fail(ctx, FSV_EUNSUP, "batch too large for 32-bit offsets; split it");
         R.mz_fixed[B.n_reads] = (uint32_t)m;
     }
@@ -1094,14 +1139,16 @@ static int rechain_listed(fsv_ctx *ctx, AsmWs &W, const Round &R, const uint32_t
     TRY(ensure(ctx, W.upair_tab_sw, std::max(1u, B.n_upairs)));
     FSV_LAUNCH(ctx, ctx->stream, k_pair_tab_swap, dim3(fsv_grid_for(B.n_upairs, 256)), dim3(256), 0, W.upair_tab.p, B.n_upairs, W.upair_tab_sw.p);
     // timed like the other k_chain launches (a profiler counts it too)
-    W.kt.begin(ctx, KN_CHAIN, 0);
     for (int side = 0; side < 2; side++) {
+        const size_t tk = W.kt.begin(ctx, KN_CHAIN, 0);
         if (side == 1) A2.upair_tab = W.upair_tab_sw.p;
         if (A2.wide_list) FSV_HIP(ctx, hipMemsetAsync(A2.n_wide, 0, 4, ctx->stream));   // (the final pass's own wide pairs are done)
+        if (A2.spill_list) FSV_HIP(ctx, hipMemsetAsync(A2.n_spill, 0, 4, ctx->stream)); // (and its spilled ones, and the other side's)
         TRY(launch_chain(ctx, CHAIN_PAIRS, R.short_reads, B.n_upairs, A2, B.n_upairs));
         if (A2.wide_list) TRY(chain_wide_pairs(ctx, A2, R.short_reads, B.n_upairs));
+        W.kt.end(ctx, tk);
+        TRY(chain_spilled_pairs(ctx, W, A2, B.n_upairs, longest_slot(R.G, B.n_reads), R.ct));
     }
-    W.kt.end(ctx);
     return FSV_OK;
 }
 
@@ -1317,6 +1364,7 @@ static void fill_stats(AsmWs &W, const Round &R, const Final &F)
     for (int sl = 0; sl <= P.n_rounds; sl++) {
         const uint32_t *c = h_ct.data() + (size_t)sl * CT_SLOT;
         mz_total[sl] = (uint64_t)c[CT_MZ_LO] | (uint64_t)c[CT_MZ_HI] << 32;
+        W.n_long_reads += c[CT_UQ_LONG]; W.n_spilled_pairs += c[CT_SPILLED];
         if (sl == P.n_rounds) { W.stats.n_inexact_candidates = c[CT_INEXACT]; break; }
         W.stats.n_windows += c[CT_TASKS];
         W.stats.dp_columns += (uint64_t)c[CT_COLS_LO] | (uint64_t)c[CT_COLS_HI] << 32;      // rescue re-runs (k_rescue_accept)
@@ -1442,13 +1490,13 @@ static std::vector<uint32_t> read_set_of(const fsv_readsets *sets)
 // The reads of a sketch-only job (fsv_sketch_reads, the k-mer stages) on the device: all of them as one set with its geometry at window w
 // (G), read through the caller's word offsets; word_off, len, mz_off -- and read_set, when given -- uploaded, warn zeroed, room for mz and
 // mz_cnt.  (lengths and word offsets in range: check_readsets)
-static int stage_sketch_reads(fsv_ctx *ctx, AsmWs &W, const fsv_readsets *sets, int w, const std::vector<uint32_t> *read_set, Geometry &G)
+static int stage_sketch_reads(fsv_ctx *ctx, AsmWs &W, const fsv_readsets *sets, int w, const std::vector<uint32_t> *read_set, Geometry &G, bool full_lists = false)
 {
     const uint32_t n_reads = sets->n_reads;
     Batch B;
     B.n_reads = n_reads; B.n_sets = 1; B.set_start = {0u, n_reads};
     const std::vector<int32_t> len(sets->read_len, sets->read_len + n_reads);
-    TRY(make_geometry(ctx, B, len, G, w));
+    TRY(make_geometry(ctx, B, len, G, w, nullptr, full_lists));
     for (uint32_t r = 0; r <= n_reads; r++) G.word_off[r] = (uint32_t)sets->word_off[r];
     TRY(upload(ctx, W.word_off, G.word_off));
     TRY(upload(ctx, W.len, len));
@@ -1864,6 +1912,7 @@ static int check_asm_params(fsv_ctx *ctx, const fsv_asm_params &P)
     if (P.k_cap < 1 || P.k_cap > FSV_K_WIDE || P.win_rate_pm < 1 || (int)(FSV_WINDOW * (P.win_rate_pm / 1000.0)) > P.k_cap || P.accept_err_pm < 0 || P.accept_err_pm > 1000 ||
         P.w_later < 0 || P.w_later > 64)
         return fsv_fail(ctx, FSV_EINVAL, "fsv_asm_params error model out of range (k_cap <= 95, 375 x win_rate_pm / 1000 <= k_cap)");
+    if (P.full_lists != 0 && P.full_lists != 1) return fsv_fail(ctx, FSV_EINVAL, "full_lists is 0 or 1");
     if (P.kmer_filter && !P.kmer_table)
         return fsv_fail(ctx, FSV_EINVAL, "kmer_filter = 1 needs kmer_table = 1: the filter is the list the k-mer count table stage leaves");
     if (P.partial_charge && P.k_cap > FSV_K_MAX)
@@ -1883,6 +1932,7 @@ static int fsv_assemble_batch_impl(fsv_ctx *ctx, const fsv_readsets *sets, const
     out->n_contigs = 0; out->off[0] = 0;
     // what the opt-in stages leave on the context belongs to this call from here on (its chunks add to it)
     W.reset_stages();
+    W.n_long_reads = W.n_spilled_pairs = 0;
     // (without reads a kmer_table call still goes on: every set gets its verdict -- no k-mer, no peak)
     if (sets->n_sets == 0 || (sets->n_reads == 0 && !P.kmer_table)) { for (uint32_t s = 0; s < sets->n_sets; s++) out->set_status[s] = 0; memset(&W.stats, 0, sizeof(W.stats)); W.mark_valid(P, false); return FSV_OK; }
     TRY(check_readsets(ctx, sets, RS_SETS | RS_LEN));   // (the word offsets: per chunk, assemble_chunk)
@@ -2031,6 +2081,41 @@ static int fsv_sketch_reads_impl(fsv_ctx *ctx, const fsv_readsets *sets, int32_t
     return FSV_OK;
 }
 
+// The per-read index alone (test hook): launch_sketch and launch_uniq as overlap_stage runs them, all reads as one set.
+static int fsv_read_index_impl(fsv_ctx *ctx, const fsv_readsets *sets, int32_t w, int32_t k, int32_t hpc, int32_t full_lists, fsv_mz *out_mz,
+                               uint64_t out_cap, uint64_t *out_off, uint32_t *warn)
+{
+    if (!ctx || !readsets_present(sets, false) || !out_mz || !out_off || !warn) return FSV_EINVAL;
+    if (full_lists != 0 && full_lists != 1) return fsv_fail(ctx, FSV_EINVAL, "full_lists is 0 or 1");
+    if (k < 1 || k > 63 || w < 1 || w > ((k & 1) ? 255 : 64)) return fsv_fail(ctx, FSV_EINVAL, "1 <= k <= 63, 1 <= w <= 255 (odd k) or 64 (even k)");
+    FSV_HIP(ctx, hipSetDevice(ctx->device));
+    AsmWs &W = *ws_get(ctx);
+    W.kt.reset();
+    const uint32_t n_reads = sets->n_reads;
+    out_off[0] = 0;
+    if (n_reads == 0) return FSV_OK;
+    TRY(check_readsets(ctx, sets, RS_LEN | RS_WORD_OFF));
+    Geometry G;
+    TRY(stage_sketch_reads(ctx, W, sets, w, nullptr, G, full_lists != 0));   // (the slots of the assembly with these settings: mz_slots)
+    const std::vector<int32_t> len(sets->read_len, sets->read_len + n_reads);
+    TRY(launch_sketch(ctx, W, SketchJob{sets->store_dev, n_reads, G.word_off[n_reads], G.max_words, w, k, hpc, nullptr, w, false, nullptr, SketchFilter{}}));
+    TRY(launch_uniq(ctx, W, UniqJob{n_reads, G.max_words, nullptr, nullptr, full_lists != 0, longest_slot(G, n_reads), reads_above(len, FSV_UQ_MAX), nullptr}, [] {}));
+    std::vector<uint32_t> cnt(n_reads);
+    TRY(download(ctx, cnt.data(), W.mz_cnt, n_reads));
+    TRY(download(ctx, warn, W.warn, n_reads));
+    FSV_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    uint64_t tot = 0;
+    for (uint32_t r = 0; r < n_reads; r++) {
+        const uint64_t c = std::min<uint64_t>(2ull * cnt[r], G.mz_off[r + 1] - G.mz_off[r]);
+        if (tot + c > out_cap) return fsv_fail(ctx, FSV_ECAP, "out_mz too small");
+        if (c) FSV_HIP(ctx, hipMemcpyAsync(out_mz + tot, W.mz.p + G.mz_off[r], (size_t)c * sizeof(fsv_mz), hipMemcpyDeviceToHost, ctx->stream));
+        tot += c;
+        out_off[r + 1] = tot;
+    }
+    FSV_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return FSV_OK;
+}
+
 // The overlap stage of one pass, alone (test hook): prepare_batch -> begin_round / begin_final -> overlap_stage, and for pass 2
 // rechain_listed on the caller's pairs -- the functions assemble_chunk runs, on one pass's worth of them -- then the raw records.
 static int fsv_asm_overlaps_impl(fsv_ctx *ctx, const fsv_readsets *sets, const fsv_asm_params *params, int32_t pass, const uint32_t *rechain,
@@ -2102,6 +2187,20 @@ extern "C" int fsv_sketch_reads(fsv_ctx *ctx, const fsv_readsets *sets, int32_t 
                                 uint64_t out_cap, uint64_t *out_off)
 {
     FSV_GUARD(ctx, fsv_sketch_reads_impl(ctx, sets, w, k, hpc, variant, out_mz, out_cap, out_off));
+}
+
+extern "C" int fsv_asm_last_long_lists(const fsv_ctx *ctx, uint64_t *n_reads, uint64_t *n_pairs)
+{
+    if (!ctx || !ctx->asm_ws || !n_reads || !n_pairs) return FSV_EINVAL;
+    const AsmWs &W = *(const AsmWs *)ctx->asm_ws;
+    *n_reads = W.n_long_reads; *n_pairs = W.n_spilled_pairs;
+    return FSV_OK;
+}
+
+extern "C" int fsv_read_index(fsv_ctx *ctx, const fsv_readsets *sets, int32_t w, int32_t k, int32_t hpc, int32_t full_lists, fsv_mz *out_mz,
+                              uint64_t out_cap, uint64_t *out_off, uint32_t *warn)
+{
+    FSV_GUARD(ctx, fsv_read_index_impl(ctx, sets, w, k, hpc, full_lists, out_mz, out_cap, out_off, warn));
 }
 
 extern "C" int fsv_sketch_reads_filtered(fsv_ctx *ctx, const fsv_readsets *sets, int32_t w, int32_t k, int32_t hpc, int32_t variant, fsv_mz *out_mz,

@@ -67,6 +67,8 @@ struct ChainArgs {
     unsigned long long *stamps;  // diagnostic (FSV_CHAIN_STAMPS=1): shader cycles per phase summed over the waves, else nullptr
     uint32_t *wide_list, *n_wide; // pairs whose two lists both have more than amax entries (only they can have more than amax anchors) are
                                   // set aside here and chained by k_chain_wide_list with the large tile; nullptr: chain every pair here
+    uint4 *spill_list; uint32_t *n_spill;   // full_lists = 1: a pair with more anchors than the tile in use is not cut but set aside here, as its pair-table
+                                            // record (roles as chained), and chained by k_chain_spill in HBM; nullptr: cut and flagged FSV_W_ANCHOR_TRUNC
 };
 
 // The unordered pairs of every set, enumerated once per batch: block b of k_chain reads one 16-byte record instead of
@@ -98,6 +100,82 @@ __global__ void k_pair_tab(const uint32_t *__restrict__ set_start, const uint32_
     // the query read of either ordered slot (k_bnd_tasks: one load instead of a search of the set table)
     pair_read[pair_base[s] + q * (ns - 1) + (t - 1)] = r0 + q;
     pair_read[pair_base[s] + t * (ns - 1) + q] = r0 + t;
+}
+
+// candidate (i <- j) of the chain DP: score or -1, with the chain's indel sum / span it would give (chain_pair and chain_pair_spill)
+__device__ __forceinline__ int chain_eval(const int bw, const int kk, int qe, int te, int qj, int tj, int indj, int slj, int fj, int &ti, int &tl)
+{
+    const int dq = qe - qj, dt = te - tj;
+    if (dq <= 0 || dt <= 0) return -1;
+    const int gap = dq > dt ? dq - dt : dt - dq;
+    ti = indj + gap; tl = slj + dq;
+    // 64-bit divisions cost ~150 VALU ops on gfx950; the operands fit 32 bits for every read below 2^17 bases (a legal
+    // ti <= tl*bw/1000 <= 2621, sc <= 63; ti is tested too: the block hypothesis sums up to 64 gaps before it asks): same quotient either way
+    if (tl < (1 << 17) && gap < (1 << 17) && ti < (1 << 17) && bw <= 20) {
+        if ((uint32_t)ti * 1000u > (uint32_t)tl * (uint32_t)bw) return -1;
+        int sc = min(min(dq, dt), kk);
+        if (ti) sc -= (int)(((uint32_t)ti * (uint32_t)sc * 1000u) / ((uint32_t)tl * (uint32_t)bw));
+        return sc + fj;
+    }
+    if ((long long)ti * 1000 > (long long)tl * bw) return -1;
+    int sc = min(min(dq, dt), kk);
+    if (ti) sc -= (int)(((long long)ti * sc * 1000) / ((long long)tl * bw));
+    return sc + fj;
+}
+
+// the window tasks of both directions of an overlap (o: q on t, om: its mirror) from its chain: ch_q(e) / ch_t(e) give chain anchor e's
+// coordinates in start-to-end order, 0 <= e < cnt, wherever the caller keeps the chain (LDS tile or HBM slab)
+template <class CQ, class CT>
+__device__ __forceinline__ void chain_window_tasks(const ChainArgs &A, const CQ ch_q, const CT ch_t, const int cnt, const int lane, const fsv_ovl &o, const fsv_ovl &om,
+                                                   const uint32_t first_win, const uint32_t xw, const uint32_t yw, const int lenq, const int lent, const int rev,
+                                                   const uint32_t p, const uint32_t pm, const int xs, const int xe)
+{
+    {
+        const int w0 = xs / FSV_WINDOW;
+        for (int j = lane; j < o.n_win; j += 64) {
+            const int gs = (w0 + j) * FSV_WINDOW, ge = gs + FSV_WINDOW - 1;
+            const int x_start = max(gs, xs);
+            const int x_len = min(ge, xe) - x_start + 1;
+            // diagonal of the last chain anchor with qe <= x_start, else of the first one
+            int lo2 = 0, hi2 = cnt;
+            while (lo2 < hi2) { int mid = (lo2 + hi2) >> 1; if (ch_q(mid) <= x_start) lo2 = mid + 1; else hi2 = mid; }
+            const int e = lo2 == 0 ? 0 : lo2 - 1;
+            const int diag = ch_t(e) - ch_q(e);
+            fsv_wtask w;
+            w.x_word = xw; w.y_word = yw; w.x_start = x_start; w.y_start = x_start + diag; w.y_len = lent;
+            w.x_len = (uint16_t)x_len; w.k = A.thr_tab[x_len]; w.y_rev = (uint8_t)rev; w.ovl = p; w.win = (uint32_t)j;
+            A.tasks[first_win + j] = w;
+        }
+    }
+    {
+        // mirrored direction: query t, target q.  Mirrored anchor of e: same strand (ct_e, cq_e) in the same order;
+        // reverse strand (lent-1-ct_e, lenq-1-cq_e) in reversed order.
+        const int mxs = om.x_s, mxe = om.x_e, w0 = mxs / FSV_WINDOW;
+        for (int j = lane; j < om.n_win; j += 64) {
+            const int gs = (w0 + j) * FSV_WINDOW, ge = gs + FSV_WINDOW - 1;
+            const int x_start = max(gs, mxs);
+            const int x_len = min(ge, mxe) - x_start + 1;
+            int diag;
+            if (!rev) {
+                int lo2 = 0, hi2 = cnt; // last anchor with ct <= x_start
+                while (lo2 < hi2) { int mid = (lo2 + hi2) >> 1; if (ch_t(mid) <= x_start) lo2 = mid + 1; else hi2 = mid; }
+                const int e = lo2 == 0 ? 0 : lo2 - 1;
+                diag = ch_q(e) - ch_t(e);
+            } else {
+                // mirrored query coordinate lent-1-ct_e decreases with e: the last mirrored anchor with coordinate <= x_start is the
+                // smallest e with ct_e >= lent-1-x_start; none -> the first mirrored anchor (e = cnt-1)
+                const int thr = lent - 1 - x_start;
+                int lo2 = 0, hi2 = cnt; // first e with ct_e >= thr
+                while (lo2 < hi2) { int mid = (lo2 + hi2) >> 1; if (ch_t(mid) < thr) lo2 = mid + 1; else hi2 = mid; }
+                const int e = lo2 == cnt ? cnt - 1 : lo2;
+                diag = (lenq - 1 - ch_q(e)) - (lent - 1 - ch_t(e));
+            }
+            fsv_wtask w;
+            w.x_word = yw; w.y_word = xw; w.x_start = x_start; w.y_start = x_start + diag; w.y_len = lenq;
+            w.x_len = (uint16_t)x_len; w.k = A.thr_tab[x_len]; w.y_rev = (uint8_t)rev; w.ovl = pm; w.win = (uint32_t)j;
+            A.tasks[om.first_win + j] = w;
+        }
+    }
 }
 
 // One wavefront per UNORDERED read pair (q < t) of a set: the chain is computed with q as the query and the overlap of t on
@@ -295,7 +373,11 @@ __device__ __forceinline__ void chain_pair(const ChainArgs &A, unsigned char *s_
         }
     } else
         for (int base = 0; base < nq; base += 64) { const int i = base + lane; lookup(i, i < nq ? mq4[i] : make_uint4(0, 0, 0, 0)); }
-    if (n > AMAX) { if (lane == 0) atomicOr(&A.warn[rq], (uint32_t)FSV_W_ANCHOR_TRUNC); n = AMAX; }
+    if (n > AMAX) {
+        if (A.spill_list) { if (lane == 0) A.spill_list[atomicAdd(A.n_spill, 1u)] = pt; return; }   // (no slot written: k_chain_spill writes them)
+        if (lane == 0) atomicOr(&A.warn[rq], (uint32_t)FSV_W_ANCHOR_TRUNC);
+        n = AMAX;
+    }
     __syncthreads();
     CH_MARK(1);
     // 2. majority strand, compaction
@@ -358,25 +440,7 @@ __device__ __forceinline__ void chain_pair(const ChainArgs &A, unsigned char *s_
         // against the oracle, on the pairs of tests/chain_cases.py).
         dp_t *const s_sl = SHORT ? (dp_t *)s_chain : (dp_t *)(s_rest + 8 * (size_t)AMAX);   // chain span per anchor (free arrays during the DP)
         const int kk = A.k_score;
-        // candidate (i <- j): score or -1, with the chain's indel sum / span it would give
-        auto eval = [&](int qe, int te, int qj, int tj, int indj, int slj, int fj, int &ti, int &tl) -> int {
-            const int dq = qe - qj, dt = te - tj;
-            if (dq <= 0 || dt <= 0) return -1;
-            const int gap = dq > dt ? dq - dt : dt - dq;
-            ti = indj + gap; tl = slj + dq;
-            // 64-bit divisions cost ~150 VALU ops on gfx950; the operands fit 32 bits for every read below 2^17 bases
-            // (ti <= tl*bw/1000 <= 2621, sc <= 63): same quotient either way
-            if (tl < (1 << 17) && gap < (1 << 17) && A.bw <= 20) {
-                if ((uint32_t)ti * 1000u > (uint32_t)tl * (uint32_t)A.bw) return -1;
-                int sc = min(min(dq, dt), kk);
-                if (ti) sc -= (int)(((uint32_t)ti * (uint32_t)sc * 1000u) / ((uint32_t)tl * (uint32_t)A.bw));
-                return sc + fj;
-            }
-            if ((long long)ti * 1000 > (long long)tl * A.bw) return -1;
-            int sc = min(min(dq, dt), kk);
-            if (ti) sc -= (int)(((long long)ti * sc * 1000) / ((long long)tl * A.bw));
-            return sc + fj;
-        };
+        auto eval = [&](int qe, int te, int qj, int tj, int indj, int slj, int fj, int &ti, int &tl) { return chain_eval(A.bw, kk, qe, te, qj, tj, indj, slj, fj, ti, tl); };
         auto scan_add = [&](int v) { for (int off = 1; off < 64; off <<= 1) { const int o2 = __shfl_up(v, off, 64); if (lane >= off) v += o2; } return v; };
         if (lane == 0) { s_f[0] = (dp_t)kk; s_aux[0] = 0xffff; s_ind[0] = 0; s_sl[0] = 0; }
         __syncthreads();
@@ -543,57 +607,7 @@ __device__ __forceinline__ void chain_pair(const ChainArgs &A, unsigned char *s_
     o.first_win = (int32_t)first_win;
     om.first_win = (int32_t)(first_win + (uint32_t)o.n_win);
     const uint32_t xw = A.word_off[rq], yw = A.word_off[rt];
-    // chain anchor e (start-to-end order, 0 <= e < cnt)
-#define CH_Q(e) KEY_Q(s_chain[cnt - 1 - (e)])
-#define CH_T(e) KEY_T(s_chain[cnt - 1 - (e)])
-    {
-        const int w0 = xs / FSV_WINDOW;
-        for (int j = lane; j < o.n_win; j += 64) {
-            const int gs = (w0 + j) * FSV_WINDOW, ge = gs + FSV_WINDOW - 1;
-            const int x_start = max(gs, xs);
-            const int x_len = min(ge, xe) - x_start + 1;
-            // diagonal of the last chain anchor with qe <= x_start, else of the first one
-            int lo2 = 0, hi2 = cnt;
-            while (lo2 < hi2) { int mid = (lo2 + hi2) >> 1; if (CH_Q(mid) <= x_start) lo2 = mid + 1; else hi2 = mid; }
-            const int e = lo2 == 0 ? 0 : lo2 - 1;
-            const int diag = CH_T(e) - CH_Q(e);
-            fsv_wtask w;
-            w.x_word = xw; w.y_word = yw; w.x_start = x_start; w.y_start = x_start + diag; w.y_len = lent;
-            w.x_len = (uint16_t)x_len; w.k = A.thr_tab[x_len]; w.y_rev = (uint8_t)rev; w.ovl = p; w.win = (uint32_t)j;
-            A.tasks[first_win + j] = w;
-        }
-    }
-    {
-        // mirrored direction: query t, target q.  Mirrored anchor of e: same strand (ct_e, cq_e) in the same order;
-        // reverse strand (lent-1-ct_e, lenq-1-cq_e) in reversed order.
-        const int mxs = om.x_s, mxe = om.x_e, w0 = mxs / FSV_WINDOW;
-        for (int j = lane; j < om.n_win; j += 64) {
-            const int gs = (w0 + j) * FSV_WINDOW, ge = gs + FSV_WINDOW - 1;
-            const int x_start = max(gs, mxs);
-            const int x_len = min(ge, mxe) - x_start + 1;
-            int diag;
-            if (!rev) {
-                int lo2 = 0, hi2 = cnt; // last anchor with ct <= x_start
-                while (lo2 < hi2) { int mid = (lo2 + hi2) >> 1; if (CH_T(mid) <= x_start) lo2 = mid + 1; else hi2 = mid; }
-                const int e = lo2 == 0 ? 0 : lo2 - 1;
-                diag = CH_Q(e) - CH_T(e);
-            } else {
-                // mirrored query coordinate lent-1-ct_e decreases with e: the last mirrored anchor with coordinate <= x_start is the
-                // smallest e with ct_e >= lent-1-x_start; none -> the first mirrored anchor (e = cnt-1)
-                const int thr = lent - 1 - x_start;
-                int lo2 = 0, hi2 = cnt; // first e with ct_e >= thr
-                while (lo2 < hi2) { int mid = (lo2 + hi2) >> 1; if (CH_T(mid) < thr) lo2 = mid + 1; else hi2 = mid; }
-                const int e = lo2 == cnt ? cnt - 1 : lo2;
-                diag = (lenq - 1 - CH_Q(e)) - (lent - 1 - CH_T(e));
-            }
-            fsv_wtask w;
-            w.x_word = yw; w.y_word = xw; w.x_start = x_start; w.y_start = x_start + diag; w.y_len = lenq;
-            w.x_len = (uint16_t)x_len; w.k = A.thr_tab[x_len]; w.y_rev = (uint8_t)rev; w.ovl = pm; w.win = (uint32_t)j;
-            A.tasks[om.first_win + j] = w;
-        }
-    }
-#undef CH_Q
-#undef CH_T
+    chain_window_tasks(A, [&](int e) { return KEY_Q(s_chain[cnt - 1 - e]); }, [&](int e) { return KEY_T(s_chain[cnt - 1 - e]); }, cnt, lane, o, om, first_win, xw, yw, lenq, lent, rev, p, pm, xs, xe);
     PUT_BOTH();
     CH_MARK(6);
 #undef CH_MARK
@@ -706,6 +720,273 @@ __global__ __launch_bounds__(64) void k_chain_chunks(ChainArgs A, uint32_t n_upa
         const fsv_mz *mq = A.mz + offq + nq;
         chain_pair<SHORT>(A, s_raw, pt, lenq, lent, nq, nt, mq, A.mz + offt, qa);
         __syncthreads();   // the next pair reuses the tile
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ k_chain_spill (full_lists = 1)
+// The pairs chain_pair set aside because their anchors exceed its LDS tile: a small fixed grid walks A.spill_list, one wavefront per pair,
+// with the per-anchor arrays -- keys, score, indel sum, span, predecessor, chain, strand: 29 B per anchor in 32 -- in the block's slab in
+// HBM (cap anchors; the host sizes it from the batch's longest minimizer slot, and a pair has at most min(nq, nt) anchors), which stays in
+// L2.  The algorithm is chain_pair's step for step and must give the oracle's records and tasks bit for bit; what differs is what the
+// tile's packing forced there: 64-bit keys whatever the read lengths, 32-bit scores and indices with -1 as "none", the best end as
+// score << 32 | (2^31 - 1 - index), every lookup a binary search of the target's list in memory.  The 32-bit division in eval keeps its guard.
+#define FSV_SPILL_GRID 32
+#define FSV_SPILL_BYTES 32   // slab bytes per anchor
+__device__ __forceinline__ void chain_pair_spill(const ChainArgs &A, const uint4 pt, unsigned char *slab, const uint32_t cap)
+{
+    uint64_t *const g_key = (uint64_t *)slab;
+    int32_t *const g_f = (int32_t *)(slab + 8 * (size_t)cap), *const g_ind = g_f + cap, *const g_sl = g_ind + cap, *const g_pred = g_sl + cap, *const g_chain = g_pred + cap;
+    uint8_t *const g_strand = (uint8_t *)(g_chain + cap);
+#define KEY_Q(i) ((int)(g_key[i] >> 32))
+#define KEY_T(i) ((int)(g_key[i] & 0xffffffffull))
+#define MAKE_KEY(q_, t_) (((uint64_t)(uint32_t)(q_) << 32) | (uint64_t)(uint32_t)(t_))
+    const int lane = threadIdx.x;
+    const uint32_t q = pt.y & 0xffffu, t = pt.y >> 16;
+    const uint32_t p = pt.z, pm = pt.w;     // ordered slots (q, t) and (t, q)
+    const uint32_t rq = pt.x + q, rt = pt.x + t;
+    const int lenq = A.read_len[rq], lent = A.read_len[rt];
+    const int nq = (int)A.mz_cnt[rq], nt = (int)A.mz_cnt[rt];
+    const fsv_mz *mq = A.mz + A.mz_off[rq] + nq, *mt = A.mz + A.mz_off[rt]; // q: position-sorted copy, t: hash-sorted
+    const uint4 *mq4 = (const uint4 *)mq;
+    fsv_ovl o;
+    o.q = q; o.t = t; o.x_s = o.x_e = o.y_s = o.y_e = 0; o.score = 0; o.n_chain = 0; o.chain_off = 0; o.first_win = 0; o.n_win = 0;
+    o.align_len = 0; o.err_sum = 0; o.rev = 0; o.is_match = 0; o.exact = 0; o.valid = 0;
+    fsv_ovl om = o; // the mirrored overlap (t on q)
+    om.q = t; om.t = q;
+#define PUT_BOTH() do { if (lane == 0) { A.ovl[p] = o; if (!A.primary_only) A.ovl[pm] = om; } } while (0)
+    // 1. anchors
+    int n = 0, nrev = 0, nfwd = 0;
+    for (int base = 0; base < nq; base += 64) {
+        const int i = base + lane;
+        bool hit = false; uint64_t key = 0; uint32_t srev = 0;
+        if (i < nq) {
+            const uint4 av = mq4[i];
+            const uint64_t ah = (uint64_t)av.x | (uint64_t)av.y << 32;
+            const uint32_t qrev = (uint32_t)(lenq - 1) - (av.z - ((av.w >> 8) & 0xffu) + 1);   // (see chain_pair)
+            int l2 = 0, h2 = nt;
+            while (l2 < h2) { const int mid = (l2 + h2) >> 1; if (mt[mid].hash < ah) l2 = mid + 1; else h2 = mid; }
+            if (l2 < nt && mt[l2].hash == ah) {
+                const fsv_mz b = mt[l2];
+                srev = (av.w & 0xffu) ^ b.rev;
+                hit = true; key = MAKE_KEY(srev ? qrev : av.z, b.pos);
+            }
+        }
+        const uint64_t m = __ballot(hit);
+        const int at = n + __popcll(m & ((1ull << lane) - 1));
+        if (hit && (uint32_t)at < cap) { g_key[at] = key; g_strand[at] = (uint8_t)srev; }
+        nrev += __popcll(__ballot(hit && srev));
+        nfwd += __popcll(__ballot(hit && !srev));
+        n += __popcll(m);
+    }
+    if ((uint32_t)n > cap) { if (lane == 0) atomicOr(&A.warn[rq], (uint32_t)FSV_W_INTERNAL); n = (int)cap; }   // cannot happen: n <= min(nq, nt) <= a slot
+    __syncthreads();
+    // 2. majority strand, compaction
+    const int rev = nrev > nfwd;
+    int m2 = 0;
+    for (int base = 0; base < n; base += 64) {
+        const int i = base + lane;
+        bool keep = false; uint64_t key = 0;
+        if (i < n) { key = g_key[i]; keep = (int)g_strand[i] == rev; }
+        const uint64_t m = __ballot(keep);
+        const int at = m2 + __popcll(m & ((1ull << lane) - 1));
+        __syncthreads();
+        if (keep) g_key[at] = key;
+        m2 += __popcll(m);
+        __syncthreads();
+    }
+    n = m2;
+    if (n < A.min_anchors) { PUT_BOTH(); return; }
+    // 3. the reverse strand's list is turned around
+    if (rev) {
+        for (int i = lane; i < n / 2; i += 64) { const uint64_t a0 = g_key[i], a1 = g_key[n - 1 - i]; g_key[i] = a1; g_key[n - 1 - i] = a0; }
+        __syncthreads();
+    }
+    // 4. chain DP: the one-diagonal fast path, else block hypothesis / proof / repair (chain_pair)
+    bool colinear;
+    {
+        const int d0 = KEY_T(0) - KEY_Q(0);
+        bool same = true;
+        for (int i = lane; i < n; i += 64) same = same && (KEY_T(i) - KEY_Q(i) == d0);
+        colinear = __all(same);
+    }
+    if (colinear) {
+        int acc = 0;
+        for (int i = 1 + lane; i < n; i += 64) acc += min(KEY_Q(i) - KEY_Q(i - 1), A.k_score);
+        for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off, 64);
+        for (int i = lane; i < n; i += 64) { g_pred[i] = i - 1; g_f[i] = i == n - 1 ? A.k_score + acc : 0; }
+        __syncthreads();
+    } else {
+        const int kk = A.k_score;
+        auto eval = [&](int qe, int te, int qj, int tj, int indj, int slj, int fj, int &ti, int &tl) { return chain_eval(A.bw, kk, qe, te, qj, tj, indj, slj, fj, ti, tl); };
+        auto scan_add = [&](int v) { for (int off = 1; off < 64; off <<= 1) { const int o2 = __shfl_up(v, off, 64); if (lane >= off) v += o2; } return v; };
+        if (lane == 0) { g_f[0] = kk; g_pred[0] = -1; g_ind[0] = 0; g_sl[0] = 0; }
+        __syncthreads();
+        int i0 = 1;
+        while (i0 < n) {
+            const int nb = min(64, n - i0), i = i0 + lane;
+            const bool in = lane < nb;
+            int qe = 0, te = 0, dq = 0, dt = 0, gap = 0;
+            if (in) { qe = KEY_Q(i); te = KEY_T(i); dq = qe - KEY_Q(i - 1); dt = te - KEY_T(i - 1); gap = dq > dt ? dq - dt : dt - dq; }
+            const int ti = g_ind[i0 - 1] + scan_add(gap), tl = g_sl[i0 - 1] + scan_add(dq);
+            bool legal = in && dq > 0 && dt > 0;
+            int sc = 0;
+            if (legal) {
+                int t2, l2;
+                const int c = eval(qe, te, qe - dq, te - dt, ti - gap, tl - dq, 0, t2, l2);
+                legal = c >= 0; sc = c;
+            }
+            const int fi = g_f[i0 - 1] + scan_add(legal ? sc : 0);
+            bool bad = in && !(legal && fi > kk);
+            __syncthreads();
+            if (in) { g_f[i] = fi; g_ind[i] = ti; g_sl[i] = tl; }
+            __syncthreads();
+            const int pj0 = i0 - 64 + lane;
+            const int pf = pj0 >= 0 ? g_f[pj0] : 0, cf = in ? fi : 0;
+            int pP = pf, cP = cf;
+            for (int off = 1; off < 64; off <<= 1) {
+                const int o1 = __shfl_up(pP, off, 64), o2 = __shfl_up(cP, off, 64);
+                if (lane >= off) { pP = max(pP, o1); cP = max(cP, o2); }
+            }
+            cP = max(cP, __shfl(pP, 63, 64));
+            bool live = in && !bad;
+            for (int d = 2; d <= 64; d++) {
+                const int j = i - d, src = (lane - d) & 63;
+                const int f_c = __shfl(cf, src, 64), f_p = __shfl(pf, src, 64), P_c = __shfl(cP, src, 64), P_p = __shfl(pP, src, 64);
+                const int fj = lane >= d ? f_c : f_p, Pj = lane >= d ? P_c : P_p;
+                live = live && !bad && j >= 0 && Pj + kk > fi;
+                if (!__any(live)) break;
+                const bool need = live && fj + kk > fi;
+                if (__any(need)) {
+                    if (need) {
+                        int t2, l2;
+                        if (eval(qe, te, KEY_Q(j), KEY_T(j), g_ind[j], g_sl[j], fj, t2, l2) > fi) bad = true;
+                    }
+                }
+            }
+            const uint64_t badm = __ballot(bad);
+            const int good = badm ? (int)__ffsll((long long)badm) - 1 : nb;     // anchors i0 .. i0 + good - 1 stand
+            if (lane < good) g_pred[i] = i - 1;
+            __syncthreads();
+            i0 += good;
+            if (good == nb) continue;
+            // sequential steps for the anchor that broke the hypothesis and up to seven behind it
+            const int s1 = min(n, i0 + 8);
+            int pq = 0, ptt = 0, rind = 0, rsl = 0, rf = 0;
+            { const int j = i0 - 1 - lane; if (j >= 0) { pq = KEY_Q(j); ptt = KEY_T(j); rind = g_ind[j]; rsl = g_sl[j]; rf = g_f[j]; } }
+            for (int is = i0; is < s1; is++) {
+                const int qe2 = KEY_Q(is), te2 = KEY_T(is);
+                const int j = is - 1 - lane;
+                int cand = -1, ti2 = 0, tl2 = 0;
+                if (j >= 0) cand = eval(qe2, te2, pq, ptt, rind, rsl, rf, ti2, tl2);
+                // the max prefers the higher score, then the nearer predecessor
+                const long long packed = cand < 0 ? -1ll : (long long)cand * 64 + (63 - lane);
+                const long long bestp = wave_max_i64(packed);
+                const int bests = bestp < 0 ? -1 : (int)(bestp >> 6);
+                int nf = kk, nind = 0, nsl = 0, npred = -1;
+                if (bests > kk) {
+                    const int wl = 63 - (int)(bestp & 63);
+                    nf = bests; npred = is - 1 - wl;
+                    nind = __builtin_amdgcn_readlane(ti2, wl); nsl = __builtin_amdgcn_readlane(tl2, wl);
+                }
+                if (lane == 0) { g_f[is] = nf; g_pred[is] = npred; g_ind[is] = nind; g_sl[is] = nsl; }
+                pq = __builtin_amdgcn_update_dpp(qe2, pq, 0x138, 0xF, 0xF, false);    // wave_shr:1, lane 0 <- the new anchor
+                ptt = __builtin_amdgcn_update_dpp(te2, ptt, 0x138, 0xF, 0xF, false);
+                rind = __builtin_amdgcn_update_dpp(nind, rind, 0x138, 0xF, 0xF, false);
+                rsl = __builtin_amdgcn_update_dpp(nsl, rsl, 0x138, 0xF, 0xF, false);
+                rf = __builtin_amdgcn_update_dpp(nf, rf, 0x138, 0xF, 0xF, false);
+            }
+            __syncthreads();
+            i0 = s1;
+        }
+        __syncthreads();
+    }
+    // 5. best chain end: highest score, smallest index on ties
+    long long bk = -1;
+    for (int i = lane; i < n; i += 64) { const long long v = ((long long)g_f[i] << 32) | (long long)(0x7fffffff - i); bk = v > bk ? v : bk; }
+    bk = wave_max_i64(bk);
+    const int best = 0x7fffffff - (int)(bk & 0xffffffffll);
+    // 6. walk back run by run, chain stored end-to-start
+    int cnt = 0;
+    if (colinear) {
+        for (int e = lane; e <= best; e += 64) g_chain[e] = best - e;
+        cnt = best + 1;
+    } else {
+        int carry = 0;
+        for (int base = 0; base < n; base += 64) {
+            const int i = base + lane;
+            int v = (i < n && i > 0 && g_pred[i] == i - 1) ? -1 : i; // run start candidate
+            if (i >= n) v = -1;
+            for (int off = 1; off < 64; off <<= 1) { const int o2 = __shfl_up(v, off, 64); if (lane >= off) v = max(v, o2); }
+            v = max(v, carry);
+            if (i < n) g_ind[i] = v;
+            carry = __shfl(v, 63, 64);
+        }
+        __syncthreads();
+        int c = best;
+        while (c >= 0) {
+            const int r = g_ind[c];
+            for (int e = lane; e <= c - r; e += 64) g_chain[cnt + e] = c - e;
+            cnt += c - r + 1;
+            c = g_pred[r];
+        }
+    }
+    __syncthreads();
+    if (cnt < A.min_anchors) { PUT_BOTH(); return; }
+    const int first = g_chain[cnt - 1];
+    int xs = KEY_Q(first), ys = KEY_T(first);
+    int xe = KEY_Q(best), ye = KEY_T(best);
+    { int m = min(xs, ys); xs -= m; ys -= m; int r = min(lenq - 1 - xe, lent - 1 - ye); xe += r; ye += r; }
+    if (xe - xs + 1 < A.min_ovlp) { PUT_BOTH(); return; }
+    const int score_best = g_f[best];
+    if (rev) {
+        { const int t0 = xs; xs = (lenq - 1) - xe; xe = (lenq - 1) - t0; }
+        { const int t0 = ys; ys = (lent - 1) - ye; ye = (lent - 1) - t0; }
+        __syncthreads();
+        for (int i = lane; i < n; i += 64) {
+            const int kq = KEY_Q(i), kt2 = KEY_T(i);
+            g_key[i] = MAKE_KEY((lenq - 1) - kq, (lent - 1) - kt2);
+        }
+        for (int e = lane; e < cnt / 2; e += 64) { const int c0 = g_chain[e], c1 = g_chain[cnt - 1 - e]; g_chain[e] = c1; g_chain[cnt - 1 - e] = c0; }
+        __syncthreads();
+    }
+    o.x_s = xs; o.x_e = xe; o.y_s = ys; o.y_e = ye; o.rev = (uint8_t)rev; o.score = score_best; o.n_chain = cnt; o.valid = 1;
+    o.n_win = xe / FSV_WINDOW - xs / FSV_WINDOW + 1;
+    om.rev = (uint8_t)rev; om.score = o.score; om.n_chain = cnt; om.valid = 1;
+    if (!rev) { om.x_s = ys; om.x_e = ye; om.y_s = xs; om.y_e = xe; }
+    else { om.x_s = lent - 1 - ye; om.x_e = lent - 1 - ys; om.y_s = lenq - 1 - xe; om.y_e = lenq - 1 - xs; }
+    om.n_win = om.x_e / FSV_WINDOW - om.x_s / FSV_WINDOW + 1;
+    if (!A.emit_tasks) { o.n_win = 0; om.n_win = 0; PUT_BOTH(); return; }
+    // 7. window tasks of both directions
+    uint32_t first_win = 0;
+    if (lane == 0) {
+        first_win = atomicAdd(A.task_counter, (uint32_t)(o.n_win + om.n_win));
+        atomicAdd(&A.set_cols[pt.x], (uint32_t)(xe - xs + 1) + (uint32_t)(om.x_e - om.x_s + 1));
+    }
+    first_win = __shfl(first_win, 0, 64);
+    if ((uint64_t)first_win + (uint32_t)(o.n_win + om.n_win) > A.task_cap) {
+        if (lane == 0) { atomicExch(A.overflow, 1u); o.valid = 0; o.n_win = 0; om.valid = 0; om.n_win = 0; A.ovl[p] = o; A.ovl[pm] = om; }
+        return;
+    }
+    o.first_win = (int32_t)first_win;
+    om.first_win = (int32_t)(first_win + (uint32_t)o.n_win);
+    const uint32_t xw = A.word_off[rq], yw = A.word_off[rt];
+    chain_window_tasks(A, [&](int e) { return KEY_Q(g_chain[cnt - 1 - e]); }, [&](int e) { return KEY_T(g_chain[cnt - 1 - e]); }, cnt, lane, o, om, first_win, xw, yw, lenq, lent, rev, p, pm, xs, xe);
+    PUT_BOTH();
+#undef PUT_BOTH
+#undef KEY_Q
+#undef KEY_T
+#undef MAKE_KEY
+}
+
+__global__ __launch_bounds__(64) void k_chain_spill(ChainArgs A, unsigned char *slab, uint32_t cap, uint32_t *spilled)
+{
+    const uint32_t n = *A.n_spill;
+    if (blockIdx.x == 0 && threadIdx.x == 0 && n) atomicAdd(spilled, n);   // statistics: pairs chained here, summed over the pass's launches
+    unsigned char *const mine = slab + (size_t)blockIdx.x * cap * FSV_SPILL_BYTES;
+    for (uint32_t i = blockIdx.x; i < n; i += gridDim.x) {
+        chain_pair_spill(A, A.spill_list[i], mine, cap);
+        __threadfence_block();
+        __syncthreads();   // the next pair reuses the slab
     }
 }
 

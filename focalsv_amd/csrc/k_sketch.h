@@ -1,5 +1,5 @@
 // k_sketch.h -- minimizer sketch and per-read index: k_sketch (replay, even k), k_sketch_fast (position-parallel, odd k),
-// k_uniq / k_uniq_walk.  Included by asm.hip (through asm_kernels.h) and by aln.hip; each of the two translation units gets its own
+// k_uniq / k_uniq_walk / k_uniq_long.  Included by asm.hip (through asm_kernels.h) and by aln.hip; each of the two translation units gets its own
 // copy of these kernels and of nothing else.
 #pragma once
 #include "fsv_internal.h"
@@ -343,6 +343,145 @@ __global__ __launch_bounds__(256) void k_uniq_walk(fsv_mz *__restrict__ mz, cons
     }
 }
 
+// ------------------------------------------------------------------------------------------------ k_uniq_long (full_lists = 1)
+// The third size class: lists above FSV_UQ_MAX entries, which no LDS tile holds.  A few blocks walk the reads as k_uniq_walk does and skip
+// by count what the two classes in front have done (they leave such a list alone when the option is on).  A list is sorted tile by tile
+// in LDS (the bitonic network of uniq_read on 16-byte records), then the sorted tiles are merged pairwise through HBM, doubling the run
+// length per pass: merge path -- every thread finds by binary search where its FSV_UQ_SEG outputs start in the two runs and merges them
+// sequentially.  The passes go back and forth between the read's slot and the block's slab in the workspace (two buffers of the longest
+// slot each: the slot's own tail would do as the second buffer only while 2n fits, and nothing bounds n below one entry per base), which
+// stays in L2.  The sketch emits through an atomic counter, so the raw list is in no particular order: the position-sorted copy of the
+// survivors is a second sort of the same kind, by position alone.  Hashes that occur once are found on the sorted list in HBM, so a run
+// of equal hashes may straddle any tile or merge boundary.
+#define FSV_UQ_SEG 16    // outputs per thread and merge step; divides every run length (multiples of FSV_UQ_MAX)
+#define FSV_UQ_LONG_GRID 32
+
+__device__ __forceinline__ uint64_t mz_hash(const uint4 e) { return (uint64_t)e.x | (uint64_t)e.y << 32; }
+// the two orders: (hash, position), or position alone (positions are distinct inside a read, so both are total)
+template <bool BY_POS> __device__ __forceinline__ bool mz_less(const uint4 a, const uint4 b)
+{
+    if (BY_POS) return a.z < b.z;
+    const uint64_t ha = mz_hash(a), hb = mz_hash(b);
+    return ha < hb || (ha == hb && a.z < b.z);
+}
+
+// sorts a[0, n) with b[0, n) as the other buffer; returns the one that holds the result.  s_e: FSV_UQ_MAX records of LDS
+template <bool BY_POS>
+__device__ __forceinline__ uint4 *sort_long(uint4 *a, uint4 *b, const uint32_t n, uint4 *s_e)
+{
+    const uint32_t tid = threadIdx.x;
+    for (uint32_t base = 0; base < n; base += FSV_UQ_MAX) {
+        const uint32_t nt = min((uint32_t)FSV_UQ_MAX, n - base);
+        uint32_t np = 1;
+        while (np < nt) np <<= 1;
+        for (uint32_t i = tid; i < np; i += 256) s_e[i] = i < nt ? a[base + i] : make_uint4(~0u, ~0u, ~0u, ~0u);   // (the dummy hash / no position: last in either order)
+        __syncthreads();
+        for (uint32_t sz = 2; sz <= np; sz <<= 1)
+            for (uint32_t st = sz >> 1; st > 0; st >>= 1) {
+                for (uint32_t t = tid; t < np / 2; t += 256) {
+                    const uint32_t i = ((t & ~(st - 1)) << 1) | (t & (st - 1)), j = i | st;
+                    const bool up = (i & sz) == 0;
+                    const uint4 ei = s_e[i], ej = s_e[j];
+                    if (mz_less<BY_POS>(ej, ei) == up) { s_e[i] = ej; s_e[j] = ei; }
+                }
+                __syncthreads();
+            }
+        for (uint32_t i = tid; i < nt; i += 256) a[base + i] = s_e[i];
+        __syncthreads();
+    }
+    uint4 *src = a, *dst = b;
+    for (uint32_t wd = FSV_UQ_MAX; wd < n; wd <<= 1) {
+        __threadfence_block();
+        __syncthreads();
+        const uint32_t n_seg = (n + FSV_UQ_SEG - 1) / FSV_UQ_SEG;
+        for (uint32_t g = tid; g < n_seg; g += 256) {
+            const uint32_t o0 = g * FSV_UQ_SEG;
+            const uint32_t lo = o0 & ~(2u * wd - 1u), mid = min(lo + wd, n), hi = min(lo + 2u * wd, n);   // runs [lo, mid) and [mid, hi)
+            const uint32_t nx = mid - lo, ny = hi - mid, d = o0 - lo;
+            const uint4 *X = src + lo, *Y = src + mid;
+            // the split of output d: i entries of X and d - i of Y in front of it -- the smallest i with X[i] > Y[d - i - 1]
+            uint32_t il = d > ny ? d - ny : 0u, ih = min(d, nx);
+            while (il < ih) { const uint32_t i = (il + ih) >> 1; if (mz_less<BY_POS>(X[i], Y[d - i - 1])) il = i + 1; else ih = i; }
+            uint32_t i = il, j = d - il;
+            const uint32_t o1 = min(o0 + (uint32_t)FSV_UQ_SEG, hi);
+            bool hx = i < nx, hy = j < ny;
+            uint4 x = make_uint4(0, 0, 0, 0), y = x;
+            if (hx) x = X[i];
+            if (hy) y = Y[j];
+            for (uint32_t o = o0; o < o1; o++) {
+                const bool tx = hx && (!hy || mz_less<BY_POS>(x, y));
+                dst[o] = tx ? x : y;
+                if (tx) { i++; hx = i < nx; if (hx) x = X[i]; }
+                else { j++; hy = j < ny; if (hy) y = Y[j]; }
+            }
+        }
+        uint4 *t = src; src = dst; dst = t;
+    }
+    __threadfence_block();
+    __syncthreads();
+    return src;
+}
+
+// ws: FSV_UQ_LONG_GRID slabs of 2 x ws_stride records, ws_stride >= the longest slot of the batch
+__global__ __launch_bounds__(256) void k_uniq_long(fsv_mz *mz, const uint32_t *__restrict__ mz_off, uint32_t *mz_cnt, uint32_t *__restrict__ warn,
+                                                   const uint32_t *__restrict__ only_changed, unsigned long long *__restrict__ total, uint32_t n_reads,
+                                                   uint4 *ws, uint32_t ws_stride, uint32_t *__restrict__ n_done)
+{
+    __shared__ uint4 s_e[FSV_UQ_MAX];
+    __shared__ uint32_t s_cnt[4];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wv = tid >> 6;
+    uint4 *const w0 = ws + (size_t)blockIdx.x * 2u * ws_stride, *const w1 = w0 + ws_stride;
+    for (uint32_t r = blockIdx.x; r < n_reads; r += gridDim.x) {
+        if (only_changed && !only_changed[r]) continue;   // lists of an unchanged read are already in place
+        const uint32_t cap = mz_off[r + 1] - mz_off[r];
+        const uint32_t raw = mz_cnt[r];
+        if (raw <= FSV_UQ_MAX) continue;                   // the other two classes' (what they left is their unique count: smaller still)
+        const uint32_t n = min(raw, cap);                  // k_sketch counts past the cap when it truncates
+        if (n > ws_stride) { if (tid == 0) atomicOr(&warn[r], (uint32_t)FSV_W_INTERNAL); continue; }   // cannot happen: the host sizes the slabs from the slots
+        uint4 *const slot = (uint4 *)(mz + mz_off[r]);
+        const uint4 *S = sort_long<false>(slot, w0, n, s_e);
+        // hashes that occur once, in hash order, to w1
+        uint32_t m = 0;
+        for (uint32_t base = 0; base < n; base += 256) {
+            const uint32_t i = base + tid;
+            bool u = false;
+            uint4 e = make_uint4(0, 0, 0, 0);
+            if (i < n) {
+                e = S[i];
+                const uint64_t h = mz_hash(e);
+                u = (i == 0 || mz_hash(S[i - 1]) != h) && (i + 1 >= n || mz_hash(S[i + 1]) != h);
+            }
+            const uint64_t bal = __ballot(u);
+            if (lane == 0) s_cnt[wv] = (uint32_t)__popcll(bal);
+            __syncthreads();
+            uint32_t before = 0, all = 0;
+#pragma unroll
+            for (uint32_t v = 0; v < 4; v++) { const uint32_t c = s_cnt[v]; if (v < wv) before += c; all += c; }
+            if (u) w1[m + before + (uint32_t)__popcll(bal & ((1ull << lane) - 1ull))] = e;
+            m += all;
+            __syncthreads();
+        }
+        __threadfence_block();
+        __syncthreads();
+        // [0, m): sorted by hash (the "target" role)
+        for (uint32_t i = tid; i < m; i += 256) slot[i] = w1[i];
+        // [m, 2m): the same minimizers sorted by position (the "query" role)
+        const uint4 *P = sort_long<true>(w1, w0, m, s_e);
+        if (2u * m <= cap) for (uint32_t i = tid; i < m; i += 256) slot[m + i] = P[i];
+        else if (tid == 0) atomicOr(&warn[r], (uint32_t)FSV_W_INTERNAL);   // more than half a slot of unique minimizers: cannot happen (w <= 2 only, and the host then sizes the slots for it: mz_slots)
+        if (tid == 0) {
+            mz_cnt[r] = m;
+            if (n_done) atomicAdd(n_done, 1u);   // statistics: lists this class indexed
+            if (total) {   // as uniq_read
+                atomicAdd(total, (unsigned long long)m);
+                atomicAdd(total + 3, (unsigned long long)n);
+                atomicAdd(total + 4, (unsigned long long)(cap - 64u));
+            }
+        }
+        __syncthreads();
+    }
+}
+
 // ------------------------------------------------------------------------------------------------ k_sketch_fast
 // Position-parallel form of ha_sketch (sketch.cpp:39-137) for odd k (hifiasm's 51, minimap2's 19): no sequential replay.
 //   phase 0  homopolymer compression in parallel: run ends are found per 16-base word, a block scan gives every kept
@@ -594,6 +733,35 @@ template <class Ws> int launch_sketch(fsv_ctx *ctx, Ws &W, const SketchJob &J)
             FSV_LAUNCH(ctx, ctx->stream, k_sketch<false>, dim3(J.n_reads), dim3(64), lds, J.store, W.word_off.p, W.len.p, W.mz_off.p, W.mz.p, W.mz_cnt.p,
                        J.n_reads, J.w, J.k, J.hpc, W.warn.p, J.wper, J.w_max, lds_words, FltView<false>{});
         }
+    }
+    return FSV_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ host: the per-read index launch
+// The unique-minimizer index of the lists launch_sketch left in W.mz / W.mz_cnt, one launch per size class.  The sort holds a read's
+// minimizers in LDS (16 B per entry): one instantiation for lists up to 1 024 entries (many reads per CU), one for lists up to
+// FSV_UQ_MAX; each launch skips the reads of the other classes by count, so the host need not know the longest list of the batch.
+// full_lists: lists above FSV_UQ_MAX go to k_uniq_long instead of being cut there (W.uq_ws: its slabs, held only by such a call).
+struct UniqJob {
+    uint32_t n_reads, max_words;          // store words of the longest read: at most one minimizer per base, so shorter reads cannot have a longer list
+    const uint32_t *only_changed;         // reads with a zero here keep their index
+    unsigned long long *total;            // the launch's statistics (unique, raw, bases), or null
+    bool full_lists; uint32_t max_slot, n_long;   // full_lists: the longest slot, the reads above FSV_UQ_MAX bases
+    uint32_t *n_long_done;                // ... and a device counter of the lists k_uniq_long indexed, or null
+};
+// before_long: called in front of the third class's launch, when there is one (the assembly times that kernel on its own)
+template <class Ws, class F> int launch_uniq(fsv_ctx *ctx, Ws &W, const UniqJob &J, F before_long)
+{
+    FSV_LAUNCH(ctx, ctx->stream, k_uniq<1024>, dim3(J.n_reads), dim3(256), 0, W.mz.p, W.mz_off.p, W.mz_cnt.p, W.warn.p, J.only_changed, 0u, 1024u, J.total);
+    if (J.max_words * 16u > 1024u)
+        FSV_LAUNCH(ctx, ctx->stream, k_uniq_walk<FSV_UQ_MAX>, dim3(std::min<uint32_t>(J.n_reads, 2u * (uint32_t)ctx->n_cu)), dim3(256), 0, W.mz.p, W.mz_off.p,
+                   W.mz_cnt.p, W.warn.p, J.only_changed, 1024u, J.full_lists ? (uint32_t)FSV_UQ_MAX : 0xffffffffu, J.total, J.n_reads);
+    if (J.full_lists && J.max_words * 16u > (uint32_t)FSV_UQ_MAX && J.n_long) {
+        const uint32_t grid = std::min<uint32_t>(J.n_long, FSV_UQ_LONG_GRID);
+        TRY(ensure(ctx, W.uq_ws, (size_t)grid * 2u * J.max_slot));
+        before_long();
+        FSV_LAUNCH(ctx, ctx->stream, k_uniq_long, dim3(grid), dim3(256), 0, W.mz.p, W.mz_off.p, W.mz_cnt.p, W.warn.p, J.only_changed, J.total, J.n_reads,
+                   W.uq_ws.p, J.max_slot, J.n_long_done);
     }
     return FSV_OK;
 }

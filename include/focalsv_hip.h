@@ -178,6 +178,13 @@ typedef struct fsv_asm_params {
                                * for every set that is not flagged FSV_SET_UNPHASED; 0: best-buddy chains (ONT profile, unphased sets) */
     int32_t junction_cigars;  /* 1 (default): the haplotype partition reads the ~50 columns on each side of a window junction off the re-aligned
                                * junction cigar, as hifiasm does (calculate_boundary_cigars, Correct.cpp:2310; markSNP_advance :5054); 0: window cigars */
+    int32_t full_lists;       /* 0 (default in all three profiles): a read's per-read index holds its first 4 096 minimizers (FSV_W_MZ_TRUNC beyond) and a
+                               * pair's chain the anchors its LDS tile holds (FSV_W_ANCHOR_TRUNC beyond).  1: neither is cut and neither bit is raised --
+                               * lists above 4 096 entries are sorted through HBM (k_uniq_long), pairs above the tile are chained in an HBM slab
+                               * (k_chain_spill); the result is the oracle's at any read length.  Any other value is FSV_EINVAL.  A read's minimizer slot holds
+                               * len + 64 entries and the index two per unique minimizer; with w <= 2 (or 0 < w_later <= 2) that can be more, so with
+                               * the option such a call gets slots of 2 len + 64 (the default keeps its slots, and FSV_W_INTERNAL for such a list).
+                               * What the two kernels took: fsv_asm_last_long_lists.  (In front of kmer_filter: the struct's tail is pinned, see there.) */
     int32_t kmer_filter;      /* 0 (default in all three profiles): off.  1 (needs kmer_table = 1, else FSV_EINVAL): hifiasm's high-count k-mer filter in
                                * every sketch of the assembly (ha_ft_isflt in ha_sketch, sketch.cpp:89; every round and the final pass take the one
                                * filter of the raw reads): a k-mer on its set's filter list keeps its slot in the window but is no candidate.  Sets
@@ -194,12 +201,12 @@ typedef struct fsv_asm_params {
                                * k_cap <= FSV_K_MAX: FSV_EINVAL with the wide-band profiles */
 } fsv_asm_params;
 void fsv_asm_default_params(fsv_asm_params *p);
-/* ONT-profile reads (BASELINE configs[4]: ~10 % error): k = 15, w = 15 without homopolymer compression (a 30 kb read then has ~3 750 minimizers: below the 4 096 a list holds), chain indel budget 0.15 / 0.05,
+/* ONT-profile reads (BASELINE configs[4]: ~10 % error): k = 15, w = 15 without homopolymer compression (a 30 kb read then has ~3 750 minimizers: below the 4 096 a list holds by default; full_lists = 1 lifts that cap), chain indel budget 0.15 / 0.05,
  * windows up to 25 % apart (k = 93: wide-band K5 / K6), overlaps up to 30 % error.  Parity unpinned: the reference has Flye here. */
 void fsv_asm_ont_params(fsv_asm_params *p);
 /* CLR reads (~12 % error, insertion-rich; the reference: flye --pacbio-raw, run_assembly.py:46-72): the ONT profile's values under a name of
  * their own.  Parity unpinned (no Flye in the tree or the image); planted truth in tests/test_gpu_ont.py.  Reads above ~32 kb lose the anchors
- * beyond their first 4 096 minimizers in either profile (set status bits 1 / 2 say so). */
+ * beyond their first 4 096 minimizers in either profile (set status bits 1 / 2 say so) unless full_lists = 1, which is off in both. */
 void fsv_asm_clr_params(fsv_asm_params *p);
 
 typedef struct fsv_mz {       /* ha_mz1_t, htab.h:8-13 */
@@ -283,6 +290,10 @@ typedef struct fsv_asm_stats {
     fsv_kernel_stat kernels[FSV_MAX_KERNEL_STATS];
 } fsv_asm_stats;
 int fsv_asm_last_stats(const fsv_ctx *ctx, fsv_asm_stats *out);
+/* full_lists = 1, the last fsv_assemble_batch on this context, all rounds, the final pass and chunks: minimizer lists above 4 096 entries that
+ * k_uniq_long indexed, and pairs beyond the chaining tile that k_chain_spill chained (their kernel times: the rows "k_uniq_long" and
+ * "k_chain_spill" of fsv_asm_stats.kernels, outside the k_uniq / k_chain rows).  Both 0 after a call with full_lists = 0. */
+int fsv_asm_last_long_lists(const fsv_ctx *ctx, uint64_t *n_reads, uint64_t *n_pairs);
 
 /* Test hook: after fsv_assemble_batch(...) with n_rounds = r, the corrected reads of the last round
  * can be fetched as ASCII (same order as the input reads). */
@@ -306,6 +317,15 @@ int fsv_asm_fetch_reads(fsv_ctx *ctx, char *seq, uint64_t seq_cap, uint64_t *off
 int fsv_asm_overlaps(fsv_ctx *ctx, const fsv_readsets *sets, const fsv_asm_params *params, int32_t pass, const uint32_t *rechain,
                      uint32_t n_rechain, fsv_ovl *ovl, uint64_t ovl_cap, uint32_t *pair_base, fsv_wtask *tasks, uint64_t task_cap,
                      uint32_t *n_tasks, uint32_t *overflow, uint32_t *warn);
+
+/* ---- the per-read index exposed (test hook): the sketch and the unique-minimizer index as the chain kernels see it, through the
+ * launch code of fsv_assemble_batch's overlap stage.  Read r with m minimizers whose hash occurs once in the read gets 2m entries at
+ * out_mz[out_off[r] .. out_off[r + 1]): [0, m) sorted by hash, [m, 2m) the same entries sorted by position; out_off has n_reads + 1 entries.
+ * full_lists as in fsv_asm_params: 0 cuts a list at 4 096 raw entries (warn[r] gets FSV_W_MZ_TRUNC), 1 indexes every entry; another value
+ * is FSV_EINVAL.  (w, k) as fsv_sketch_reads takes them with variant 0; the slots are the assembly's for the same (w, full_lists).
+ * warn: n_reads words of FSV_W_* bits. */
+int fsv_read_index(fsv_ctx *ctx, const fsv_readsets *sets, int32_t w, int32_t k, int32_t hpc, int32_t full_lists,
+                   fsv_mz *out_mz, uint64_t out_cap, uint64_t *out_off, uint32_t *warn);
 
 /* ---- K1 exposed: minimizer sketch of every read (ha_sketch, sketch.cpp:39-137) -------------------------
  * out_mz receives, per read, its minimizers in position order; out_off (n_reads+1) indexes them.
