@@ -541,6 +541,54 @@ struct PathJob {
     bool all_accepted;    // every task belongs to an accepted overlap (W.ovl then holds that one overlap)
 };
 
+// The two walk kernels nearly every window that needs a walk goes to: the sub-band kernel (distance 4 .. FSV_SB_MAXERR) and, a launch per
+// distance, the walk without the matrix (distance <= 3: nine in ten).  persistent(per_cu): the grid of path_stage.
+// STAMP (FSV_K6_STAMPS=1; diagnostic, never in a measured run): the kernels' stamp instantiations, each launch waited for and where its
+// waves spent their cycles printed -- PhaseClock's layout: cycles of phase i in h[i], trips through the list that passed it in h[8 + i].
+template <bool STAMP, class Grid>
+static int path_walks(fsv_ctx *ctx, AsmWs &W, const PathJob &J, Grid persistent)
+{
+    const uint32_t *store = J.store; const fsv_wtask *tasks = J.tasks; const fsv_wres *res = J.res; fsv_wpath *paths = J.paths;
+    uint32_t *ct = J.ct;
+    unsigned long long h[16] = {0};
+    uint32_t nl = 0;
+    auto clear_stamps = [&]() -> int { TRY(ensure(ctx, W.tmp, 16)); return zero(ctx, W.tmp, 16); };
+    auto read_stamps = [&](const uint32_t *cnt) -> int {   // waits for the launch: its stamps in h, its list's length in nl
+        TRY(download(ctx, h, W.tmp, 16));
+        if (cnt) FSV_HIP(ctx, hipMemcpyAsync(&nl, cnt, 4, hipMemcpyDeviceToHost, ctx->stream));
+        FSV_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        return FSV_OK;
+    };
+    auto per_wave = [&](int i) { return h[8 + i] ? (double)h[i] / h[8 + i] : 0.0; };
+    if (!W.occ_sb) FSV_HIP(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&W.occ_sb, k_path_sb<false>, 64, 0));
+    const uint32_t grid = persistent(W.occ_sb);
+    TRY(ensure(ctx, W.cols_sb, (size_t)grid * FSV_SB_QUADS * 64));
+    if (STAMP) TRY(clear_stamps());
+    FSV_LAUNCH(ctx, ctx->stream, k_path_sb<STAMP>, dim3(grid), dim3(64), 0, store, tasks, res, W.dp_list2.p, ct + CT_DP_SB, paths, W.cols_sb.p,
+               STAMP ? W.tmp.p : nullptr);
+    if (STAMP) {
+        TRY(read_stamps(nullptr));
+        fprintf(stderr, "[fsv] k_path_sb round %d: %llu waves, cycles per wave: forward %.0f, walk %.0f, finish %.0f (grid %u)\n", J.round, h[8], per_wave(0), per_wave(1),
+                per_wave(2), grid);
+    }
+    auto fr = [&](auto kern, int e, const Dev<uint32_t> &list, uint32_t *cnt) -> int {
+        int &pf = W.occ_fr[e - 1];
+        if (!pf || STAMP) FSV_HIP(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&pf, kern, 64, 0));
+        if (STAMP) TRY(clear_stamps());
+        FSV_LAUNCH(ctx, ctx->stream, kern, dim3(persistent(pf)), dim3(64), 0, store, tasks, res, list.p, cnt, paths, STAMP ? W.tmp.p : nullptr);
+        if (STAMP) {
+            TRY(read_stamps(cnt));
+            fprintf(stderr, "[fsv] k_path_fr<%d> round %d: %u windows, %llu waves (%d per CU), cycles per wave: table %.0f, walk %.0f, finish %.0f\n", e, J.round, nl, h[8], pf,
+                    per_wave(0), per_wave(1), per_wave(2));
+        }
+        return FSV_OK;
+    };
+    TRY(fr(k_path_fr<1, STAMP>, 1, W.dp_list16, ct + CT_DP_SB16));
+    TRY(fr(k_path_fr<2, STAMP>, 2, W.dp_list, ct + CT_DP));
+    TRY(fr(k_path_fr<3, STAMP>, 3, W.dp_list_e3, ct + CT_DP_FR3));
+    return FSV_OK;
+}
+
 // K6 for a task list: the fast paths, then the DP kernels on what is left (the lists and their counters live in the counter row J.ct).
 // Used for the window tasks of a round, the junction tasks of its second consensus pass, the junction cigars of its partition,
 // and for the caller's tasks of fsv_bpm_paths.
@@ -563,56 +611,13 @@ static int path_stage(fsv_ctx *ctx, AsmWs &W, const PathJob &J)
     // the rest by the general one
     W.kt.begin(ctx, J.pass, KN_PATH_DP, 0);
     // persistent grids, each block striding through its list, so the column scratch is a fixed few hundred MB whatever the number of windows
-    const bool stamps = getenv("FSV_K6_STAMPS") != nullptr;    // diagnostic: where a wave spends its cycles (never in a measured run)
-    unsigned long long h[4] = {0, 0, 0, 0};
-    uint32_t nl = 0;
-    auto read_stamps = [&](const uint32_t *cnt) -> int {   // waits for the launch: its stamps in h, its list's length in nl
-        TRY(download(ctx, h, W.tmp, 4));
-        if (cnt) FSV_HIP(ctx, hipMemcpyAsync(&nl, cnt, 4, hipMemcpyDeviceToHost, ctx->stream));
-        FSV_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        return FSV_OK;
-    };
-    if (!W.occ_sb) FSV_HIP(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&W.occ_sb, k_path_sb<false>, 64, 0));
-    const uint32_t grid = persistent(W.occ_sb);
-    TRY(ensure(ctx, W.cols_sb, (size_t)grid * FSV_SB_QUADS * 64));
-    if (stamps) {
-        TRY(ensure(ctx, W.tmp, 8));
-        TRY(zero(ctx, W.tmp, 8));
-        FSV_LAUNCH(ctx, ctx->stream, k_path_sb<true>, dim3(grid), dim3(64), 0, store, tasks, res, W.dp_list2.p, ct + CT_DP_SB, paths, W.cols_sb.p, W.tmp.p);
-        TRY(read_stamps(nullptr));
-        fprintf(stderr, "[fsv] k_path_sb round %d: %llu waves, cycles per wave: forward %.0f, walk %.0f, finish %.0f (grid %u)\n", J.round, h[3],
-                h[3] ? (double)h[0] / h[3] : 0.0, h[3] ? (double)h[1] / h[3] : 0.0, h[3] ? (double)h[2] / h[3] : 0.0, grid);
-    } else
-        FSV_LAUNCH(ctx, ctx->stream, k_path_sb<false>, dim3(grid), dim3(64), 0, store, tasks, res, W.dp_list2.p, ct + CT_DP_SB, paths, W.cols_sb.p,
-                   (unsigned long long *)nullptr);
-    // distance <= 3 (nine in ten): walked without the matrix, a launch per distance
-    auto fr = [&](auto kern, int e, const Dev<uint32_t> &list, uint32_t *cnt) -> int {
-        int &pf = W.occ_fr[e - 1];
-        if (!pf || stamps) FSV_HIP(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&pf, kern, 64, 0));
-        if (stamps) { TRY(ensure(ctx, W.tmp, 8)); TRY(zero(ctx, W.tmp, 8)); }
-        FSV_LAUNCH(ctx, ctx->stream, kern, dim3(persistent(pf)), dim3(64), 0, store, tasks, res, list.p, cnt, paths, stamps ? W.tmp.p : nullptr);
-        if (stamps) {
-            TRY(read_stamps(cnt));
-            fprintf(stderr, "[fsv] k_path_fr<%d> round %d: %u windows, %llu waves (%d per CU), cycles per wave: table %.0f, walk %.0f, finish %.0f\n", e, J.round, nl, h[3], pf,
-                    h[3] ? (double)h[0] / h[3] : 0.0, h[3] ? (double)h[1] / h[3] : 0.0, h[3] ? (double)h[2] / h[3] : 0.0);
-        }
-        return FSV_OK;
-    };
-    if (stamps) {
-        TRY(fr(k_path_fr<1, true>, 1, W.dp_list16, ct + CT_DP_SB16));
-        TRY(fr(k_path_fr<2, true>, 2, W.dp_list, ct + CT_DP));
-        TRY(fr(k_path_fr<3, true>, 3, W.dp_list_e3, ct + CT_DP_FR3));
-    } else {
-        TRY(fr(k_path_fr<1>, 1, W.dp_list16, ct + CT_DP_SB16));
-        TRY(fr(k_path_fr<2>, 2, W.dp_list, ct + CT_DP));
-        TRY(fr(k_path_fr<3>, 3, W.dp_list_e3, ct + CT_DP_FR3));
-    }
+    TRY(getenv("FSV_K6_STAMPS") ? path_walks<true>(ctx, W, J, persistent) : path_walks<false>(ctx, W, J, persistent));
     // the general kernel's lists are short (rescue windows, distances above 7): two blocks per CU are plenty
-    const uint32_t gridg = persistent(2), stride = gridg * 64;
-    TRY(ensure(ctx, W.cols, (size_t)stride * (FSV_WINDOW + 2) * 3));
-    FSV_LAUNCH(ctx, ctx->stream, k_path_dp<uint32_t>, dim3(gridg), dim3(64), 0, store, tasks, W.dp_list3.p, 0u, 0u, paths,
-               (uint32_t *)W.cols.p /* 32-bit columns in the same scratch */, stride, ct + CT_DP_GEN);
-    FSV_LAUNCH(ctx, ctx->stream, k_path_dp<uint64_t>, dim3(gridg), dim3(64), 0, store, tasks, W.dp_wide.p, 0u, 0u, paths, W.cols.p, stride, ct + CT_DP_WIDE);
+    const uint32_t gridg = persistent(2);
+    TRY(ensure(ctx, W.cols, (size_t)gridg * 64 * (FSV_WINDOW + 2) * 3));
+    FSV_LAUNCH(ctx, ctx->stream, k_path_dp<uint32_t>, dim3(gridg), dim3(64), 0, store, tasks, W.dp_list3.p, ct + CT_DP_GEN, paths,
+               (uint32_t *)W.cols.p /* 32-bit columns in the same scratch */);
+    FSV_LAUNCH(ctx, ctx->stream, k_path_dp<uint64_t>, dim3(gridg), dim3(64), 0, store, tasks, W.dp_wide.p, ct + CT_DP_WIDE, paths, W.cols.p);
     if (J.wide_bands) {
         // bands above 63 rows: every gapped window of an ONT-profile batch; 1.15 MB of column scratch per persistent block
         if (!W.occ_wide) FSV_HIP(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&W.occ_wide, k_path_wide, 64, 0));
@@ -925,13 +930,13 @@ static int verify_stage(fsv_ctx *ctx, AsmWs &W, const Round &R)
             FSV_LAUNCH(ctx, ctx->stream, k_rescue_accept<false>, dim3(fsv_grid_for(B.n_pairs, 64)), dim3(64), 0, R.store, W.ovl.p, B.n_pairs, W.tasks.p, W.res.p, cols,
                        W.ovl_c.p, P.k_cap, P.accept_err_pm, W.left_list.p, ct + CT_LEFT);
             FSV_LAUNCH(ctx, ctx->stream, k_left_rescue<false>, dim3(gridl), dim3(64), 0, R.store, W.ovl.p, W.left_list.p, ct + CT_LEFT, W.tasks.p, W.res.p, W.paths.p,
-                       (uint64_t *)nullptr, W.ovl_c.p, P.k_cap, P.accept_err_pm);
+                       W.ovl_c.p, P.k_cap, P.accept_err_pm);
         } else {
             // the same two kernels with the error-rate test deferred: charge_stage gives the verdict once K6 has run
             FSV_LAUNCH(ctx, ctx->stream, (k_rescue_accept<false, true>), dim3(fsv_grid_for(B.n_pairs, 64)), dim3(64), 0, R.store, W.ovl.p, B.n_pairs, W.tasks.p, W.res.p,
                        cols, W.ovl_c.p, P.k_cap, P.accept_err_pm, W.left_list.p, ct + CT_LEFT);
             FSV_LAUNCH(ctx, ctx->stream, k_left_rescue<true>, dim3(gridl), dim3(64), 0, R.store, W.ovl.p, W.left_list.p, ct + CT_LEFT, W.tasks.p, W.res.p, W.paths.p,
-                       (uint64_t *)nullptr, W.ovl_c.p, P.k_cap, P.accept_err_pm);
+                       W.ovl_c.p, P.k_cap, P.accept_err_pm);
         }
     }
     W.kt.end(ctx);

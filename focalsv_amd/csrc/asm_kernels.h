@@ -194,19 +194,22 @@ __device__ __forceinline__ ChainPair chain_pair_of(const ChainArgs &A, const uin
 // supplies the key packing, the arrays (or typed accessors), the "no predecessor" value, the width of the repair step's packed maximum
 // and whether phase stamps exist.
 
-// FSV_CHAIN_STAMPS=1: shader cycles per phase summed over the waves (the tile kernels; the slab's clock is empty)
-template <bool ON> struct ChainClock {
+// Phase stamps of a diagnostic run: shader cycles since the last mark (or restart) added to stamps[phase] and one to stamps[8 + phase],
+// by the wave's lane 0.  FSV_CHAIN_STAMPS=1: the tile kernels, one block in 64 (the atomics must not become the load; the slab's clock
+// is empty); FSV_K6_STAMPS=1: k_path_sb<true> and k_path_fr<E, true>, every block.  PhaseClock<false> is empty: no stamp code at all.
+template <bool ON> struct PhaseClock {
     bool on; unsigned long long tm;
-    __device__ __forceinline__ explicit ChainClock(const ChainArgs &A) : on(A.stamps && (blockIdx.x & 63u) == 0u), tm(0ull)   // one block in 64: the atomics must not become the load
-    { if (on) tm = __builtin_amdgcn_s_memtime(); }
-    __device__ __forceinline__ void mark(const ChainArgs &A, const int lane, const int i)
+    __device__ __forceinline__ explicit PhaseClock(const bool sample) : on(sample), tm(0ull) { restart(); }
+    __device__ __forceinline__ void restart() { if (on) tm = __builtin_amdgcn_s_memtime(); }
+    __device__ __forceinline__ void mark(unsigned long long *stamps, const int lane, const int i)
     {
-        if (on) { const unsigned long long t_ = __builtin_amdgcn_s_memtime(); if (lane == 0) { atomicAdd(&A.stamps[i], t_ - tm); atomicAdd(&A.stamps[8 + i], 1ull); } tm = t_; }
+        if (on) { const unsigned long long t_ = __builtin_amdgcn_s_memtime(); if (lane == 0) { atomicAdd(&stamps[i], t_ - tm); atomicAdd(&stamps[8 + i], 1ull); } tm = t_; }
     }
 };
-template <> struct ChainClock<false> {
-    __device__ __forceinline__ explicit ChainClock(const ChainArgs &) {}
-    __device__ __forceinline__ void mark(const ChainArgs &, int, int) {}
+template <> struct PhaseClock<false> {
+    __device__ __forceinline__ explicit PhaseClock(bool) {}
+    __device__ __forceinline__ void restart() {}
+    __device__ __forceinline__ void mark(unsigned long long *, int, int) {}
 };
 
 // The LDS tile.  SHORT (every read of the batch shorter than 65 536 bases -- all HiFi data): 12 B per anchor -- the anchor's two
@@ -224,7 +227,7 @@ struct ChainTile {
     using dp_t = typename std::conditional<SHORT, uint16_t, int32_t>::type;
     using idx_t = uint16_t;
     using pack_t = int;             // candidate score * 64 + lane: a tile's scores stay far below 2^25
-    using Clock = ChainClock<true>;
+    using Clock = PhaseClock<true>;
     static constexpr int NONE = 0xffff;
     static constexpr int KSH = SHORT ? 16 : 32;
     static constexpr uint64_t KMASK = SHORT ? 0xffffull : 0xffffffffull;
@@ -266,7 +269,7 @@ struct ChainSlab {
     using dp_t = int32_t;
     using idx_t = int32_t;
     using pack_t = long long;       // slab scores can pass 2^25
-    using Clock = ChainClock<false>;
+    using Clock = PhaseClock<false>;
     static constexpr int NONE = -1;
     int cap;
     key_t *key;
@@ -360,7 +363,7 @@ __device__ __forceinline__ void chain_core(const ChainArgs &A, const S &st, cons
         __syncthreads();
     }
     n = m2;
-    if (n < A.min_anchors) { put_both(); clk.mark(A, lane, 2); return; }
+    if (n < A.min_anchors) { put_both(); clk.mark(A.stamps, lane, 2); return; }
     // 3. anchors are in query order: q's minimizers were walked by position and both compactions keep the order (query positions
     //    are distinct, so (qe, te) order == qe order) -- for a reverse-strand pair that is decreasing order on the query's reverse
     //    strand, so the list is turned around
@@ -373,7 +376,7 @@ __device__ __forceinline__ void chain_core(const ChainArgs &A, const S &st, cons
     //    the DP provably links each anchor to its nearest predecessor -- gap 0 means no indel penalty, and
     //    f[i-1] + min(d_i,k) >= f[j] + min(qe_i - qe_j, k) for every j < i-1 because min(.,k) is sub-additive, with the
     //    nearest predecessor winning ties -- so the chain is the whole list and the score a running sum.
-    clk.mark(A, lane, 3);
+    clk.mark(A.stamps, lane, 3);
     bool colinear;
     {
         const int d0 = st.t(0) - st.q(0);
@@ -489,7 +492,7 @@ __device__ __forceinline__ void chain_core(const ChainArgs &A, const S &st, cons
         }
         __syncthreads();
     }
-    clk.mark(A, lane, 4);
+    clk.mark(A.stamps, lane, 4);
     // 5. best chain end: highest score, smallest index on ties
     long long bk = -1;
     for (int i = lane; i < n; i += 64) { const long long v = ((long long)st.f[i] << 32) | (long long)(0x7fffffff - i); bk = v > bk ? v : bk; }
@@ -523,7 +526,7 @@ __device__ __forceinline__ void chain_core(const ChainArgs &A, const S &st, cons
         }
     }
     __syncthreads();
-    clk.mark(A, lane, 5);
+    clk.mark(A.stamps, lane, 5);
     if (cnt < A.min_anchors) { put_both(); return; }
     const int first = st.chain[cnt - 1];
     int xs = st.q(first), ys = st.t(first);
@@ -570,7 +573,7 @@ __device__ __forceinline__ void chain_core(const ChainArgs &A, const S &st, cons
     const uint32_t xw = A.word_off[rq], yw = A.word_off[rt];
     chain_window_tasks(A, [&](int e) { return st.q(st.chain[cnt - 1 - e]); }, [&](int e) { return st.t(st.chain[cnt - 1 - e]); }, cnt, lane, o, om, first_win, xw, yw, lenq, lent, rev, p, pm, xs, xe);
     put_both();
-    clk.mark(A, lane, 6);
+    clk.mark(A.stamps, lane, 6);
 }
 
 // One wavefront per UNORDERED read pair (q < t) of a set: the chain is computed with q as the query and the overlap of t on
@@ -590,7 +593,7 @@ __device__ __forceinline__ void chain_pair(const ChainArgs &A, unsigned char *s_
     // and holds them in ~80 extra registers -- two waves per SIMD instead of three)
     asm volatile("" : "+v"(lane_));
     const int lane = lane_;
-    typename Tile::Clock clk(A);
+    typename Tile::Clock clk(A.stamps && (blockIdx.x & 63u) == 0u);
 
     // 1. anchors: every q minimizer is looked up in t's sorted unique list.  All global loads are issued up front -- t's
     //    hashes go to LDS (the long layout also stages {pos, span, strand}: 12 B per entry in the DP arrays, free until the
@@ -641,7 +644,7 @@ __device__ __forceinline__ void chain_pair(const ChainArgs &A, unsigned char *s_
         if (lane == 0) s_bk[64] = (uint32_t)nt;
         __syncthreads();
     }
-    clk.mark(A, lane, 0);
+    clk.mark(A.stamps, lane, 0);
     int n = 0, nrev = 0, nfwd = 0;
     auto lookup = [&](int i, const uint4 av) {
         bool hit = false; typename Tile::key_t key = 0; uint32_t srev = 0, tspan = 0;
@@ -727,7 +730,7 @@ __device__ __forceinline__ void chain_pair(const ChainArgs &A, unsigned char *s_
         n = AMAX;
     }
     __syncthreads();
-    clk.mark(A, lane, 1);
+    clk.mark(A.stamps, lane, 1);
     chain_core(A, st, P, n, nrev, nfwd, lane, clk);
 }
 
@@ -840,7 +843,7 @@ __device__ __forceinline__ void chain_pair_spill(const ChainArgs &A, const uint4
     const ChainPair P = chain_pair_of(A, pt);
     const int lane = threadIdx.x;
     const uint4 *mq4 = (const uint4 *)P.mq;
-    ChainSlab::Clock clk(A);
+    ChainSlab::Clock clk(false);
     int n = 0, nrev = 0, nfwd = 0;
     for (int base = 0; base < P.nq; base += 64) {
         const int i = base + lane;
@@ -957,20 +960,37 @@ __global__ __launch_bounds__(64) void k_rescue_accept(const uint32_t *__restrict
 }
 
 // ------------------------------------------------------------------------------------------------ K6 paths
-__device__ __forceinline__ void ops_set(uint8_t *ops, int i, uint32_t v) { ops[i >> 2] = (uint8_t)((ops[i >> 2] & ~(3u << ((i & 3) << 1))) | (v << ((i & 3) << 1))); }
-__device__ __forceinline__ uint32_t ops_get(const uint8_t *ops, int i) { return (ops[i >> 2] >> ((i & 3) << 1)) & 3u; }
-
-// y base of the padded window column c for a task
-__device__ __forceinline__ uint32_t task_ybase(const uint32_t *__restrict__ store, const fsv_wtask &t, int c)
-{
-    return bpm_ywin_base(store, t, t.y_start - t.k, c);
-}
-
 // Fast paths of Reserve_Banded_BPM_PATH (Levenshtein_distance.h:516-531): err == 0, or a gap-free placement with
 // exactly err mismatches (try_cigar).  Everything else is queued for one of the walk kernels.
 struct PathLists {      // task lists and their device-side lengths: 0-2 k_path_fr<1..3>, 3 k_path_sb, 4 k_path_dp<32>, 5 k_path_dp<64>, 6 k_path_wide,
     uint32_t *list[8], *cnt[8];   // 7 (may be null): windows whose alignment may touch the edge of its band (k_fix_boundary looks at them again)
 };
+// The record of a window's path, for the gap-free placement (path_gapfree) and for the walked paths (path_finish): the y interval
+// [start, end] in padded-window columns, the distance after generate_cigar and plen ops, of which word(wd) gives the wd-th sixteen,
+// start-to-end.  pad: bit 0 = an op other than a match among the first ten, bit 1 = among the last ten (tail10: those fields) -- what
+// scan_cigar (Correct.cpp:1070) over ten columns from either end asks about (calculate_boundary_cigars :2360; k_bcig_tasks reads the
+// header only); bit 2 = raw0: the alignment started in the padded window's first column before generate_cigar moved it (fix_boundary's
+// question).  with_ops false (path_gapfree, distance 0: every op a match): the record carries no ops -- its consumers (k_consensus,
+// k_het) look at err first and never read them, and in the later correction rounds nearly every window is one: 24 bytes out instead of 128.
+template <class Words>
+__device__ __forceinline__ void path_record(fsv_wpath *__restrict__ P, const fsv_wtask &t, int start, int end, int plen, int err, bool raw0, uint32_t tail10,
+                                            bool with_ops, Words word)
+{
+    uint32_t head10 = 0;
+    if (with_ops) {
+        uint2 *dst = reinterpret_cast<uint2 *>(P->ops); // ops sit at byte 24 of the record: 8-byte aligned
+        for (int i = 0; i < FSV_PATH_CAP / 32; i++) {
+            const uint32_t v0 = word(2 * i), v1 = word(2 * i + 1);
+            if (i == 0) head10 = v0 & 0xfffffu;
+            dst[i] = make_uint2(v0, v1);
+        }
+    }
+    P->ry_start = t.y_start - t.k + start;
+    P->ry_end = t.y_start - t.k + end;
+    P->path_len = (int16_t)plen; P->err = (int16_t)err; P->state = 1; P->y_rev = t.y_rev;
+    P->pad = (uint16_t)((head10 ? 1u : 0u) | (tail10 ? 2u : 0u) | (raw0 ? 4u : 0u)); P->y_word = t.y_word; P->y_len = t.y_len;
+}
+
 // try_cigar (Levenshtein_distance.h:465-507): the gap-free placement on the end diagonal K5 reported.  When its mismatches are the
 // window's distance that is the path (generate_cigar then only trims mismatches at the two ends into x-only ops): the record is
 // written and true returned; false: the window needs a walk.  One lane per window, no cross-lane traffic.
@@ -996,12 +1016,8 @@ __device__ __forceinline__ bool path_gapfree(const uint32_t *__restrict__ store,
                 for (int q = 0; q < 4; q++) {
                     const int b = c * 4 + q;
                     if (b * 16 < n) {
-                        uint32_t d = xb4[q] ^ yb4[q];
-                        d = (d | (d >> 1)) & 0x55555555u;
-                        // columns outside the read ('N') never match; columns past the window do not count
-                        uint32_t inval = ~yv4[q] & 0xffffu, spread = 0;
-                        for (int j = 0; j < 16; j++) spread |= ((inval >> j) & 1u) << (2 * j);
-                        d |= spread;
+                        uint32_t d = mismatch_fields16(xb4[q], yb4[q], yv4[q]);
+                        // columns past the window do not count
                         const int lim = min(16, n - b * 16);
                         if (lim < 16) d &= (1u << (2 * lim)) - 1u;
                         ops32[b] = d;
@@ -1020,21 +1036,13 @@ __device__ __forceinline__ bool path_gapfree(const uint32_t *__restrict__ store,
         for (int i = n - 1; i >= 0 && ((ops32[i >> 4] >> ((i & 15) << 1)) & 3u) == 1u; i--) { ops32[i >> 4] |= 3u << ((i & 15) << 1); e2--; }
         for (int i = 0; i < n && ((ops32[i >> 4] >> ((i & 15) << 1)) & 3u) == 1u; i++) { ops32[i >> 4] |= 3u << ((i & 15) << 1); s2++; }
     }
-    P->ry_start = t.y_start - t.k + s2;
-    P->ry_end = t.y_start - t.k + e2;
-    uint32_t flags10 = 0;      // as in path_finish: an op other than a match among the first / last ten
+    uint32_t tail10 = 0;
     if (r.err > 0) {
         const int a = max(n - 10, 0), wi = a >> 4, sh = (a & 15) << 1;
         const uint32_t lo = ops32[wi] >> sh, hi = (sh && wi + 1 < 26) ? ops32[wi + 1] << (32 - sh) : 0u;
-        flags10 = ((ops32[0] & 0xfffffu) ? 1u : 0u) | (((lo | hi) & 0xfffffu) ? 2u : 0u) | (start == 0 ? 4u : 0u);   // bit 2: the alignment starts in the padded window's first column
+        tail10 = (lo | hi) & 0xfffffu;
     }
-    P->path_len = (int16_t)n; P->err = (int16_t)r.err; P->state = 1; P->y_rev = t.y_rev; P->pad = (uint16_t)flags10; P->y_word = t.y_word; P->y_len = t.y_len;
-    // a distance-0 record carries no ops: its consumers (k_consensus, k_het) look at err first and never read them, and in the
-    // later correction rounds nearly every window is one -- 24 bytes out instead of 128
-    if (r.err == 0 && !write_clean_ops) return true;
-    uint2 *dst = reinterpret_cast<uint2 *>(P->ops); // ops sit at byte 24 of the record: 8-byte aligned
-#pragma unroll
-    for (int i = 0; i < 13; i++) dst[i] = make_uint2(ops32[2 * i], ops32[2 * i + 1]);
+    path_record(P, t, s2, e2, n, r.err, r.err > 0 && start == 0, tail10, r.err > 0 || write_clean_ops, [&](int wd) { return ops32[wd]; });
     return true;
 }
 
@@ -1080,53 +1088,76 @@ __global__ __launch_bounds__(256) void k_path_fast(const uint32_t *__restrict__ 
     }
 }
 
-// base access through one cached 16-base word (forward position >> 4 is the key)
-struct XBaseCache {
-    uint32_t w = 0; int idx = -1;
-    __device__ __forceinline__ uint32_t get(const uint32_t *__restrict__ store, uint32_t word_off, int pos)
+// One lane's walk back through the DP (Levenshtein_distance.h:757-888) as every K6 kernel records it: the path in the lane's column of
+// the block's LDS array s_ops[28][64] -- 2 bits per op (0 diagonal over a match, 1 diagonal over a mismatch, 2 up, 3 left), stored
+// end-to-start, 448 ops -- and where the walk stands: the ops so far, the y column of the padded window the alignment would start in if
+// the rest were matches, the x column, the errors left, the band row (absolute, or relative to the rows a kernel keeps), the last op.
+// The ops are gathered in a register that goes to LDS once per 16 steps.
+struct PathWalk {
+    static constexpr int WORDS = 28, CAP = WORDS * 16;
+    uint32_t (*ops)[64]; int lane;
+    int plen, start, ci, cur, row, dir;
+    uint32_t acc;
+    __device__ __forceinline__ PathWalk(uint32_t (*s_ops)[64], int lane64) : ops(s_ops), lane(lane64) {}
+    // a window of n columns whose alignment ends in window column `end` on band row `row_` with distance `err`
+    __device__ __forceinline__ void clear(int n, int end, int err, int row_)
     {
-        const int wi = pos >> 4;
-        if (wi != idx) { w = store[word_off + (uint32_t)wi]; idx = wi; }
-        return (w >> ((pos & 15) << 1)) & 3u;
+        for (int i = 0; i < WORDS; i++) ops[i][lane] = 0;
+        plen = 0; start = end; ci = n - 1; cur = err; row = row_; dir = 0; acc = 0;
     }
-};
-struct YBaseCache {   // task_ybase: window column c of the (strand-oriented) target, 4 outside the read
-    uint32_t w = 0; int idx = -1;
-    __device__ __forceinline__ uint32_t get(const uint32_t *__restrict__ store, const fsv_wtask &t, int c)
+    // one step: the op is recorded and the walk moves -- "up" stays in its column, "left" keeps its y base, every op but a match spends an error
+    __device__ __forceinline__ void put(uint32_t code)
     {
-        const int p = t.y_start - t.k + c;
-        if (p < 0 || p >= t.y_len) return 4u;
-        const int q = t.y_rev ? (t.y_len - 1 - p) : p, wi = q >> 4;
-        if (wi != idx) { w = store[t.y_word + (uint32_t)wi]; idx = wi; }
-        const uint32_t b = (w >> ((q & 15) << 1)) & 3u;
-        return t.y_rev ? 3u - b : b;
+        acc |= code << ((plen & 15) << 1);
+        if ((plen & 15) == 15) { ops[plen >> 4][lane] = acc; acc = 0; }
+        plen++;
+        cur -= (int)(code != 0u);
+        start -= (int)(code != 3u);
+        row += (int)(code == 3u) - (int)(code == 2u);
+        ci -= (int)(code != 2u);
+        dir = (int)code;
+    }
+    // a run of matches: the fields are already 0, a word that fills up with them goes out
+    __device__ __forceinline__ void matches(int steps)
+    {
+        const int np = plen + steps;
+        if ((np >> 4) != (plen >> 4)) { ops[plen >> 4][lane] = acc; acc = 0; }
+        plen = np; start -= steps; ci -= steps; dir = 0;
+    }
+    __device__ __forceinline__ void flush() { if (plen & 15) ops[plen >> 4][lane] = acc; }
+    // the recorded path, for generate_cigar: op i (0 = the alignment's last), a word of 16 of them
+    __device__ __forceinline__ uint32_t word(int wi) const { return ops[wi][lane]; }
+    __device__ __forceinline__ uint32_t get(int i) const { return (ops[i >> 4][lane] >> ((i & 15) << 1)) & 3u; }
+    __device__ __forceinline__ void set(int i, uint32_t v)
+    {
+        const int wi = i >> 4, sh = (i & 15) << 1;
+        ops[wi][lane] = (ops[wi][lane] & ~(3u << sh)) | (v << sh);
     }
 };
 
-// The end of K6, shared by the two DP kernels: the all-match rest of the walk, generate_cigar's end trimming and greedy gap
-// left-shift (Correct.cpp:1302-1536) on the path in LDS (2 bits per op, end-to-start), and the record.
-#define TMP(i) ((s_ops[(i) >> 4][lane64] >> (((i) & 15) << 1)) & 3u)
-#define TMP_SET(i, v) do { const int w_ = (i) >> 4, sh_ = ((i) & 15) << 1; s_ops[w_][lane64] = (s_ops[w_][lane64] & ~(3u << sh_)) | ((uint32_t)(v) << sh_); } while (0)
-__device__ __forceinline__ void path_finish(const uint32_t *__restrict__ store, const fsv_wtask &t, fsv_wpath *__restrict__ P, uint32_t (*s_ops)[64],
-                                            int lane64, int col, int dir, int plen, int start, int end, int err)
+// The end of K6, shared by all the walks: the all-match rest of the walk, generate_cigar's end trimming and greedy gap left-shift
+// (Correct.cpp:1302-1536) on the path in LDS, and the record.
+__device__ __forceinline__ void path_finish(const uint32_t *__restrict__ store, const fsv_wtask &t, fsv_wpath *__restrict__ P, PathWalk &w, int end, int err)
 {
+    int plen = w.plen, start = w.start, dir = w.dir;
+    const int col = w.ci + 1;
     if (col > 0) { start -= col; plen += col; dir = 0; } // the rest of the path is matches: the fields are already 0
     // a record holds FSV_PATH_CAP ops (x_len + k <= 406 for hifiasm's thresholds: never reached); a longer path -- a wide-band
     // window with more than 41 inserted bases -- leaves the window without a path, as oracle/asm.c:window_path does
     if (plen > FSV_PATH_CAP) { P->state = 0; return; }
     if (dir != 3) start++;
-    const uint32_t raw0 = (err > 0 && start == 0) ? 4u : 0u;      // the alignment starts in the padded window's first column (before generate_cigar moves it): fix_boundary's question
-    // generate_cigar: TMP is stored end-to-start
+    const bool raw0 = err > 0 && start == 0;      // before generate_cigar moves the start
+    // generate_cigar: the path is stored end-to-start
     if (err > 0) {
         int stop = -1;
-        for (int i = 0; i < plen && TMP(i) == 1; i++) { TMP_SET(i, 3); end--; stop = i; }
-        for (int i = plen - 1; i >= 0 && TMP(i) == 1; i--) { TMP_SET(i, 3); start++; }
+        for (int i = 0; i < plen && w.get(i) == 1; i++) { w.set(i, 3); end--; stop = i; }
+        for (int i = plen - 1; i >= 0 && w.get(i) == 1; i--) { w.set(i, 3); start++; }
         int xi = 0, yi = 0;
-        XBaseCache xc; YBaseCache yc;
+        BaseCache xc, yc;
         for (int i = plen - 1; i > stop;) {
             // runs of match / mismatch ops are skipped a path word at a time: a gap op is a field with its high bit set
             const int f = i & 15;
-            const uint32_t wv = s_ops[i >> 4][lane64];
+            const uint32_t wv = w.word(i >> 4);
             const uint32_t m = wv & 0xAAAAAAAAu & (f == 15 ? 0xffffffffu : ((1u << (2 * f + 2)) - 1u));
             const int skip = min(m == 0u ? f + 1 : f - ((31 - __clz(m)) >> 1), i - stop);
             if (skip > 0) { xi += skip; yi += skip; i -= skip; continue; }
@@ -1135,128 +1166,106 @@ __device__ __forceinline__ void path_finish(const uint32_t *__restrict__ store, 
             int pi = i + 1, x2 = xi, y2 = yi;
             if (op == 3) y2--; else x2--;
             for (; pi < plen && x2 >= 0 && y2 >= 0; pi++, x2--, y2--) {
-                const uint32_t pv = TMP(pi);
+                const uint32_t pv = w.get(pi);
                 // the shift reads bases at falling positions: one 16-base word per 16 steps instead of two dependent global loads
                 // per step (a gap inside a homopolymer travels a long way, and the whole wave waits for its slowest lane)
-                const bool same = xc.get(store, t.x_word, t.x_start + x2) == yc.get(store, t, start + y2);
+                const bool same = xc.get(store, t.x_word, t.x_start + x2) == yc.ycol(store, t, start + y2);
                 if (pv >= 2 || (pv == 0 && !same)) break;
-                if (pv == 1 && same) { TMP_SET(pi - 1, 0); err--; }
-                else TMP_SET(pi - 1, pv);
-                TMP_SET(pi, op);
+                if (pv == 1 && same) { w.set(pi - 1, 0); err--; }
+                else w.set(pi - 1, pv);
+                w.set(pi, op);
             }
             if (op == 2) yi++; else xi++;
             i--;
         }
     }
-    // pack start-to-end: output word wd holds the source fields plen-16-16wd .. plen-1-16wd in reverse order
-    const int pl = min(plen, FSV_PATH_CAP);
-    uint32_t *dst = reinterpret_cast<uint32_t *>(P->ops);
-    uint32_t head10 = 0;
-    for (int wd = 0; wd < 26; wd++) {
+    // the record holds the ops start-to-end: its word wd is the path's fields plen-16-16wd .. plen-1-16wd in reverse order
+    auto packed = [&](int wd) -> uint32_t {
         const int a = plen - 16 - 16 * wd;
         uint32_t v = 0;
         if (a >= 0) {
             const int wi = a >> 4, sh = (a & 15) << 1;
-            const uint32_t w0 = s_ops[wi][lane64], w1 = (sh && wi + 1 < 28) ? s_ops[wi + 1][lane64] : 0u;
+            const uint32_t w0 = w.word(wi), w1 = (sh && wi + 1 < PathWalk::WORDS) ? w.word(wi + 1) : 0u;
             v = sh ? (w0 >> sh) | (w1 << (32 - sh)) : w0;
-        } else if (a > -16) v = s_ops[0][lane64] << ((-a) << 1);
-        v = rev_fields2(v);
-        if (wd == 0) head10 = v & 0xfffffu;
-        dst[wd] = v;
-    }
-    P->ry_start = t.y_start - t.k + start;
-    P->ry_end = t.y_start - t.k + end;
-    // pad: bit 0 = an op other than a match among the first ten, bit 1 = among the last ten -- what scan_cigar (Correct.cpp:1070) over ten
-    // columns from either end asks about (calculate_boundary_cigars :2360; k_bcig_tasks reads the header only)
-    const uint32_t tail10 = s_ops[0][lane64] & 0xfffffu;
-    P->path_len = (int16_t)pl; P->err = (int16_t)err; P->state = 1; P->y_rev = t.y_rev; P->pad = (uint16_t)((head10 ? 1u : 0u) | (tail10 ? 2u : 0u) | raw0); P->y_word = t.y_word; P->y_len = t.y_len;
+        } else if (a > -16) v = w.word(0) << ((-a) << 1);
+        return rev_fields2(v);
+    };
+    path_record(P, t, start, end, plen, err, raw0, w.word(0) & 0xfffffu, true, packed);
 }
-#undef TMP
-#undef TMP_SET
 
-// General K6 (any band up to 63 rows, any distance): forward pass keeping {D0, VP, VN} of every column in a per-lane slice of
-// an HBM scratch ([block][column][word][lane]), the reference's walk back on those words, then path_finish.  Since round 2
+// General K6 (any band up to 63 rows, any distance): forward pass keeping {D0, VP, VN} of every column in a per-lane scratch, the
+// reference's walk back on those words, then path_finish.  Since round 2
 // this is the fallback: first-pass windows (k <= 15) at distance <= FSV_SB_MAXERR go through k_path_sb below, which keeps
 // 4 bytes per column instead of 12 and walks without a dependent global load per step; what is left for this kernel are
 // the doubled-threshold rescue windows (k > 15) and distances above 7 -- a fraction of a percent of the HiFi windows.
 // WordT = uint32_t for bands of at most 31 diagonals (k <= 15): the walk back only looks at bits below the band width, so the
 // low halves of D0 / VP / VN are all it needs and the scratch traffic halves; uint64_t for the doubled thresholds (k <= 31).
-template <class WordT> struct PathSink {
-    WordT *cols; uint32_t stride, lane;
+// LANES: the lanes that share the scratch -- 64: a block's slice in HBM, [column][word][lane] (k_path_dp); 1: one lane's columns in LDS
+// (k_fix_boundary, k_left_rescue)
+template <class WordT, int LANES> struct PathSink {
+    WordT *cols; uint32_t lane;
+    __device__ __forceinline__ WordT &at(int c, int w) const { return cols[((size_t)c * 3 + w) * LANES + lane]; }
     __device__ __forceinline__ void operator()(int i, uint64_t d0, uint64_t vp, uint64_t vn) const
     {
-        WordT *c = cols + (size_t)(i + 1) * 3 * stride + lane;
-        c[0] = (WordT)d0; c[stride] = (WordT)vp; c[2 * (size_t)stride] = (WordT)vn;
+        at(i + 1, 0) = (WordT)d0; at(i + 1, 1) = (WordT)vp; at(i + 1, 2) = (WordT)vn;
     }
 };
 
-// Reserve_Banded_BPM_PATH by one lane for one window: the forward pass with every column's {D0, VP, VN} kept in the lane's slice of the
-// HBM scratch, the walk back, generate_cigar and the record (path_finish).  The general K6 kernel's body; k_left_rescue calls it too.
-template <class WordT>
+// Reserve_Banded_BPM_PATH by one lane for one window: the forward pass with every column's {D0, VP, VN} kept in the lane's scratch, the
+// walk back, generate_cigar and the record (path_finish).  The general K6 kernel's body; fix_boundary and k_left_rescue call it too.
+template <class WordT, int LANES>
 __device__ __forceinline__ void path_general(const uint32_t *__restrict__ store, const fsv_wtask &t, fsv_wpath *__restrict__ P, uint32_t (*s_ops)[64],
-                                             int lane64, WordT *cols_slice, uint32_t cstride = 64u)
+                                             int lane64, WordT *cols_slice)
 {
-    // cols_slice: the scratch of this lane's block, word w of column c of lane l at ((c) * 3 + w) * cstride + l (k_path_dp: 64 lanes a
-    // block in HBM; k_left_rescue: one lane a block, in LDS)
     const int n = t.x_len, k = t.k, band = 2 * k + 1;
     fsv_wres r;
-    PathSink<WordT> sink{cols_slice, cstride, cstride == 1u ? 0u : (uint32_t)lane64};
+    const PathSink<WordT, LANES> sink{cols_slice, LANES == 1 ? 0u : (uint32_t)lane64};
     bpm_run(store, t, r, sink);
     if (r.err < 0) { P->state = 0; return; } // cannot happen: K5 matched this window
-#define COL(c, w) (sink.cols[((c) * 3 + (w)) * (size_t)sink.stride + sink.lane])
-    for (int i = 0; i < 28; i++) s_ops[i][lane64] = 0;
-    int end = r.end_site, err = r.err;
-    int cur = err, col = n, plen = 0, start = end, row = band - (n + 2 * k - end), dir = 0;
-    {
+    PathWalk w(s_ops, lane64);
+    w.clear(n, r.end_site, r.err, band - (n + 2 * k - r.end_site));
     // the kernel is instruction-bound (4-5 waves per SIMD keep the issue slots full), so the walk is written for few
-    // instructions: WordT-wide bit tests (only band bits are read), the column it leaves behind handed to the next step
-    // instead of re-read, and the ops gathered in a register that goes to LDS once per 16 steps
-    WordT vp = COL(col, 1), vn = COL(col, 2);
-    uint32_t acc = 0;
-    while (col > 0 && cur != 0) {
-        const WordT d0 = COL(col, 0);
-        const WordT vpi = col > 1 ? COL(col - 1, 1) : (WordT)0, vni = col > 1 ? COL(col - 1, 2) : (WordT)0;
+    // instructions: WordT-wide bit tests (only band bits are read) and the column it leaves behind handed to the next step
+    // instead of re-read (scratch column c + 1 holds x column c)
+    WordT vp = sink.at(n, 1), vn = sink.at(n, 2);
+    while (w.ci >= 0 && w.cur != 0) {
+        const int row = w.row, cur = w.cur;
+        const WordT d0 = sink.at(w.ci + 1, 0);
+        const WordT vpi = w.ci > 0 ? sink.at(w.ci, 1) : (WordT)0, vni = w.ci > 0 ? sink.at(w.ci, 2) : (WordT)0;
         const WordT hn = vpi & d0, hp = vni | ~(vpi | d0);
         const int diag = cur - (int)((~(d0 >> row)) & 1u);
         const bool can_up = row != 0, can_left = row == 0 || row != band - 1;
         int left = cur, up = cur;
         if (can_left) left = cur - (int)((hp >> row) & 1u) + (int)((hn >> row) & 1u);
         if (can_up) up = cur - (int)((vp >> (row - 1)) & 1u) + (int)((vn >> (row - 1)) & 1u);
-        int best = diag; dir = 0;
-        if (can_up && up < best) { best = up; dir = 2; }
-        if (can_left && left < best) { best = left; dir = 3; }
-        if (dir == 0) { if (diag != cur) dir = 1; col--; start--; vp = vpi; vn = vni; }
-        else if (dir == 2) { row--; start--; }
-        else { col--; row++; vp = vpi; vn = vni; }
-        acc |= (uint32_t)dir << ((plen & 15) << 1);
-        if ((plen & 15) == 15) { s_ops[plen >> 4][lane64] = acc; acc = 0; }
-        plen++;
-        cur = best;
+        // ties: diagonal, then up, then left; a neighbour that is cheaper is so by exactly one
+        int best = diag;
+        uint32_t code = diag != cur ? 1u : 0u;
+        if (can_up && up < best) { best = up; code = 2u; }
+        if (can_left && left < best) code = 3u;
+        if (code != 2u) { vp = vpi; vn = vni; }
+        w.put(code);
     }
-    if (plen & 15) s_ops[plen >> 4][lane64] = acc;
-    }
-    path_finish(store, t, P, s_ops, lane64, col, dir, plen, start, end, err);
-#undef COL
+    w.flush();
+    path_finish(store, t, P, w, r.end_site, r.err);
 }
 
 template <class WordT>
 __global__ __launch_bounds__(64) void k_path_dp(const uint32_t *__restrict__ store, const fsv_wtask *__restrict__ tasks,
-                                                const uint32_t *__restrict__ dp_list, uint32_t list_begin, uint32_t list_end,
-                                                fsv_wpath *__restrict__ paths, WordT *__restrict__ cols, uint32_t stride,
-                                                const uint32_t *__restrict__ n_dev)
+                                                const uint32_t *__restrict__ dp_list, const uint32_t *__restrict__ n_dev,
+                                                fsv_wpath *__restrict__ paths, WordT *__restrict__ cols)
 {
-    __shared__ uint32_t s_ops[28][64];     // per lane: the path being built, 2 bits per op, stored end-to-start (448 ops)
+    __shared__ uint32_t s_ops[PathWalk::WORDS][64];
     const int lane64 = threadIdx.x;
-    if (n_dev) list_end = list_begin + *n_dev;   // the list's length as the kernel before left it: no host round trip
-    const uint32_t slot = blockIdx.x * 64 + threadIdx.x;   // this lane's slice of the scratch, reused for every task it takes
+    const uint32_t n_list = *n_dev;     // the list's length as the kernel before left it: no host round trip
     // persistent blocks: the grid is sized to what the device holds at once and every block strides through the list, so the
-    // scratch is a few hundred MB whatever the number of windows, and the whole list is one launch
-    for (uint32_t li = list_begin + slot; li < list_end; li += gridDim.x * 64) {
+    // scratch is a few hundred MB whatever the number of windows, and the whole list is one launch; a block's slice of the scratch is
+    // reused for every task it takes
+    for (uint32_t li = blockIdx.x * 64 + threadIdx.x; li < n_list; li += gridDim.x * 64) {
         const uint32_t tid = dp_list[li];
         const fsv_wtask t = tasks[tid];
-        path_general<WordT>(store, t, paths + tid, s_ops, lane64, cols + (size_t)blockIdx.x * (FSV_WINDOW + 2) * 3 * 64);
+        path_general<WordT, 64>(store, t, paths + tid, s_ops, lane64, cols + (size_t)blockIdx.x * (FSV_WINDOW + 2) * 3 * 64);
     }
-    (void)stride;
 }
 
 // ------------------------------------------------------------------------------------------------ fix_boundary
@@ -1264,7 +1273,7 @@ __global__ __launch_bounds__(64) void k_path_dp(const uint32_t *__restrict__ sto
 // starts in the first column of its padded window, or ends in its last one, may have been cut off by the band -- the window is aligned
 // once more with the band shifted by k towards that side (from the old region's first base / so that the x interval ends at the old
 // alignment's last base), without a hint, and the new alignment stands when it has fewer errors.  t / r / the record at P: the window
-// as K6 left it; they are replaced when the new alignment stands.  One lane, column scratch `cols` with lane stride 1 (LDS).
+// as K6 left it; they are replaced when the new alignment stands.  One lane, its column scratch `cols` in LDS.
 // oracle/asm.c:window_path is the same, statement for statement.
 __device__ __forceinline__ void fix_boundary_dev(const uint32_t *__restrict__ store, fsv_wtask &t, fsv_wres &r, fsv_wpath *__restrict__ P, uint32_t (*s_ops)[64],
                                                  uint64_t *cols, int k_cap)
@@ -1282,7 +1291,7 @@ __device__ __forceinline__ void fix_boundary_dev(const uint32_t *__restrict__ st
     if (r2.y_beg == r.y_beg) return;
     bpm_run(store, t2, r2, BpmNoSink());
     if (r2.err < 0 || r2.err >= r.err) return;
-    path_general<uint64_t>(store, t2, P, s_ops, 0, cols, 1u);
+    path_general<uint64_t, 1>(store, t2, P, s_ops, 0, cols);
     r2.extra_begin = (int16_t)(r2.extra_begin | 0x4000);
     t = t2; r = r2;
 }
@@ -1292,7 +1301,7 @@ __global__ __launch_bounds__(64) void k_fix_boundary(const uint32_t *__restrict_
                                                      fsv_wtask *__restrict__ tasks, fsv_wres *__restrict__ res, fsv_wpath *__restrict__ paths, int k_cap,
                                                      uint32_t *__restrict__ n_fixed)
 {
-    __shared__ uint32_t s_ops[28][64];
+    __shared__ uint32_t s_ops[PathWalk::WORDS][64];
     __shared__ uint64_t s_cols[(FSV_WINDOW + 2) * 3];
     if (threadIdx.x != 0) return;
     const uint32_t n_list = *n_list_dev;
@@ -1317,18 +1326,15 @@ __global__ __launch_bounds__(64) void k_fix_boundary(const uint32_t *__restrict_
 template <bool DEFER = false>
 __global__ __launch_bounds__(64) void k_left_rescue(const uint32_t *__restrict__ store, fsv_ovl *__restrict__ ovl, const uint32_t *__restrict__ list,
                                                     const uint32_t *__restrict__ n_list_dev, fsv_wtask *__restrict__ tasks, fsv_wres *__restrict__ res,
-                                                    fsv_wpath *__restrict__ paths, uint64_t *__restrict__ cols, uint4 *__restrict__ ovl_c, int k_cap, int accept_err_pm)
+                                                    fsv_wpath *__restrict__ paths, uint4 *__restrict__ ovl_c, int k_cap, int accept_err_pm)
 {
     // One lane of a block works, with the column scratch of its window in LDS: the walk back is a chain of dependent reads of that
     // scratch, column after column -- 1.3 ms for a single window from HBM, whatever the number of overlaps listed (a few thousand in the
-    // first round, a dozen later); 40 us from LDS.  (cols: unused.)
-    __shared__ uint32_t s_ops[28][64];
+    // first round, a dozen later); 40 us from LDS.
+    __shared__ uint32_t s_ops[PathWalk::WORDS][64];
     __shared__ uint64_t s_cols[(FSV_WINDOW + 2) * 3];
     if (threadIdx.x != 0) return;
-    const int lane64 = 0;
     const uint32_t n_list = *n_list_dev;
-    uint64_t *slice = s_cols;
-    (void)cols;
     for (uint32_t li = blockIdx.x; li < n_list; li += gridDim.x) {
         const uint32_t p = list[li];
         fsv_ovl o = ovl[p];
@@ -1337,20 +1343,18 @@ __global__ __launch_bounds__(64) void k_left_rescue(const uint32_t *__restrict__
         fsv_wpath *PP = paths + o.first_win;
         long long post = 0;          // sum over the windows whose path was computed here of (distance after generate_cigar - K5's distance)
         auto window_path = [&](fsv_wtask &t, fsv_wres &r, fsv_wpath *P) {
-            if (!path_gapfree(store, t, r, P, true)) path_general<uint64_t>(store, t, P, s_ops, lane64, slice, 1u);
-            fix_boundary_dev(store, t, r, P, s_ops, slice, k_cap);
+            if (!path_gapfree(store, t, r, P, true)) path_general<uint64_t, 1>(store, t, P, s_ops, 0, s_cols);
+            fix_boundary_dev(store, t, r, P, s_ops, s_cols, k_cap);
         };
         for (int j = 1; j < o.n_win; j++) {
             if (R[j].err < 0 || R[j - 1].err >= 0) continue;
             fsv_wtask tj = T[j];
             fsv_wres rj = R[j];
-            const int raw_err_j = rj.err;
             window_path(tj, rj, PP + j);
             if (tj.y_start != T[j].y_start) { T[j] = tj; R[j] = rj; }      // (fix_boundary moved the window)
             const uint4 hj = *reinterpret_cast<const uint4 *>(PP + j);
             if ((hj.w & 0xffu) != 1u) { R[j].err = -1; continue; }       // (a path longer than a record holds: the window is unused, as in window_path)
             post += (int)(int16_t)(hj.z >> 16) - rj.err;
-            (void)raw_err_j;
             int total_y_end = (int)hj.x - 1;
             for (int k2 = j - 1; k2 >= 0 && R[k2].err < 0; k2--) {
                 fsv_wtask u = T[k2];
@@ -1518,6 +1522,28 @@ __global__ __launch_bounds__(64) void k_charge_accept(ChargeArgs A)
     }
 }
 
+// ---- the walk kernels' task: a listed window, its record, and what K5 found for it -- the end site, the distance, and the band row
+// the alignment ends on
+struct PathTask { fsv_wtask t; fsv_wpath *P; int n, k, band, end, err, row0; };
+__device__ __forceinline__ PathTask path_task_of(const fsv_wtask *__restrict__ tasks, const fsv_wres *__restrict__ res, fsv_wpath *__restrict__ paths, const uint32_t tid)
+{
+    PathTask T;
+    T.t = tasks[tid];
+    const fsv_wres r0 = res[tid];
+    T.P = paths + tid;
+    T.n = T.t.x_len; T.k = T.t.k; T.band = 2 * T.k + 1;
+    T.end = r0.end_site; T.err = r0.err;
+    T.row0 = T.band - (T.n + 2 * T.k - T.end);
+    return T;
+}
+// a walk kernel's forward pass is K5's DP once more: it reproduces (end site, distance), or the window is left without a path (cannot happen)
+__device__ __forceinline__ bool path_same_dp(const PathTask &T, const fsv_wres &r)
+{
+    if (r.err == T.err && r.end_site == T.end) return true;
+    T.P->state = 0;
+    return false;
+}
+
 // ---- K6 for first-pass windows: k <= 15, distance 4 .. FSV_SB_MAXERR (3 and below: k_path_fr further down) ----------------
 // What the walk back (Levenshtein_distance.h:757-888) asks of a DP cell is which way it leaves it -- 0 diagonal over a match,
 // 1 diagonal over a mismatch, 2 up, 3 left; ties: diagonal, then up, then left -- and that is known while the column is
@@ -1547,79 +1573,64 @@ struct SubbandSink {
 
 __device__ __forceinline__ uint32_t quad_elem(const uint4 &q, int e) { return e == 0 ? q.x : e == 1 ? q.y : e == 2 ? q.z : q.w; }
 
-// STAMP: diagnostic build only (FSV_K6_STAMPS=1): shader-clock cycles of the three phases summed per wave into `stamps`
+// STAMP: diagnostic build only (FSV_K6_STAMPS=1): shader-clock cycles of the three phases summed over the waves' trips into `stamps`
 template <bool STAMP>
 __global__ __launch_bounds__(64) void k_path_sb(const uint32_t *__restrict__ store, const fsv_wtask *__restrict__ tasks, const fsv_wres *__restrict__ res,
                                                 const uint32_t *__restrict__ dp_list, const uint32_t *__restrict__ n_dev,
                                                 fsv_wpath *__restrict__ paths, uint4 *__restrict__ cols, unsigned long long *__restrict__ stamps)
 {
-    unsigned long long t_fwd = 0, t_walk = 0, t_fin = 0, t0 = 0, t1 = 0, t2 = 0;
-    __shared__ uint32_t s_ops[28][64];     // per lane: the path being built, 2 bits per op, stored end-to-start (448 ops)
+    PhaseClock<STAMP> clk(true);
+    __shared__ uint32_t s_ops[PathWalk::WORDS][64];
     const int lane64 = threadIdx.x;
     const uint32_t n_list = *n_dev;
     uint4 *slot = cols + (size_t)blockIdx.x * FSV_SB_QUADS * 64 + lane64;   // persistent blocks: the slice is reused for every task
     for (uint32_t li = blockIdx.x * 64 + threadIdx.x; li < n_list; li += gridDim.x * 64) {
-        const uint32_t tid = dp_list[li];
-        const fsv_wtask t = tasks[tid];
-        const fsv_wres r0 = res[tid];
-        fsv_wpath *P = paths + tid;
-        const int n = t.x_len, k = t.k, band = 2 * k + 1;
-        const int end = r0.end_site, err = r0.err;
+        const PathTask T = path_task_of(tasks, res, paths, dp_list[li]);
         constexpr int ME = FSV_SB_MAXERR, QSH = 2;
-        const int row0 = band - (n + 2 * k - end), lo = row0 - ME;
+        const int lo = T.row0 - ME;
         SubbandSink sink;
         sink.slot = slot; sink.sr = (uint32_t)max(lo, 0); sink.sl = (uint32_t)max(-lo, 0);
-        sink.lmask = band == 1 ? 1u : (1u << (band - 1)) - 1u;
+        sink.lmask = T.band == 1 ? 1u : (1u << (T.band - 1)) - 1u;
         sink.a0 = sink.a1 = sink.a2 = sink.a3 = 0;
         fsv_wres r;
-        if (STAMP) t0 = __builtin_amdgcn_s_memtime();
-        bpm_run32(store, t, r, sink);
-        if (STAMP) t1 = __builtin_amdgcn_s_memtime();
-        if (r.err != err || r.end_site != end) { P->state = 0; continue; }   // cannot happen: the same DP as K5
-        for (int i = 0; i < 28; i++) s_ops[i][lane64] = 0;
-        int cur = err, ci = n - 1, plen = 0, start = end, rel = ME, dir = 0;
-        uint32_t acc = 0;
+        clk.restart();
+        bpm_run32(store, T.t, r, sink);
+        clk.mark(stamps, lane64, 0);
+        if (!path_same_dp(T, r)) continue;
+        PathWalk w(s_ops, lane64);
+        w.clear(T.n, T.end, T.err, ME);      // the row: relative to the sub-band
         // The walk, a quad of columns per phase: every lane walks until it leaves its current quad (four column steps plus its
         // "up" steps), then all lanes move one quad down together.  Six quads rotate through registers and the one just left
         // is refilled with the quad six below, so a quad is requested five phases before it is walked and no lane ever waits
         // for a load another lane has just issued (with a per-lane "switch when I cross" every crossing waited out the full
         // memory latency of the neighbour's request: 1 500 cycles per step, FSV_K6_STAMPS).
-        int qi = ci >> QSH;
+        int qi = w.ci >> QSH;
         auto quad = [&](int q) { return q >= 0 ? slot[(size_t)q * 64] : make_uint4(0, 0, 0, 0); };
         uint4 qa = quad(qi), qb = quad(qi - 1), qc = quad(qi - 2), qd = quad(qi - 3), qe = quad(qi - 4), qf = quad(qi - 5);
         auto phase = [&](const uint4 &q4) {
-            while (cur != 0 && ci >= 0 && (ci >> QSH) == qi) {
-                // A match step keeps the band row (`rel`) and moves one column left, so a run of matches is a run of zero codes at ONE
-                // bit position of consecutive columns' words: the columns of this quad whose code at `rel` is not 0 are found with a few
+            while (w.cur != 0 && w.ci >= 0 && (w.ci >> QSH) == qi) {
+                // A match step keeps the band row and moves one column left, so a run of matches is a run of zero codes at ONE
+                // bit position of consecutive columns' words: the columns of this quad whose code at the row is not 0 are found with a few
                 // shifts, and the matches in front of the first of them are taken in one step (round 2 walked them one by one, ~40
                 // instructions each: half of K6's time by the cycle stamps, 375 steps for the 1-3 deviations of a HiFi window).
+                const int rel = w.row;
                 uint32_t nz;
                 nz = (((q4.x >> rel) | (q4.x >> (rel + 16))) & 1u) | ((((q4.y >> rel) | (q4.y >> (rel + 16))) & 1u) << 1) |
                      ((((q4.z >> rel) | (q4.z >> (rel + 16))) & 1u) << 2) | ((((q4.w >> rel) | (q4.w >> (rel + 16))) & 1u) << 3);
-                const int cl = ci & 3;
+                const int cl = w.ci & 3;
                 const uint32_t m = nz & ((2u << cl) - 1u);          // deviating columns at or below this one
                 const int steps = m ? cl - (31 - __clz((int)m)) : cl + 1;
                 if (steps) {
-                    const int np = plen + steps;
-                    if ((np >> 4) != (plen >> 4)) { s_ops[plen >> 4][lane64] = acc; acc = 0; }   // the word fills up with matches
-                    plen = np; start -= steps; ci -= steps; dir = 0;
+                    w.matches(steps);
                     if (!m) continue;                                   // the rest of the quad matched
                 }
-                const uint32_t w = quad_elem(q4, ci & 3);
-                const uint32_t code = ((w >> rel) & 1u) | (((w >> (16 + rel)) & 1u) << 1);
-                acc |= code << ((plen & 15) << 1);
-                if ((plen & 15) == 15) { s_ops[plen >> 4][lane64] = acc; acc = 0; }
-                plen++;
-                cur -= (int)(code != 0u);
-                start -= (int)(code != 3u);
-                rel += (int)(code == 3u) - (int)(code == 2u);
-                ci -= (int)(code != 2u);      // "up" stays in its column
-                dir = (int)code;
+                const uint32_t cw = quad_elem(q4, w.ci & 3);
+                w.put(((cw >> rel) & 1u) | (((cw >> (16 + rel)) & 1u) << 1));
             }
         };
         // (six quads in rotation since round 3: a quad is requested five phases before it is walked.  With three -- two phases, ~800
         // cycles of walking -- every phase still waited out most of a memory round trip: the stamps showed half of K6's time in the walk)
-        while (__any(cur != 0 && ci >= 0)) {
+        while (__any(w.cur != 0 && w.ci >= 0)) {
             phase(qa); qi--; qa = quad(qi - 5);
             phase(qb); qi--; qb = quad(qi - 5);
             phase(qc); qi--; qc = quad(qi - 5);
@@ -1627,12 +1638,11 @@ __global__ __launch_bounds__(64) void k_path_sb(const uint32_t *__restrict__ sto
             phase(qe); qi--; qe = quad(qi - 5);
             phase(qf); qi--; qf = quad(qi - 5);
         }
-        if (plen & 15) s_ops[plen >> 4][lane64] = acc;
-        if (STAMP) t2 = __builtin_amdgcn_s_memtime();
-        path_finish(store, t, P, s_ops, lane64, ci + 1, dir, plen, start, end, err);
-        if (STAMP) { const unsigned long long t3 = __builtin_amdgcn_s_memtime(); t_fwd += t1 - t0; t_walk += t2 - t1; t_fin += t3 - t2; }
+        w.flush();
+        clk.mark(stamps, lane64, 1);
+        path_finish(store, T.t, T.P, w, T.end, T.err);
+        clk.mark(stamps, lane64, 2);
     }
-    if (STAMP && lane64 == 0) { atomicAdd(&stamps[0], t_fwd); atomicAdd(&stamps[1], t_walk); atomicAdd(&stamps[2], t_fin); atomicAdd(&stamps[3], 1ull); }
 }
 
 // ---- K6 without the matrix: distance <= FSV_FR_MAXERR ------------------------------------------------------------------------
@@ -1653,12 +1663,7 @@ __global__ __launch_bounds__(64) void k_path_sb(const uint32_t *__restrict__ sto
 // first column in [cs, cs + 64) (none at or past n) whose x base differs from the y base at strand position ypos + column, as an offset from cs
 __device__ __forceinline__ int diag_mismatch16(uint32_t xb, uint32_t yb, uint32_t yvalid)
 {
-    uint32_t d = xb ^ yb;
-    d = (d | (d >> 1)) & 0x55555555u;
-    uint32_t inval = ~yvalid & 0xffffu;     // columns outside read y never match
-    inval = (inval | (inval << 8)) & 0x00ff00ffu; inval = (inval | (inval << 4)) & 0x0f0f0f0fu;
-    inval = (inval | (inval << 2)) & 0x33333333u; inval = (inval | (inval << 1)) & 0x55555555u;
-    d |= inval;
+    const uint32_t d = mismatch_fields16(xb, yb, yvalid);     // columns outside read y never match
     return d ? (__ffs((int)d) - 1) >> 1 : 16;
 }
 __device__ __forceinline__ int diag_probe64(const uint32_t *__restrict__ store, const fsv_wtask &t, int ypos, int cs, int n)
@@ -1673,26 +1678,22 @@ __device__ __forceinline__ int diag_probe64(const uint32_t *__restrict__ store, 
 }
 
 // E = the windows' distance (one list per distance: a wave's lanes then have the same number of table entries to fill)
-// STAMP: diagnostic build only (FSV_K6_STAMPS=1): shader-clock cycles of table / walk / finish summed per wave into `stamps`
+// STAMP: diagnostic build only (FSV_K6_STAMPS=1): shader-clock cycles of table / walk / finish summed over the waves' trips into `stamps`
 template <int E, bool STAMP = false>
 __global__ __launch_bounds__(64) void k_path_fr(const uint32_t *__restrict__ store, const fsv_wtask *__restrict__ tasks, const fsv_wres *__restrict__ res,
                                                 const uint32_t *__restrict__ dp_list, const uint32_t *__restrict__ n_dev, fsv_wpath *__restrict__ paths,
                                                 unsigned long long *__restrict__ stamps = nullptr)
 {
-    unsigned long long t_tab = 0, t_walk = 0, t_fin = 0, t0 = 0, t1 = 0, t2 = 0;
-    __shared__ uint32_t s_ops[28][64];     // per lane: the path, 2 bits per op, end-to-start (path_finish works on it)
+    PhaseClock<STAMP> clk(true);
+    __shared__ uint32_t s_ops[PathWalk::WORDS][64];
     constexpr int NJ = 2 * E + 1;
     const int lane64 = threadIdx.x;
     const uint32_t n_list = *n_dev;
     for (uint32_t li = blockIdx.x * 64 + threadIdx.x; li < n_list; li += gridDim.x * 64) {
-        if (STAMP) t0 = __builtin_amdgcn_s_memtime();
-        const uint32_t tid = dp_list[li];
-        const fsv_wtask t = tasks[tid];
-        const fsv_wres r0 = res[tid];
-        fsv_wpath *P = paths + tid;
-        const int n = t.x_len, k = t.k, band = 2 * k + 1;
-        const int end = r0.end_site;
-        const int row0 = band - (n + 2 * k - end), win0 = t.y_start - k;
+        clk.restart();
+        const PathTask T = path_task_of(tasks, res, paths, dp_list[li]);
+        const fsv_wtask &t = T.t;
+        const int n = T.n, band = T.band, row0 = T.row0, win0 = t.y_start - T.k;
         // Q[s][j + E] = F[s][row0 + j] + 1: the first column of the row that is NOT within s errors; -1 = no such row (outside the
         // band or the triangle): F = -2 is below every column the walk can ask about
         int Q[E][NJ];
@@ -1762,30 +1763,23 @@ __global__ __launch_bounds__(64) void k_path_fr(const uint32_t *__restrict__ sto
             }
             extend(Q[s], run);
         }
-        if (STAMP) t1 = __builtin_amdgcn_s_memtime();
-        for (int i = 0; i < 28; i++) s_ops[i][lane64] = 0;
-        int ci = n - 1, plen = 0, start = end, j = E, dir = 0;
+        clk.mark(stamps, lane64, 0);
+        PathWalk w(s_ops, lane64);
+        w.clear(n, T.end, E, E);        // the row: an index into a level of Q
 #pragma unroll
         for (int s = E - 1; s >= 0; s--) {      // the walk has s + 1 errors left: its neighbours are judged on level s
             int fa = -1, fb = -2, fc = -1;      // first columns (from the end) where the mismatch / up / left move is open
 #pragma unroll
-            for (int i = 0; i < NJ; i++) { fa = i == j ? Q[s][i] : fa; fb = i == j - 1 ? Q[s][i] - 1 : fb; fc = i == j + 1 ? Q[s][i] : fc; }
-            const int cstop = min(ci, max(fa, max(fb, fc)));    // fa >= 0: column 0 is a mismatch at the latest
-            const int steps = ci - cstop;
-            plen += steps; start -= steps; ci = cstop;
-            const uint32_t code = ci <= fa ? 1u : ci <= fb ? 2u : 3u;
-            s_ops[plen >> 4][lane64] |= code << ((plen & 15) << 1);
-            plen++;
-            start -= (int)(code != 3u);
-            j += (int)(code == 3u) - (int)(code == 2u);
-            ci -= (int)(code != 2u);
-            dir = (int)code;
+            for (int i = 0; i < NJ; i++) { fa = i == w.row ? Q[s][i] : fa; fb = i == w.row - 1 ? Q[s][i] - 1 : fb; fc = i == w.row + 1 ? Q[s][i] : fc; }
+            const int cstop = min(w.ci, max(fa, max(fb, fc)));    // fa >= 0: column 0 is a mismatch at the latest
+            w.matches(w.ci - cstop);
+            w.put(w.ci <= fa ? 1u : w.ci <= fb ? 2u : 3u);
         }
-        if (STAMP) t2 = __builtin_amdgcn_s_memtime();
-        path_finish(store, t, P, s_ops, lane64, ci + 1, dir, plen, start, end, E);
-        if (STAMP) { const unsigned long long t3 = __builtin_amdgcn_s_memtime(); t_tab += t1 - t0; t_walk += t2 - t1; t_fin += t3 - t2; }
+        w.flush();
+        clk.mark(stamps, lane64, 1);
+        path_finish(store, t, T.P, w, T.end, E);
+        clk.mark(stamps, lane64, 2);
     }
-    if (STAMP && lane64 == 0) { atomicAdd(&stamps[0], t_tab); atomicAdd(&stamps[1], t_walk); atomicAdd(&stamps[2], t_fin); atomicAdd(&stamps[3], 1ull); }
 }
 
 // ---- K6 for wide bands (k > 31, up to 95): the ONT profile ---------------------------------------------------------------------
@@ -1815,24 +1809,18 @@ __global__ __launch_bounds__(64) void k_path_wide(const uint32_t *__restrict__ s
                                                   const uint32_t *__restrict__ dp_list, const uint32_t *__restrict__ n_dev,
                                                   fsv_wpath *__restrict__ paths, uint32_t *__restrict__ cols, int k_cap)
 {
-    __shared__ uint32_t s_ops[28][64];
+    __shared__ uint32_t s_ops[PathWalk::WORDS][64];
     const int lane64 = threadIdx.x;
     const uint32_t n_list = *n_dev;
     uint32_t *slot = cols + (size_t)blockIdx.x * FSV_WINDOW * 2 * FSV_WL * 64;
     for (uint32_t li = blockIdx.x * 64 + threadIdx.x; li < n_list; li += gridDim.x * 64) {
-        const uint32_t tid = dp_list[li];
-        const fsv_wtask t = tasks[tid];
-        const fsv_wres r0 = res[tid];
-        fsv_wpath *P = paths + tid;
-        const int n = t.x_len, k = t.k, band = 2 * k + 1;
-        const int end = r0.end_site, err = r0.err;
-        WideCodeSink sink{slot, (uint32_t)lane64, band};
+        const PathTask T = path_task_of(tasks, res, paths, dp_list[li]);
+        WideCodeSink sink{slot, (uint32_t)lane64, T.band};
         fsv_wres r;
-        bpm_run_wide(store, t, r, sink, k_cap);
-        if (r.err != err || r.end_site != end) { P->state = 0; continue; }   // cannot happen: the same DP as K5
-        for (int i = 0; i < 28; i++) s_ops[i][lane64] = 0;
-        int cur = err, ci = n - 1, plen = 0, start = end, row = band - (n + 2 * k - end), dir = 0;
-        uint32_t acc = 0;
+        bpm_run_wide(store, T.t, r, sink, k_cap);
+        if (!path_same_dp(T, r)) continue;
+        PathWalk w(s_ops, lane64);
+        w.clear(T.n, T.end, T.err, T.row0);
         bool fits = true;
         // The walk, column by column for the whole wavefront: the two code words a lane needs at a column (those of its row's limb)
         // are requested FOUR columns ahead, at a point every lane passes together, and held in four register pairs that an unrolled
@@ -1843,40 +1831,32 @@ __global__ __launch_bounds__(64) void k_path_wide(const uint32_t *__restrict__ s
             if (c >= 0) { const uint32_t *p = slot + (size_t)c * 2 * FSV_WL * 64 + lane64; lo = p[(size_t)lm * 64]; hi = p[(size_t)(FSV_WL + lm) * 64]; }
         };
         auto column = [&](int c, uint32_t &lo, uint32_t &hi, int &lmx) {
-            if (c >= 0 && ci == c && cur != 0 && fits) {
+            if (c >= 0 && w.ci == c && w.cur != 0 && fits) {
                 while (true) {
-                    const int lm = row >> 5, bt = row & 31;
+                    const int lm = w.row >> 5, bt = w.row & 31;
                     if (lm != lmx) { ld(c, lm, lo, hi); lmx = lm; }
-                    const uint32_t code = ((lo >> bt) & 1u) | (((hi >> bt) & 1u) << 1);
-                    if (plen >= 28 * 16 - 1) { fits = false; break; }        // the path buffer holds 448 ops; such a path is dropped below anyway
-                    acc |= code << ((plen & 15) << 1);
-                    if ((plen & 15) == 15) { s_ops[plen >> 4][lane64] = acc; acc = 0; }
-                    plen++;
-                    cur -= (int)(code != 0u);
-                    start -= (int)(code != 3u);
-                    row += (int)(code == 3u) - (int)(code == 2u);
-                    dir = (int)code;
-                    if (code != 2u) { ci--; break; }     // "up" stays in its column
-                    if (cur == 0) break;
+                    if (w.plen >= PathWalk::CAP - 1) { fits = false; break; }        // the path buffer is full; such a path is dropped below anyway
+                    w.put(((lo >> bt) & 1u) | (((hi >> bt) & 1u) << 1));
+                    if (w.dir != 2 || w.cur == 0) break;     // "up" stays in its column
                 }
             }
-            lmx = row >> 5;
+            lmx = w.row >> 5;
             ld(c - 4, lmx, lo, hi);          // (every lane, walking or not: the request is issued where the whole wave passes)
         };
         const int c0 = FSV_WINDOW - 1;       // every window has at most FSV_WINDOW columns; a shorter one idles until the loop reaches its last column
         uint32_t lo0 = 0, hi0 = 0, lo1 = 0, hi1 = 0, lo2 = 0, hi2 = 0, lo3 = 0, hi3 = 0;
-        int lm0 = row >> 5, lm1 = lm0, lm2 = lm0, lm3 = lm0;
+        int lm0 = w.row >> 5, lm1 = lm0, lm2 = lm0, lm3 = lm0;
         ld(c0, lm0, lo0, hi0); ld(c0 - 1, lm1, lo1, hi1); ld(c0 - 2, lm2, lo2, hi2); ld(c0 - 3, lm3, lo3, hi3);
         for (int c = c0; c >= 0; c -= 4) {
-            if (!__any(cur != 0 && ci >= 0 && fits)) break;
+            if (!__any(w.cur != 0 && w.ci >= 0 && fits)) break;
             column(c, lo0, hi0, lm0);
             column(c - 1, lo1, hi1, lm1);
             column(c - 2, lo2, hi2, lm2);
             column(c - 3, lo3, hi3, lm3);
         }
-        if (plen & 15) s_ops[plen >> 4][lane64] = acc;
-        if (!fits) { P->state = 0; continue; }
-        path_finish(store, t, P, s_ops, lane64, ci + 1, dir, plen, start, end, err);
+        w.flush();
+        if (!fits) { T.P->state = 0; continue; }
+        path_finish(store, T.t, T.P, w, T.end, T.err);
     }
 }
 

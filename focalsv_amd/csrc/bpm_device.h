@@ -25,15 +25,6 @@ __device__ __forceinline__ void bpm_eq_set(BpmState &s, uint32_t c, uint64_t bit
     s.eq3 |= (c == 3u) ? bit : 0ull;
 }
 
-// y base at padded-window column j (column 0 sits k bases before the predicted start);
-// 4 = outside the read ('N' in the reference's fill_subregion).
-__device__ __forceinline__ uint32_t bpm_ywin_base(const uint32_t *__restrict__ store, const fsv_wtask &t, int win0, int j)
-{
-    int p = win0 + j;
-    if (p < 0 || p >= t.y_len) return 4u;
-    return fsv_base_at(store, t.y_word, t.y_len, t.y_rev, p);
-}
-
 // determine_overlap_region (Correct.cpp:203-250): false = window geometrically impossible
 __device__ __forceinline__ bool bpm_window_geometry(const fsv_wtask &t, fsv_wres &r, int k_cap = FSV_K_MAX)
 {
@@ -48,14 +39,14 @@ __device__ __forceinline__ bool bpm_window_geometry(const fsv_wtask &t, fsv_wres
     return true;
 }
 
-// last-column scan, Levenshtein_distance.h:418-457
-__device__ __forceinline__ int bpm_pick_end(const BpmState &s, int err, int n, int k, int &best_out)
+// last-column scan, Levenshtein_distance.h:418-457, over a bit reader: delta(i) = bit i of VP minus bit i of VN
+template <class Delta>
+__device__ __forceinline__ int bpm_end_scan(Delta delta, int err, int n, int k, int &best_out)
 {
     int best = -1, site = -1, e = err, ungapped = -1;
     if (e <= k) { best = e; site = n - 1; }
     for (int i = 0; i < 2 * k;) {
-        e += (int)((s.vp >> i) & 1ull);
-        e -= (int)((s.vn >> i) & 1ull);
+        e += delta(i);
         ++i;
         if (e <= k && (best < 0 || e <= best)) { best = e; site = n - 1 + i; }
         if (i == k) ungapped = e;
@@ -63,6 +54,16 @@ __device__ __forceinline__ int bpm_pick_end(const BpmState &s, int err, int n, i
     if (best >= 0 && k > 0 && ungapped == best) site = n - 1 + k;
     best_out = best;
     return best < 0 ? -1 : site;
+}
+// VP / VN in one 64-bit word (bpm_run, bpm_ext_run; bpm_run32 widens its words: scanned as 32-bit words they cost k5_bpm_kernel a
+// VGPR and with it a wave per SIMD) or in 32-bit limbs (bpm_run_wide)
+__device__ __forceinline__ int bpm_pick_end(uint64_t vp, uint64_t vn, int err, int n, int k, int &best_out)
+{
+    return bpm_end_scan([=](int i) { return (int)((vp >> i) & 1ull) - (int)((vn >> i) & 1ull); }, err, n, k, best_out);
+}
+__device__ __forceinline__ int bpm_pick_end(const uint32_t *vp, const uint32_t *vn, int err, int n, int k, int &best_out)
+{
+    return bpm_end_scan([=](int i) { return (int)((vp[i >> 5] >> (i & 31)) & 1u) - (int)((vn[i >> 5] >> (i & 31)) & 1u); }, err, n, k, best_out);
 }
 
 // ---- 16-base stream fetch -----------------------------------------------------------------------------------
@@ -179,6 +180,19 @@ __device__ __forceinline__ uint32_t compress_even16(uint32_t d)
     d = (d | (d >> 1)) & 0x33333333u; d = (d | (d >> 2)) & 0x0f0f0f0fu; d = (d | (d >> 4)) & 0x00ff00ffu; d = (d | (d >> 8)) & 0xffffu;
     return d;
 }
+// the inverse: bit j of a 16-bit mask -> bit 2j
+__device__ __forceinline__ uint32_t spread_even16(uint32_t m)
+{
+    m = (m | (m << 8)) & 0x00ff00ffu; m = (m | (m << 4)) & 0x0f0f0f0fu; m = (m | (m << 2)) & 0x33333333u; m = (m | (m << 1)) & 0x55555555u;
+    return m;
+}
+// 16 columns of a gap-free placement as 2-bit fields: 1 where the x base differs from the y base or y lies outside its read ('N' never
+// matches), 0 over a match -- the op codes "mismatch" and "match"
+__device__ __forceinline__ uint32_t mismatch_fields16(uint32_t xb, uint32_t yb, uint32_t yvalid)
+{
+    const uint32_t d = xb ^ yb;
+    return ((d | (d >> 1)) & 0x55555555u) | spread_even16(~yvalid & 0xffffu);
+}
 
 // One column of the recurrence (Levenshtein_distance.h:330-366); false when the column's diagonal cell is a mismatch.
 __device__ __forceinline__ bool bpm_column(uint64_t eq, uint64_t &vp, uint64_t &vn, uint64_t &d0_out)
@@ -266,7 +280,7 @@ __device__ __forceinline__ void bpm_run(const uint32_t *__restrict__ store, cons
         }
     }
     int best;
-    r.end_site = bpm_pick_end(s, err, n, k, best);
+    r.end_site = bpm_pick_end(s.vp, s.vn, err, n, k, best);
     r.err = best;
 }
 
@@ -356,9 +370,8 @@ __device__ __forceinline__ void bpm_run32(const uint32_t *__restrict__ store, co
         for (int i = 0; i < 5; i++) { X[i] = XN[i]; Y[i] = YN[i]; }
     }
     sink.flush(n);
-    BpmState s; s.eq0 = s.eq1 = s.eq2 = s.eq3 = 0; s.vp = vp; s.vn = vn;
     int best;
-    r.end_site = bpm_pick_end(s, err, n, k, best);
+    r.end_site = bpm_pick_end((uint64_t)vp, (uint64_t)vn, err, n, k, best);
     r.err = best;
 }
 
@@ -373,23 +386,6 @@ __device__ __forceinline__ void bpm_run32(const uint32_t *__restrict__ store, co
 struct WideNoSink {
     __device__ __forceinline__ void operator()(int, const uint32_t *, const uint32_t *, const uint32_t *) {}
 };
-
-// the end-site scan of bpm_pick_end on limbs
-__device__ __forceinline__ int bpm_pick_end_wide(const uint32_t *vp, const uint32_t *vn, int err, int n, int k, int &best_out)
-{
-    int best = -1, site = -1, e = err, ungapped = -1;
-    if (e <= k) { best = e; site = n - 1; }
-    for (int i = 0; i < 2 * k;) {
-        e += (int)((vp[i >> 5] >> (i & 31)) & 1u);
-        e -= (int)((vn[i >> 5] >> (i & 31)) & 1u);
-        ++i;
-        if (e <= k && (best < 0 || e <= best)) { best = e; site = n - 1 + i; }
-        if (i == k) ungapped = e;
-    }
-    if (best >= 0 && k > 0 && ungapped == best) site = n - 1 + k;
-    best_out = best;
-    return best < 0 ? -1 : site;
-}
 
 // Sink sees every column: (column, D0, HP of the column, VP after it), six limbs each.
 template <class Sink>
@@ -477,7 +473,7 @@ __device__ __forceinline__ void bpm_run_wide(const uint32_t *__restrict__ store,
         xb = xn; yb = yn;
     }
     int best;
-    r.end_site = bpm_pick_end_wide(vp, vn, err, n, k, best);
+    r.end_site = bpm_pick_end(vp, vn, err, n, k, best);
     r.err = best;
 }
 
@@ -487,8 +483,9 @@ __device__ __forceinline__ void bpm_run_wide(const uint32_t *__restrict__ store,
 // within k (oracle/bpm.c:orc_bpm_extension, statement for statement).  dir 1 aligns both strings reversed -- x from its last base down,
 // the padded y window from its last column down -- which is what the reference does for the extension from the right; only base equality
 // enters, so no strand is taken.  One lane per task, the reference's column-by-column slide for every k: the end-site scan after each
-// column (2k steps) is what the lane spends its time on, not the slide, and bases come through one cached 16-base word per operand.
-struct ExtBaseCache {
+// column (2k steps) is what the lane spends its time on, not the slide, and bases come through one cached 16-base word per operand
+// (BaseCache; the gap shift of K6's path_finish reads its bases the same way).
+struct BaseCache {
     uint32_t w = 0; int idx = -0x7fffffff;
     // base at forward position q of the read at word_off (0 <= q < its length)
     __device__ __forceinline__ uint32_t get(const uint32_t *__restrict__ store, uint32_t word_off, int q)
@@ -496,6 +493,15 @@ struct ExtBaseCache {
         const int wi = q >> 4;
         if (wi != idx) { w = store[word_off + (uint32_t)wi]; idx = wi; }
         return (w >> ((q & 15) << 1)) & 3u;
+    }
+    // y base of a task's padded-window column c (column 0 sits k bases before the predicted start), on the task's strand;
+    // 4 = outside the read ('N' in the reference's fill_subregion)
+    __device__ __forceinline__ uint32_t ycol(const uint32_t *__restrict__ store, const fsv_wtask &t, int c)
+    {
+        const int p = t.y_start - t.k + c;
+        if (p < 0 || p >= t.y_len) return 4u;
+        const uint32_t b = get(store, t.y_word, t.y_rev ? t.y_len - 1 - p : p);
+        return t.y_rev ? 3u - b : b;
     }
 };
 
@@ -505,15 +511,10 @@ __device__ __forceinline__ bool bpm_ext_run(const uint32_t *__restrict__ store, 
     out.t_end = -1; out.err = -1; out.p_end = -1; out.pad = 0;
     fsv_wres g;
     if (!bpm_window_geometry(t, g, k_cap)) return false;
-    const int n = t.x_len, k = t.k, wlen = n + 2 * k, win0 = t.y_start - k;
-    ExtBaseCache xc, yc;
-    // column c of the (possibly reversed) padded y window: 4 outside the read; base i of the (possibly reversed) x window
-    auto ycol = [&](int c) -> uint32_t {
-        const int p = win0 + (dir ? wlen - 1 - c : c);
-        if (p < 0 || p >= t.y_len) return 4u;
-        const uint32_t b = yc.get(store, t.y_word, t.y_rev ? t.y_len - 1 - p : p);
-        return t.y_rev ? 3u - b : b;
-    };
+    const int n = t.x_len, k = t.k, wlen = n + 2 * k;
+    BaseCache xc, yc;
+    // column c of the (possibly reversed) padded y window; base i of the (possibly reversed) x window
+    auto ycol = [&](int c) -> uint32_t { return yc.ycol(store, t, dir ? wlen - 1 - c : c); };
     auto xcol = [&](int i) -> uint32_t { return xc.get(store, t.x_word, t.x_start + (dir ? n - 1 - i : i)); };
     BpmState s;
     s.eq0 = s.eq1 = s.eq2 = s.eq3 = 0; s.vp = 0; s.vn = 0;
@@ -527,7 +528,7 @@ __device__ __forceinline__ bool bpm_ext_run(const uint32_t *__restrict__ store, 
             if (err - 2 * k > k) return true; // Levenshtein_distance.h:367-375: what was found so far stands
         }
         int best;
-        const int site = bpm_pick_end(s, err, i + 1, k, best);
+        const int site = bpm_pick_end(s.vp, s.vn, err, i + 1, k, best);
         if (best >= 0) { out.t_end = i; out.err = best; out.p_end = site; }
         if (i + 1 < n) {
             s.eq0 >>= 1; s.eq1 >>= 1; s.eq2 >>= 1; s.eq3 >>= 1;
