@@ -336,34 +336,25 @@ __global__ __launch_bounds__(64) void k_chain_aln(const int32_t *__restrict__ re
 __global__ __launch_bounds__(256) void k_thin_seeds(fsv_mz *__restrict__ mz, const uint32_t *__restrict__ mz_off, uint32_t *__restrict__ mz_cnt,
                                                     const uint16_t *__restrict__ thin)
 {
-    __shared__ uint32_t s_n, s_base;
+    __shared__ uint32_t s_w[4];
     const uint32_t r = blockIdx.x, m = thin[r];
     if (m <= 1) return;
     fsv_mz *a = mz + mz_off[r];
     const uint32_t n = min(mz_cnt[r], mz_off[r + 1] - mz_off[r]);
-    if (threadIdx.x == 0) s_n = 0;
-    __syncthreads();
+    uint32_t kept = 0;
     for (uint32_t base = 0; base < n; base += 256) {
         const uint32_t i = base + threadIdx.x;
-        fsv_mz v; v.hash = 0; v.pos = 0; v.rev = 0; v.span = 0; v.pad = 0;
+        fsv_mz v = mz_make(0, 0, 0, 0);
         bool keep = false;
         if (i < n) { v = a[i]; keep = (v.hash >> 11) % (uint64_t)m == 0; }
-        // rank inside the chunk: wave ballots, the waves' counts added up through LDS
-        const uint64_t bal = __ballot(keep);
-        const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-        __shared__ uint32_t s_w[4];
-        if (lane == 0) s_w[wv] = (uint32_t)__popcll(bal);
-        __syncthreads();          // also: every thread has read its a[i] before anyone overwrites a slot at or below it
-        uint32_t off = 0;
-        for (uint32_t k2 = 0; k2 < wv; k2++) off += s_w[k2];
-        if (threadIdx.x == 0) s_base = s_n;
-        __syncthreads();
-        if (keep) a[s_base + off + (uint32_t)__popcll(bal & ((1ull << lane) - 1))] = v;     // destination index <= i: only slots already read
-        __syncthreads();
-        if (threadIdx.x == 0) s_n = s_base + s_w[0] + s_w[1] + s_w[2] + s_w[3];
+        // rank inside the chunk.  The barrier inside is also: every thread has read its a[i] before anyone overwrites a slot at or below it
+        uint32_t all;
+        const uint32_t at = block_rank_256(keep, s_w, &all);
+        if (keep) a[kept + at] = v;     // destination index <= i: only slots already read
+        kept += all;
         __syncthreads();
     }
-    if (threadIdx.x == 0) mz_cnt[r] = s_n;
+    if (threadIdx.x == 0) mz_cnt[r] = kept;
 }
 
 // ------------------------------------------------------------------------------------------------ events

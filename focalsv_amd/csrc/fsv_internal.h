@@ -78,6 +78,71 @@ __device__ __forceinline__ long long wave_max_i64(long long v)
     return v;
 }
 
+// ---- block compaction: a thread's place among the 256 threads (four waves) of its block --------------------------------------------
+// The four wave totals go through s_w (four words of LDS); returns what the waves in front of this one hold and sets *total to the
+// block's sum.  One barrier inside, between the totals' store and their loads: whatever the block did before the call is done after
+// it.  The caller puts a barrier between two calls on the same s_w.  wave_total counts on lane 63 only.
+__device__ __forceinline__ uint32_t block_waves_before_256(uint32_t wave_total, uint32_t *s_w, uint32_t *total)
+{
+    const uint32_t wv = threadIdx.x >> 6;
+    if ((threadIdx.x & 63u) == 63u) s_w[wv] = wave_total;
+    __syncthreads();
+    uint32_t before = 0, all = 0;
+#pragma unroll
+    for (uint32_t v = 0; v < 4; v++) { const uint32_t c = s_w[v]; if (v < wv) before += c; all += c; }
+    *total = all;
+    return before;
+}
+// exclusive offset of this thread's count: a shuffle scan inside the wave in front of the wave totals
+__device__ __forceinline__ uint32_t block_offset_256(uint32_t cnt, uint32_t *s_w, uint32_t *total)
+{
+    const uint32_t lane = threadIdx.x & 63u;
+    uint32_t incl = cnt;
+    for (uint32_t off = 1; off < 64; off <<= 1) { const uint32_t o = __shfl_up(incl, off, 64); if (lane >= off) incl += o; }
+    return block_waves_before_256(incl, s_w, total) + incl - cnt;
+}
+// the one-bit case: the rank of a thread that keeps its element (for the others, the kept in front of them) from a ballot
+__device__ __forceinline__ uint32_t block_rank_256(bool keep, uint32_t *s_w, uint32_t *total)
+{
+    const uint64_t bal = __ballot(keep);
+    return block_waves_before_256((uint32_t)__popcll(bal), s_w, total) + (uint32_t)__popcll(bal & ((1ull << (threadIdx.x & 63u)) - 1ull));
+}
+
+// ---- an open-addressed set of 8-byte keys --------------------------------------------------------------------------------------------
+// The k-mer count table's keys (k_kmer_insert) and the sketch's filter sets (k_flt_build, probed by the sketch kernels): slots
+// [base, base + size) of a key array, size a power of two (or 0: no set), a free slot holds FSV_KMER_EMPTY, linear probing from bits of
+// the key itself (it is mix64 output).  Every probe is bounded by the set's size.
+#define FSV_KMER_EMPTY (~0ull)     // no key: hifiasm's dummy hash, which the sketch never emits
+struct KmerSet {
+    uint64_t base, size;
+    __device__ __forceinline__ uint64_t start(uint64_t h) const { return (h ^ (h >> 29)) & (size - 1); }
+    // is h a key?  The sets are at most half full, so a probe ends at a free slot after a step or two.
+    __device__ __forceinline__ bool has(const unsigned long long *__restrict__ keys, uint64_t h) const
+    {
+        uint64_t slot = start(h);
+        for (uint64_t probe = 0; probe < size; probe++) {
+            const unsigned long long cur = keys[base + slot];
+            if (cur == h) return true;
+            if (cur == FSV_KMER_EMPTY) return false;
+            slot = (slot + 1) & (size - 1);
+        }
+        return false;
+    }
+    // the slot that holds h, claimed now if nobody had: a 64-bit compare-and-swap against the empty value.  A slot only ever goes from
+    // empty to one key, so a stale read of "empty" is settled by the compare-and-swap.  Returns `size` when the set is full.
+    __device__ __forceinline__ uint64_t claim(unsigned long long *keys, uint64_t h) const
+    {
+        uint64_t slot = start(h);
+        for (uint64_t probe = 0; probe < size; probe++) {
+            unsigned long long cur = keys[base + slot];
+            if (cur == FSV_KMER_EMPTY) { cur = atomicCAS(&keys[base + slot], FSV_KMER_EMPTY, h); if (cur == FSV_KMER_EMPTY) cur = h; }
+            if (cur == h) return slot;
+            slot = (slot + 1) & (size - 1);
+        }
+        return size;
+    }
+};
+
 int fsv_live_contexts(int device);   // ctx.hip: contexts alive on a device
 
 // the C entry points never let a C++ exception through (a std::bad_alloc from a vector sized by caller data, a std::system_error

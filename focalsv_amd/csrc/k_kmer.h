@@ -1,7 +1,9 @@
 // k_kmer.h -- the per-set k-mer count table (hifiasm's ha_ft_gen / ha_analyze_count, htab.cpp:917-950, hist.cpp:15-96): the verdict on a
 // count histogram (host and device), and the kernels that count a read set's sketch entries in an open-addressed table, take the
-// histogram of the counts and gather the high-count keys.  Included by asm.hip; the first part compiles without HIP (a plain C++
-// program can include this header for fsv_kmer_peaks_hd alone).
+// histogram of the counts and gather the high-count keys.  The table's keys and the sketch's filter sets are the same open-addressed set,
+// KmerSet (fsv_internal.h, with FSV_KMER_EMPTY): k_kmer_insert and k_flt_build claim a key's slot through it, the sketch kernels
+// (k_sketch.h) look a hash up in it.  Included by asm.hip; the first part compiles without HIP (a plain C++ program can include this
+// header for fsv_kmer_peaks_hd alone).
 #pragma once
 #include <stdint.h>
 
@@ -63,9 +65,6 @@ FSV_KMER_HD inline int fsv_kmer_cutoff(int peak_hom)
 #if defined(__HIPCC__)
 #include "fsv_internal.h"
 
-#ifndef FSV_KMER_EMPTY
-#define FSV_KMER_EMPTY (~0ull)     // no key: hifiasm's dummy hash, which the sketch never emits (k_sketch.h has the same line)
-#endif
 #define FSV_KMER_MIN_SLOTS 1024u   // smallest table
 #define FSV_KMER_TILE 4096u        // slots a block of k_kmer_hist / k_kmer_filter walks
 #define FSV_KMER_E_FULL 1u         // error flags: a table had no free slot; a filter segment was too short
@@ -83,8 +82,8 @@ inline uint64_t kmer_table_slots(uint64_t entries)
 }
 
 // One block per read: every entry of the read's sketch (W.mz, in whatever order the sketch kernel left them) is counted in the table of
-// the read's set -- slots [tab_off[s], tab_off[s + 1]), linear probing from the hash's own bits (it is mix64 output).  A key is claimed
-// with a 64-bit compare-and-swap against the empty value, its count bumped with an atomic add and clamped when read, so thousands of
+// the read's set -- the KmerSet in slots [tab_off[s], tab_off[s + 1]).  A key is claimed (KmerSet::claim: linear probing from the hash's
+// own bits, a 64-bit compare-and-swap against the empty value), its count bumped with an atomic add and clamped when read, so thousands of
 // adds on one slot (a tandem array) stay exact.  Which slot a key lands in depends on the order of arrival; what is read out of
 // the table (histogram, filter set) does not.  The probe is bounded by the table's size: a full table raises FSV_KMER_E_FULL.
 __global__ __launch_bounds__(256) void k_kmer_insert(const fsv_mz *__restrict__ mz, const uint32_t *__restrict__ mz_off, const uint32_t *__restrict__ mz_cnt,
@@ -94,23 +93,15 @@ __global__ __launch_bounds__(256) void k_kmer_insert(const fsv_mz *__restrict__ 
     const uint32_t r = blockIdx.x;
     if (r >= n_reads) return;
     const uint32_t s = read_set[r];
-    const uint64_t base = tab_off[s], size = tab_off[s + 1] - base, mask = size - 1;
+    const KmerSet T{tab_off[s], tab_off[s + 1] - tab_off[s]};
     const uint32_t n = min(mz_cnt[r], mz_off[r + 1] - mz_off[r]);   // (the sketch counts past the slot when it truncates)
-    if (n && size == 0) { if (threadIdx.x == 0) atomicOr(err, FSV_KMER_E_FULL); return; }
+    if (n && T.size == 0) { if (threadIdx.x == 0) atomicOr(err, FSV_KMER_E_FULL); return; }
     const fsv_mz *a = mz + mz_off[r];
     for (uint32_t i = threadIdx.x; i < n; i += 256) {
         const unsigned long long h = a[i].hash;
         if (h == FSV_KMER_EMPTY) continue;
-        uint64_t slot = (h ^ (h >> 29)) & mask;
-        bool placed = false;
-        for (uint64_t probe = 0; probe < size; probe++) {
-            // a slot only ever goes from empty to one key: a stale read of "empty" is settled by the compare-and-swap
-            unsigned long long cur = keys[base + slot];
-            if (cur == FSV_KMER_EMPTY) { cur = atomicCAS(&keys[base + slot], FSV_KMER_EMPTY, h); if (cur == FSV_KMER_EMPTY) cur = h; }
-            if (cur == h) { atomicAdd(&cnt[base + slot], 1u); placed = true; break; }
-            slot = (slot + 1) & mask;
-        }
-        if (!placed) atomicOr(err, FSV_KMER_E_FULL);
+        const uint64_t slot = T.claim(keys, h);
+        if (slot < T.size) atomicAdd(&cnt[T.base + slot], 1u); else atomicOr(err, FSV_KMER_E_FULL);
     }
 }
 
@@ -165,7 +156,7 @@ inline uint64_t flt_set_slots(uint64_t keys)
 
 // One thread per key of the sets' filter lists (flt, segments [flt_off[s], flt_off[s + 1]), any order, duplicates allowed): the key is
 // claimed in its set's slots [set_off[s], set_off[s + 1]) of `keys` -- all FSV_KMER_EMPTY before the launch -- as k_kmer_insert claims
-// one: linear probing from the same bits, a 64-bit compare-and-swap against the empty value.  The probe is bounded by the set's size;
+// one (KmerSet::claim; where the key lands is of no interest here).  The probe is bounded by the set's size;
 // a set that ran full (the host sized it wrongly) or a list that holds the empty value raises FSV_KMER_E_FULL.  A set whose slot range
 // is empty while its list is not is one the host leaves unfiltered: its keys are passed over.
 __global__ __launch_bounds__(256) void k_flt_build(const unsigned long long *__restrict__ flt, const uint64_t *__restrict__ flt_off,
@@ -175,18 +166,10 @@ __global__ __launch_bounds__(256) void k_flt_build(const unsigned long long *__r
     if (i >= flt_off[n_sets]) return;
     uint32_t lo = 0, hi = n_sets;              // the set whose segment holds key i: the last s with flt_off[s] <= i
     while (hi - lo > 1) { const uint32_t mid = lo + (hi - lo) / 2; if (flt_off[mid] <= i) lo = mid; else hi = mid; }
-    const uint64_t base = set_off[lo], size = set_off[lo + 1] - base, mask = size - 1;
+    const KmerSet S{set_off[lo], set_off[lo + 1] - set_off[lo]};
     const unsigned long long h = flt[i];
-    if (size == 0) return;                    // a set the host gave no slots (left unfiltered) takes no keys
-    if (h == FSV_KMER_EMPTY) { atomicOr(err, FSV_KMER_E_FULL); return; }
-    uint64_t slot = (h ^ (h >> 29)) & mask;
-    for (uint64_t probe = 0; probe < size; probe++) {
-        unsigned long long cur = keys[base + slot];
-        if (cur == FSV_KMER_EMPTY) { cur = atomicCAS(&keys[base + slot], FSV_KMER_EMPTY, h); if (cur == FSV_KMER_EMPTY) cur = h; }
-        if (cur == h) return;
-        slot = (slot + 1) & mask;
-    }
-    atomicOr(err, FSV_KMER_E_FULL);
+    if (S.size == 0) return;                  // a set the host gave no slots (left unfiltered) takes no keys
+    if (h == FSV_KMER_EMPTY || S.claim(keys, h) == S.size) atomicOr(err, FSV_KMER_E_FULL);
 }
 
 } // namespace

@@ -1,6 +1,6 @@
 """Reads and read pairs beyond the two caps that fsv_asm_params.full_lists lifts: minimizer lists above FSV_UQ_MAX = 4 096 entries (the
 per-read index, k_uniq_long) and pairs with more anchors than the chaining tile holds (4 096 in the compact layout, 2 560 in the long
-one: k_chain_spill).  Everything is built from seeded random strings and classified through the oracle alone, which has neither cap;
+one: k_chain_spill), and reads at the edges of the two small classes of the index (SMALL_LISTS).  Everything is built from seeded random strings and classified through the oracle alone, which has neither cap;
 tests/test_long_list_cases.py asserts the floors on a machine without a GPU, tests/test_gpu_read_index.py and
 tests/test_gpu_long_chain.py compare the kernels with the oracle on the same reads.
 
@@ -91,6 +91,50 @@ def index_batches():
     ont = [g[:20000], _bases(rng, 40000), g[5000:6000], _bases(rng, 45000), read_with_list(4097, ONT), read_with_list(4096, ONT)]
     w1 = [_bases(rng, 5000), _bases(rng, 1000), _bases(rng, 4300)]
     return {"dense": (DENSE, dense), "ont": (ONT, ont), "w1": (W1, w1)}
+
+
+# ---- the two small size classes of the index at their edges (k_uniq<1024>: raw lists up to 1 024 entries; k_uniq_walk<4096> above)
+# raw list sizes: nothing, the first few, either side of the 256 threads of a block (one entry per thread, then two; the network padded
+# to the next power of two), of 512 and of the boundary between the two classes
+SMALL_LISTS = (0, 1, 2, 3, 255, 256, 257, 511, 512, 513, 1023, 1024, 1025)
+
+
+@lru_cache(maxsize=None)
+def read_with_raw_list(want, scheme=DENSE):
+    """a substring of the genome, 14 bases (k - 1: no k-mer at all) or more, whose raw list has exactly `want` entries; found as
+    read_with_list finds its reads"""
+    g = genome()
+    per = 3.0
+    for start in range(0, 400, 7):
+        n_bases = max(14, int(want * per))
+        for _ in range(200):
+            mz, _uq = lists(g[start:start + n_bases], scheme)
+            if len(mz) == want:
+                return g[start:start + n_bases]
+            n_bases = max(14, n_bases + max(1, int(abs(want - len(mz)) * per * 0.7)) * (1 if len(mz) < want else -1))
+    raise AssertionError("no read with a raw list of %d" % want)
+
+
+@lru_cache(maxsize=None)
+def small_tandem_reads():
+    """(a, b): random flanks around a tandem array.  a: four copies of a 200-base unit, a raw list of at most 1 024 entries; b: six
+    copies of a 500-base unit, a raw list of 1 025 to 4 096 entries in which a run of equal hashes lies across a multiple of 256 of
+    the hash-sorted list (a chunk boundary of the compaction whatever the list's length).  In both the array's hashes occur several
+    times, so the unique list is shorter than the raw one"""
+    rng = random.Random(SEED + 6)
+    for _ in range(200):
+        a = _bases(rng, 300) + _bases(rng, 200) * 4 + _bases(rng, 300)
+        b = _bases(rng, 1500) + _bases(rng, 500) * 6 + _bases(rng, 1500)
+        (ra, ua), (rb, ub) = lists(a, DENSE), lists(b, DENSE)
+        if len(ua) < len(ra) <= 1024 < len(rb) <= UQ_MAX and len(ub) < len(rb) and straddled(sorted(int(x) for x in rb["hash"]), 256):
+            return a, b
+    raise AssertionError("no pair of small tandem reads")
+
+
+@lru_cache(maxsize=None)
+def small_index_batch():
+    """the reads of SMALL_LISTS, then the two tandem reads (scheme DENSE)"""
+    return tuple(read_with_raw_list(n) for n in SMALL_LISTS) + small_tandem_reads()
 
 
 # ---- pairs by anchor count

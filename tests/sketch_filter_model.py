@@ -45,6 +45,12 @@ def _mix64_np(key):
         return key + (key << np.uint64(31))
 
 
+def start_slot(h, n_slots):
+    """where the probe of key h starts in a filter set of n_slots slots (a power of two): bits of the hash itself; from there the
+    probe steps one slot at a time and wraps behind the last one"""
+    return (h ^ (h >> 29)) & (n_slots - 1)
+
+
 def sketch_literal(seq, w, k, hpc, flt=()):
     """sketch.cpp:39-137 line by line -> list of (hash, pos, rev, span) in the order ha_sketch pushes them"""
     flt = flt if isinstance(flt, (set, frozenset)) else {int(x) for x in flt}

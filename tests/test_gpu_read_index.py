@@ -58,6 +58,24 @@ def test_full_lists_index_equals_the_oracle(ctx, batch, order):
         assert same(g[m:], by_pos), (batch, i, len(r), m, "by position")
 
 
+@pytest.mark.parametrize("order", ["as listed", "reversed"])
+def test_small_classes_at_their_edges_equal_the_oracle(ctx, order):
+    """raw lists of 0 .. 3, 255 .. 257, 511 .. 513 and 1 023 .. 1 025 entries and two tandem reads (L.small_index_batch): the boundary
+    between k_uniq<1024> and k_uniq_walk<4096>, the padding of the sort network, the chunks of the compaction"""
+    reads = list(L.small_index_batch())
+    reads = reads if order == "as listed" else reads[::-1]
+    got, warn = index(ctx, reads, L.DENSE, 1)
+    cut, warn_cut = index(ctx, reads, L.DENSE, 0)
+    assert not warn.any() and not warn_cut.any(), (warn, warn_cut)
+    for i, (r, g) in enumerate(zip(reads, got)):
+        by_hash, by_pos = wanted(L.DENSE, r)
+        m = len(by_hash)
+        assert len(g) == 2 * m, (i, len(r), len(g), m)
+        assert same(g[:m], by_hash), (i, len(r), m, "by hash")
+        assert same(g[m:], by_pos), (i, len(r), m, "by position")
+        assert cut[i].tobytes() == g.tobytes(), (i, len(r), "full_lists 0 and 1")
+
+
 @pytest.mark.parametrize("batch", ["dense", "ont"])
 def test_default_cuts_and_flags_the_long_lists_only(ctx, batch):
     scheme, reads = L.index_batches()[batch]

@@ -200,6 +200,42 @@ def test_filter_set_sizing(ctx, n_keys):
         assert _diff(got[0], want) is None and _diff(got[1], want) is None, (n_keys, variant)
 
 
+def test_probe_wraps_past_the_last_slot(ctx):
+    """eight keys, so a set of 16 slots: a real minimizer of the read and four made-up keys that all start at slot 15, three made-up
+    keys that start at slots 0, 1 and 2 -- whatever the order of arrival the claims run over the end of the set (slots 15, 0 .. 6), and
+    the lookup of an absent hash that starts at slots 15 .. 3 walks the wrapped run to a free slot"""
+    gp = (51, 51, 1)
+    seq = _read(gp)
+    sl = FM.slots(seq, 51, 1)
+    plain = FM.sketch(seq, 51, 51, 1, None, sl)
+    real = {int(h) for h in sl["hash"] if h != MAXH}
+    key = next(int(h) for h in plain["hash"] if FM.start_slot(int(h), 16) == 15)
+    rng = random.Random("probe wrap")
+
+    def made_up(slot):
+        while True:
+            x = rng.getrandbits(64)
+            if x != FM.MAX and x not in real and x not in keys and FM.start_slot(x, 16) == slot:
+                return x
+    keys = [key]
+    for slot in (15, 15, 15, 15, 0, 1, 2):
+        keys.append(made_up(slot))
+    assert len(set(keys)) == 8 and [FM.start_slot(x, 16) for x in keys] == [15] * 5 + [0, 1, 2]
+    assert not (set(keys[1:]) & real) and FM.MAX not in keys
+    unfiltered = real - {key}
+    assert any(FM.start_slot(h, 16) == 15 for h in unfiltered) and any(FM.start_slot(h, 16) == 0 for h in unfiltered)
+    want = FM.sketch(seq, 51, 51, 1, [key], sl)
+    assert _diff(want, plain) is not None
+    shuffled = list(keys)
+    rng.shuffle(shuffled)
+    for variant in (0, 1):
+        for lst in (keys, shuffled):
+            got = _run(ctx, [seq, seq], [0, 1, 2], [lst, []], 51, 51, 1, variant)
+            assert _diff(got[0], want) is None, (variant, _diff(got[0], want))
+            assert _diff(got[1], plain) is None, (variant, _diff(got[1], plain))
+            assert _diff(got[0], got[1]) is not None
+
+
 @pytest.mark.parametrize("variant", [0, 1])
 def test_no_lists_is_the_plain_sketch_and_contexts_are_reusable(variant):
     """NULL lists, lists that are all empty, and a context that ran with lists first: the bytes of fsv_sketch_reads"""

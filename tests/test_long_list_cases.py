@@ -31,6 +31,17 @@ def test_tandem_read_has_runs_across_tile_and_merge_boundaries():
     assert L.straddled(h, 4096), "no run of equal hashes across a multiple of 4 096"
 
 
+def test_small_batch_meets_every_raw_count_and_has_its_tandem_runs():
+    reads = L.small_index_batch()
+    sizes = _sizes(L.DENSE, reads)
+    assert len(reads) == len(L.SMALL_LISTS) + 2 and min(len(r) for r in reads) == 14
+    assert tuple(raw for raw, _ in sizes[:len(L.SMALL_LISTS)]) == L.SMALL_LISTS, sizes
+    (raw_a, uq_a), (raw_b, uq_b) = sizes[-2:]
+    assert uq_a < raw_a <= 1024 and 1024 < raw_b <= L.UQ_MAX and uq_b < raw_b, sizes[-2:]
+    h = sorted(int(x) for x in L.lists(reads[-1], L.DENSE)[0]["hash"])
+    assert L.straddled(h, 256), "no run of equal hashes across a multiple of 256"
+
+
 def test_homopolymer_read_outgrows_half_its_slot():
     r = L.homopolymer_read()
     mz, uq = L.lists(r, L.DENSE)
