@@ -306,8 +306,7 @@ __device__ __forceinline__ uint32_t chain_anchor_q(const uint4 av, const uint32_
 __device__ __forceinline__ bool chain_lookup_mem(const fsv_mz *mt, const int nt, const uint4 av, const int lenq, uint32_t &aq, uint32_t &at, uint32_t &srev, uint32_t &tspan)
 {
     const uint64_t ah = (uint64_t)av.x | (uint64_t)av.y << 32;
-    int l2 = 0, h2 = nt;
-    while (l2 < h2) { const int mid = (l2 + h2) >> 1; if (mt[mid].hash < ah) l2 = mid + 1; else h2 = mid; }
+    const int l2 = mz_lower_bound(mt, nt, ah);
     if (!(l2 < nt && mt[l2].hash == ah)) return false;
     const fsv_mz b = mt[l2];
     srev = (av.w & 0xffu) ^ b.rev; tspan = b.span;
@@ -405,7 +404,6 @@ __device__ __forceinline__ void chain_core(const ChainArgs &A, const S &st, cons
         // tests/test_gpu_long_chain.py: every record and window task against the oracle, on the pairs of tests/chain_cases.py).
         const int kk = A.k_score;
         auto eval = [&](int qe, int te, int qj, int tj, int indj, int slj, int fj, int &ti, int &tl) { return chain_eval(A.bw, kk, qe, te, qj, tj, indj, slj, fj, ti, tl); };
-        auto scan_add = [&](int v) { for (int off = 1; off < 64; off <<= 1) { const int o2 = __shfl_up(v, off, 64); if (lane >= off) v += o2; } return v; };
         if (lane == 0) { st.f[0] = (dp_t)kk; st.pred[0] = (idx_t)S::NONE; st.ind[0] = 0; st.sl[0] = 0; }
         __syncthreads();
         int i0 = 1;
@@ -414,7 +412,7 @@ __device__ __forceinline__ void chain_core(const ChainArgs &A, const S &st, cons
             const bool in = lane < nb;
             int qe = 0, te = 0, dq = 0, dt = 0, gap = 0;
             if (in) { qe = st.q(i); te = st.t(i); dq = qe - st.q(i - 1); dt = te - st.t(i - 1); gap = dq > dt ? dq - dt : dt - dq; }
-            const int ti = (int)st.ind[i0 - 1] + scan_add(gap), tl = (int)st.sl[i0 - 1] + scan_add(dq);
+            const int ti = (int)st.ind[i0 - 1] + wave_incl_sum(gap, lane), tl = (int)st.sl[i0 - 1] + wave_incl_sum(dq, lane);
             bool legal = in && dq > 0 && dt > 0;
             int sc = 0;
             if (legal) {
@@ -422,7 +420,7 @@ __device__ __forceinline__ void chain_core(const ChainArgs &A, const S &st, cons
                 const int c = eval(qe, te, qe - dq, te - dt, ti - gap, tl - dq, 0, t2, l2);
                 legal = c >= 0; sc = c;
             }
-            const int fi = (int)st.f[i0 - 1] + scan_add(legal ? sc : 0);
+            const int fi = (int)st.f[i0 - 1] + wave_incl_sum(legal ? sc : 0, lane);
             bool bad = in && !(legal && fi > kk);
             __syncthreads();
             if (in) { st.f[i] = (dp_t)fi; st.ind[i] = (dp_t)ti; st.sl[i] = (dp_t)tl; }
@@ -511,7 +509,7 @@ __device__ __forceinline__ void chain_core(const ChainArgs &A, const S &st, cons
             const int i = base + lane;
             int v = (i < n && i > 0 && st.pred[i] == (idx_t)(i - 1)) ? -1 : i; // run start candidate
             if (i >= n) v = -1;
-            for (int off = 1; off < 64; off <<= 1) { const int o2 = __shfl_up(v, off, 64); if (lane >= off) v = max(v, o2); }
+            for (int off = 1; off < 64; off <<= 1) { const int o2 = __shfl_up(v, off, 64); if (lane >= off) v = max(v, o2); }   // (wave_incl_max: written out, the call reorders the k_chain kernels' code)
             v = max(v, carry);
             if (i < n) st.ind[i] = (dp_t)v;
             carry = __shfl(v, 63, 64);

@@ -78,6 +78,20 @@ __device__ __forceinline__ long long wave_max_i64(long long v)
     return v;
 }
 
+// inclusive prefix sum / prefix maximum over the wavefront's lanes
+__device__ __forceinline__ int wave_incl_sum(int v, int lane)
+{
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) { const int o = __shfl_up(v, off, 64); if (lane >= off) v += o; }
+    return v;
+}
+__device__ __forceinline__ int wave_incl_max(int v, int lane)
+{
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) { const int o = __shfl_up(v, off, 64); if (lane >= off) v = max(v, o); }
+    return v;
+}
+
 // ---- block compaction: a thread's place among the 256 threads (four waves) of its block --------------------------------------------
 // The four wave totals go through s_w (four words of LDS); returns what the waves in front of this one hold and sets *total to the
 // block's sum.  One barrier inside, between the totals' store and their loads: whatever the block did before the call is done after
@@ -96,9 +110,7 @@ __device__ __forceinline__ uint32_t block_waves_before_256(uint32_t wave_total, 
 // exclusive offset of this thread's count: a shuffle scan inside the wave in front of the wave totals
 __device__ __forceinline__ uint32_t block_offset_256(uint32_t cnt, uint32_t *s_w, uint32_t *total)
 {
-    const uint32_t lane = threadIdx.x & 63u;
-    uint32_t incl = cnt;
-    for (uint32_t off = 1; off < 64; off <<= 1) { const uint32_t o = __shfl_up(incl, off, 64); if (lane >= off) incl += o; }
+    const uint32_t incl = (uint32_t)wave_incl_sum((int)cnt, (int)(threadIdx.x & 63u));
     return block_waves_before_256(incl, s_w, total) + incl - cnt;
 }
 // the one-bit case: the rank of a thread that keeps its element (for the others, the kept in front of them) from a ballot

@@ -335,13 +335,6 @@ __device__ __forceinline__ bool homo_strict(F B, int site, int len)
     return f_len >= 3 || b_len >= 3 || (own == f_ch && b_ch == f_ch && f_len + b_len >= 3);
 }
 
-// inclusive prefix sum over the wavefront's lanes
-__device__ __forceinline__ int wave_incl_sum(int v, int lane)
-{
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) { const int o = __shfl_up(v, off, 64); if (lane >= off) v += o; }
-    return v;
-}
 // ---- the column tally of one window: its LDS state and the steps every kernel of the family takes on it ------------------------------
 // TallyCols is what k_snp_sites needs: per-column counters, the coverage difference array, a row of op words per lane and the
 // backbone's bases.  Tally<EVC> (k_consensus, k_consensus_redo, k_bnd_consensus) adds the inserted strings, the "after an insertion"
@@ -1169,7 +1162,7 @@ __global__ __launch_bounds__(64) void k_hap_partition(ConsArgs A, SiteArgs S, fs
         const uint32_t gw = gb + lane;
         const uint32_t c = gw < g1 ? S.site_cnt[gw] : 0u;
         uint32_t incl = c;
-        for (int d = 1; d < 64; d <<= 1) { const uint32_t v = __shfl_up(incl, d); if (lane >= d) incl += v; }
+        for (int d = 1; d < 64; d <<= 1) { const uint32_t v = __shfl_up(incl, d); if (lane >= d) incl += v; }   // (wave_incl_sum: written out, the call reorders this kernel's code)
         const uint32_t base = s_n + incl - c;
         for (uint32_t k = 0; k < c; k++)
             if (base + k < FSV_SITE_RAW_CAP) { const uint2 rec = S.site_rec[(size_t)S.site_off[gw] + k]; s_pos[base + k] = (int32_t)rec.x; s_voff[base + k] = rec.y; }

@@ -4,6 +4,7 @@
 //
 // The pieces the kernels share, each written once:
 //   mz_pack / mz_unpack / mz_make   an fsv_mz as the (hash, pos | rev << 32 | span << 40) pair the LDS sorts move
+//   mz_lower_bound                  a hash looked up in a hash-sorted list (the chain kernels of both translation units)
 //   MzList, mz_emit                 a read's list in its slot: claim an entry, store the record or flag the truncation (both sketch kernels)
 //   flt_set_of, flt_dummy           the read's filter set (KmerSet, fsv_internal.h) and "is this hash filtered"; nothing without FLT
 //   bitonic_lds                     the bitonic network over a view (ByHashPos, ByPos: uniq_read's two arrays; LongTile: sort_long's records)
@@ -37,6 +38,13 @@ __device__ __forceinline__ fsv_mz mz_make(uint64_t hash, uint32_t pos, uint32_t 
 // pay = pos | rev << 32 | span << 40: its low word orders by position
 __device__ __forceinline__ void mz_pack(const fsv_mz m, uint64_t *hash, uint64_t *pay) { *hash = m.hash; *pay = (uint64_t)m.pos | (uint64_t)m.rev << 32 | (uint64_t)m.span << 40; }
 __device__ __forceinline__ fsv_mz mz_unpack(uint64_t hash, uint64_t pay) { return mz_make(hash, (uint32_t)pay, (uint8_t)(pay >> 32), (uint8_t)(pay >> 40)); }
+// the first of the nt entries of a hash-sorted list whose hash is not below `hash` (nt: there is none)
+__device__ __forceinline__ int mz_lower_bound(const fsv_mz *mt, const int nt, const uint64_t hash)
+{
+    int l2 = 0, h2 = nt;
+    while (l2 < h2) { const int mid = (l2 + h2) >> 1; if (mt[mid].hash < hash) l2 = mid + 1; else h2 = mid; }
+    return l2;
+}
 
 // a read's list while the sketch fills it: `cap` entries at out, the count (which runs past the cap when the list is cut) and the read's warning word
 struct MzList { fsv_mz *out; uint32_t cap; uint32_t *cnt, *warn; };

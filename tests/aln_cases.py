@@ -216,6 +216,95 @@ def dp_class_cases():
     return [Case("dp-classes-+", ref, hap, truth, strands=[0]), Case("dp-classes--", ref, synth.revcomp(hap), truth, strands=[1])]
 
 
+# ---- small boxes: the oversize-event path (k_extract_boxes, k_chain_aln<true>, k_aln_events<true>, k_corner) at a few hundred bases
+SMALL_BOX_MAX_CELLS = 1 << 16   # 256 x 256 cells: an event of 300 bases a side is oversize, the 400-base insertion found inside a re-seeded
+                                # box (about 470 x 70 cells with its padding) still goes to the DP
+CORNER_RUNS = (0, 1, 63, 64, 65, 127, 128, 129)
+
+
+def _array(unit, n):
+    """n bases of a tandem array of a 7-base unit: identical on both sides, so a corner's gap-free run crosses it, and nothing in it
+    seeds -- each of its k-mers occurs every 7 bases, more often than a seed may at either depth"""
+    return (unit * (n // len(unit) + 1))[:n]
+
+
+class BoxCase(Case):
+    """kind 'seeded': the box has anchors of its own, the planted gap comes out of the DP (truth as in Case); kind 'corner': nothing
+    in it seeds, it is closed from its corners: an insertion run next to a deletion run"""
+    def __init__(self, name, ref, hap, truth, kind, strands):
+        Case.__init__(self, name, ref, hap, truth, strands=strands)
+        self.kind = kind
+
+
+def small_box_cases():
+    """contigs of 3.3-3.9 kb, each forward and reverse-complemented, with one event that exceeds SMALL_BOX_MAX_CELLS between unique
+    flanks of 1 500 bases:
+      a tandem duplication of a 400-base unit as an insertion and as a deletion: the box seeds again (minimizers that occur twice);
+      300 bases replaced by 330 unrelated ones: nothing seeds, the box is closed from its corners; the same with a reference N ten
+      bases in front of the fill -- no seed covers the N, so it lies inside the left corner's run;
+      such fills behind a shared head, in front of a shared tail, or both, of CORNER_RUNS bases of a tandem array: the corner runs
+      cross them, in steps of 64 positions"""
+    out = []
+
+    def both_strands(name, ref, hap, truth, kind):
+        out.append(BoxCase(name + "-+", ref, hap, truth, kind, [0]))
+        out.append(BoxCase(name + "--", ref, synth.revcomp(hap), truth, kind, [1]))
+
+    rng = np.random.default_rng(2025)
+    L, R, C = rnd(rng, 1500), rnd(rng, 1500), rnd(rng, 400)
+    ref, hap = L + C + R, L + C + C + R
+    both_strands("box-dup-INS", ref, hap, [("INS", left_ins(hap, len(L) + 400, 400, len(L) + 400), 400)], "seeded")
+    ref, hap = L + C + C + R, L + C + R
+    both_strands("box-dup-DEL", ref, hap, [("DEL", left_del(ref, len(L) + 400, 400), 400)], "seeded")
+    X = rnd(rng, 300)
+    Y = _unlike(rng, 330, X)
+    both_strands("box-unrelated", L + X + R, L + Y + R, None, "corner")
+    both_strands("box-unrelated-N", L[:-10] + b"N" + L[-9:] + X + R, L + Y + R, None, "corner")
+    unit = b"ACCTGAT"
+    for n in CORNER_RUNS:
+        for name, head, tail in (("head", n, 0), ("tail", 0, n), ("both", n, n)):
+            rng = np.random.default_rng(7000 + n)
+            L, R, X = rnd(rng, 1500), rnd(rng, 1500), rnd(rng, 300)
+            Y = _unlike(rng, 330, X)
+            H, T = _array(unit, head), _array(unit, tail)
+            both_strands("box-corner-%s-%d" % (name, n), L + H + X + T + R, L + H + Y + T + R, None, "corner")
+    return out
+
+
+def small_box_params(p):
+    p.max_cells = SMALL_BOX_MAX_CELLS
+    return p
+
+
+_small_box_oracle = []
+
+
+def small_box_oracle():
+    """the cases and the oracle's records of each, computed once per process"""
+    if not _small_box_oracle:
+        from tests import oracle_lib as O
+        cases = small_box_cases()
+        po = small_box_params(O.aln_default_params())
+        _small_box_oracle.append((cases, [O.align_contig_multi(c.hap, c.ref, po) for c in cases]))
+    return _small_box_oracle[0]
+
+
+def check_box_case(case, recs):
+    """what the oracle (or the GPU) must make of a small box case: one record on the planted strand that covers the contig; 'seeded':
+    the planted gap with its length, left-aligned, and nothing else; 'corner': exactly one insertion run next to one deletion run,
+    both of at least the lengths that the two fills differ by construction, and no other gap"""
+    assert len(recs) == 1 and [r["rev"] for r in recs] == case.strands, (case.name, len(recs))
+    cg = recs[0]["cigar"]
+    assert sum(n for op, n in cg if op in (0, 1, 4)) == len(case.hap), case.name
+    if case.kind == "seeded":
+        check_case(case, recs)
+        return
+    gaps = [(i, op, n) for i, (op, n) in enumerate(cg) if op in (1, 2)]
+    assert len(gaps) == 2 and gaps[1][0] == gaps[0][0] + 1 and (gaps[0][1], gaps[1][1]) == (1, 2), (case.name, cg)     # I, then D
+    ins, dele = gaps[0][2], gaps[1][2]
+    assert ins - dele == 30 and dele >= 200, (case.name, cg)
+
+
 def check_case(case, recs):
     """recs: the records of the contig (dicts with ref_start, rev, cigar): every planted SV within 1 bp with its exact length,
     nothing else; the expected number of records and their strands"""

@@ -145,6 +145,23 @@ def test_duplications_beyond_max_cells(ctx):
         _same_records(got, O.align_contig_multi(c.hap, c.ref), c.name)
 
 
+def test_small_boxes_and_corner_runs(ctx):
+    """aln_cases.small_box_cases with max_cells lowered so that a few hundred bases a side are an oversize event: boxes that seed
+    again, boxes closed from their corners (one with a reference N in the left corner's run), corner runs of 0 ... 129 bases on
+    either or both sides -- k_extract_boxes, k_chain_aln<true>, k_aln_events<true> and k_corner's 64-position steps.  One call,
+    both strands: every status 0, every contig's event went through a box, records bit-identical to the oracle's."""
+    from tests import aln_cases as A
+    cases, want = A.small_box_oracle()
+    p = A.small_box_params(ctx.default_aln_params())
+    rec, cigar, status = ctx.align_batch([c.hap for c in cases], list(range(len(cases))), [c.ref for c in cases], p)
+    assert (status == 0).all(), list(status)
+    assert ctx.aln_stats()["n_boxes"] >= len(cases)
+    by = _records_by_contig(rec, cigar, len(cases))
+    for c, got, w in zip(cases, by, want):
+        _same_records(got, w, c.name)
+        A.check_box_case(c, got)
+
+
 def test_inversions_make_no_call(ctx):
     """a 2 kb and a 5 kb inversion (contig on either strand): the inverted piece is a record of the other
     strand, the record around it is cut in two, DipPAV's split rule makes nothing of records of different strands -- 0 calls

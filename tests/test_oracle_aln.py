@@ -129,6 +129,21 @@ def test_duplications_beyond_max_cells_are_aligned():
         A.check_case(case, recs)
 
 
+def test_small_boxes_and_corner_runs():
+    """aln_cases.small_box_cases under max_cells = 2^16, the oracle alone: every contig comes back as one record on its strand;
+    a box that seeds again shows its planted 400-base gap, left-aligned, and nothing else; a box with nothing to seed is closed
+    from its corners: exactly one insertion run next to one deletion run, 30 bases apart in length as the fills are (a DP of
+    the two unrelated fills would pair bases inside them instead).  So the set cannot silently stop reaching the path.  The GPU
+    test runs the same cases in one batch and also checks that every contig made a box."""
+    from tests import aln_cases as A
+    cases, recs = A.small_box_oracle()
+    assert len(cases) == 2 * (4 + 3 * len(A.CORNER_RUNS)) and all(3300 <= len(c.hap) <= 3900 for c in cases)
+    assert sum(1 for c in cases if c.kind == "corner") == 2 * (2 + 3 * len(A.CORNER_RUNS))
+    for case, r in zip(cases, recs):
+        assert r is not None, case.name     # status 0
+        A.check_box_case(case, r)
+
+
 def test_inversions_make_no_call():
     """an inversion came back as one forward record with INS + DEL at the breakpoint.  Now the inverted piece is a
     record of the other strand and the forward record is cut around it; DipPAV's split rule ignores pairs of different strands"""
