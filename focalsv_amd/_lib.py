@@ -91,6 +91,20 @@ class Alns(C.Structure):
                 ("n_cigar", C.c_uint64), ("contig_status", C.c_void_p)]
 
 
+class AlnTags(C.Structure):
+    """struct fsv_aln_tags"""
+    _fields_ = [("nm", C.c_void_p), ("cs_off", C.c_void_p), ("cs", C.c_void_p), ("cs_cap", C.c_uint64), ("cs_bytes", C.c_uint64),
+                ("rec_status", C.c_void_p), ("ms", C.c_double)]
+
+
+class BamOut(C.Structure):
+    """fsv_bam_out"""
+    _fields_ = [("n_refs", C.c_uint32), ("ref_name", C.POINTER(C.c_char_p)), ("ref_len", C.c_void_p), ("header_text", C.c_char_p),
+                ("n_rec", C.c_uint64)] + \
+               [(n, C.c_void_p) for n in ("ref_id", "pos", "flag", "mapq", "qname_off", "qname", "cigar_off", "n_cigar_op", "cigar", "seq_off", "seq",
+                                          "nm", "cs_off", "cs", "sa_off", "sa")]
+
+
 class AlnStats(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("n_pairs", "n_events", "dp_cells", "algo_bytes")] + \
                [(n, C.c_double) for n in ("ms_seed", "ms_chain", "ms_events", "ms_dp", "ms_total")] + [("n_boxes", C.c_uint64)]
@@ -174,6 +188,8 @@ def load():
         "fsv_aln_default_params": (None, [C.POINTER(AlnParams)]),
         "fsv_align_batch": (C.c_int, [vp, vp, vp, C.c_uint32, vp, vp, vp, C.c_uint32, C.POINTER(AlnParams), C.POINTER(Alns)]),
         "fsv_aln_last_stats": (C.c_int, [vp, C.POINTER(AlnStats)]),
+        "fsv_aln_tags": (C.c_int, [vp, vp, vp, C.c_uint32, vp, vp, vp, C.c_uint32, C.POINTER(Alns), C.POINTER(AlnTags)]),
+        "fsv_bam_write": (C.c_int, [C.c_char_p, C.POINTER(BamOut), C.c_int]),
         "fsv_bam_open": (C.c_int, [C.c_char_p, C.POINTER(vp)]),
         "fsv_bam_close": (None, [vp]),
         "fsv_bam_n_refs": (C.c_int, [vp]),
@@ -224,6 +240,49 @@ def join_refs(refs):
     roff = np.zeros(len(refs) + 1, dtype=np.uint64)
     np.cumsum([len(r) for r in refs], out=roff[1:])
     return np.frombuffer(b"".join(refs) + b"\0", dtype=np.uint8), roff
+
+
+def bam_write(path, refs, records, header_text="@HD\tVN:1.6\tSO:coordinate\n", threads=4):
+    """fsv_bam_write (host only, no GPU): a coordinate-sorted BAM at `path` and its index at path + '.bai'.
+    refs: [(name, length)]; records: dicts with ref (index, -1 unmapped), pos (0-based, -1 unmapped), flag, mapq, qname, cigar ([(op, len)]
+    or a uint32 array in BAM encoding), seq (str / bytes), and optionally nm (int), cs (str / bytes), sa (str); the writer sorts them.
+    Raises FsvError on a bad argument or an unwritable path (no file is left behind)."""
+    n = len(records)
+
+    def b(x):
+        return x.encode() if isinstance(x, str) else bytes(x)
+
+    def joined(parts, terminated):
+        off = np.zeros(n + 1, dtype=np.uint64)
+        np.cumsum([len(p) + terminated for p in parts], out=off[1:])
+        return np.frombuffer((b"\0" if terminated else b"").join(parts) + b"\0", dtype=np.uint8), off
+
+    cig = [np.asarray([(int(l) << 4) | int(op) for op, l in r["cigar"]] if not isinstance(r["cigar"], np.ndarray) else r["cigar"], dtype=np.uint32)
+           for r in records]
+    ncig = np.asarray([len(c) for c in cig], dtype=np.uint32)
+    coff = np.zeros(n + 1, dtype=np.uint64)
+    np.cumsum(ncig, out=coff[1:])
+    cigar = np.concatenate(cig + [np.zeros(1, np.uint32)])
+    qname, qoff = joined([b(r["qname"]) for r in records], 1)
+    seq, soff = joined([b(r.get("seq", "")) for r in records], 0)
+    a = {"ref_id": np.asarray([r["ref"] for r in records], dtype=np.int32), "pos": np.asarray([r["pos"] for r in records], dtype=np.int32),
+         "flag": np.asarray([r.get("flag", 0) for r in records], dtype=np.uint16), "mapq": np.asarray([r.get("mapq", 60) for r in records], dtype=np.uint8),
+         "qname_off": qoff, "qname": qname, "cigar_off": coff, "n_cigar_op": ncig, "cigar": cigar, "seq_off": soff, "seq": seq}
+    if any(r.get("nm") is not None for r in records):
+        a["nm"] = np.asarray([-(1 << 31) if r.get("nm") is None else r["nm"] for r in records], dtype=np.int32)
+    if any(r.get("cs") for r in records):
+        a["cs"], a["cs_off"] = joined([b(r.get("cs") or "") for r in records], 0)
+    if any(r.get("sa") for r in records):
+        a["sa"], a["sa_off"] = joined([b(r.get("sa") or "") for r in records], 1)
+    names = (C.c_char_p * max(1, len(refs)))(*[nm.encode() for nm, _ in refs])
+    rlen = np.asarray([ln for _, ln in refs] + [0], dtype=np.int32)
+    out = BamOut(len(refs), names, _ptr(rlen), header_text.encode(), n)
+    for k, v in a.items():
+        setattr(out, k, _ptr(v).value)
+    rc = load().fsv_bam_write(os.fsencode(path), C.byref(out), int(threads))
+    if rc:
+        raise FsvError(rc, "fsv_bam_write", str(path))
+    return path
 
 
 def kmer_peaks(hist, start_cnt=5):
@@ -585,6 +644,40 @@ class Context:
         self.check(self._lib.fsv_align_batch(self._h, None if from_dev else _ptr(cseq), _ptr(coff), n, _ptr(cref), _ptr(rseq), _ptr(roff), n_refs, C.byref(p),
                                              C.byref(out)), "fsv_align_batch")
         return rec[: out.n_rec].copy(), cigar[: out.n_cigar].copy(), status[:n].copy()
+
+    def aln_tags(self, rec, cigar, contigs=None, contig_ref=None, refs=None, n_contigs=None, n_refs=None):
+        """fsv_aln_tags: NM and the cs difference string of alignment records (any CIGAR of M / I / D / S / H ops).
+        contigs / contig_ref / refs as align_batch takes them, or contigs = refs = None with n_contigs / n_refs: the sequences the last
+        align_batch left on the device -> (nm int32[n_rec], cs: list of bytes, rec_status int32[n_rec], kernel ms)"""
+        rec = np.ascontiguousarray(rec, dtype=ALN_REC_DTYPE)
+        cigar = np.ascontiguousarray(cigar, dtype=np.uint32)
+        n = len(rec)
+        cg = cigar if len(cigar) else np.zeros(1, np.uint32)
+        alns = Alns(_ptr(rec).value if n else None, n, n, _ptr(cg).value, len(cigar), len(cigar), None)
+        if contigs is None and refs is None:
+            args = (None, None, int(n_contigs), None, None, None, int(n_refs))
+            keep = ()
+        else:
+            rseq, roff = refs if isinstance(refs, tuple) else join_refs(refs)
+            coff = np.zeros(len(contigs) + 1, dtype=np.uint64)
+            np.cumsum([len(c) for c in contigs], out=coff[1:])
+            cseq = np.frombuffer(b"".join(contigs) + b"\0", dtype=np.uint8)
+            cref = np.ascontiguousarray(contig_ref, dtype=np.uint32)
+            keep = (rseq, roff, coff, cseq, cref)
+            args = (_ptr(cseq), _ptr(coff), len(contigs), _ptr(cref), _ptr(rseq), _ptr(roff), len(roff) - 1)
+        nm = np.zeros(max(1, n), dtype=np.int32)
+        off = np.zeros(n + 1, dtype=np.uint64)
+        status = np.zeros(max(1, n), dtype=np.int32)
+        out = AlnTags(_ptr(nm).value, _ptr(off).value, None, 0, 0, _ptr(status).value, 0.0)
+        self.check(self._lib.fsv_aln_tags(self._h, *args, C.byref(alns), C.byref(out)), "fsv_aln_tags")   # the sizing call
+        cs = np.zeros(max(1, int(out.cs_bytes)), dtype=np.uint8)
+        out.cs, out.cs_cap = _ptr(cs).value, int(out.cs_bytes)
+        ms = out.ms
+        if out.cs_bytes:
+            self.check(self._lib.fsv_aln_tags(self._h, *args, C.byref(alns), C.byref(out)), "fsv_aln_tags")
+            ms = out.ms
+        del keep
+        return nm[:n].copy(), [cs[int(off[i]):int(off[i + 1])].tobytes() for i in range(n)], status[:n].copy(), ms
 
     def aln_stats(self):
         st = AlnStats()

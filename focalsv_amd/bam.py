@@ -235,3 +235,53 @@ def reads_signatures(ctx, bam_path, chrom, min_mapq=50):
             ds += d
             is_ += i
     return RS._sort(RS._sort(dc) + RS._sort(ic) + RS._sort(ds) + RS._sort(is_))
+
+
+# ---- contig alignment BAM (the reference's assemblies.sorted.bam: `minimap2 -a --cs | samtools sort`, DipPAV_variant_call.py:103-112)
+_COMP = bytes.maketrans(b"ACGTNacgtn", b"TGCANtgcan")
+
+
+def cigar_string(ops) -> str:
+    return "".join("%d%s" % (n, "MIDNSHP=X"[op]) for op, n in ops)
+
+
+def write_contig_bam(path, chrom_names_and_lengths, records, tags, seqs, *, unaligned=(), threads=4):
+    """The aligner's records as a coordinate-sorted BAM with its .bai (fsv_bam_write).
+      chrom_names_and_lengths  [(name, full length)]: one @SQ line each, in this order
+      records    (rec, cigar, names, chrom_of, offset_of) as dippav.variant_call.records_from_alignment takes them: fsv_aln_rec rows with
+                 their CIGAR buffer and, per contig, its name (or names: a contig filed under both haplotypes yields a record per name),
+                 chromosome and the chromosome offset of its reference window
+      tags       (nm, cs) per record from Context.aln_tags, or None: no NM / cs tags (the SA tags then carry NM 0)
+      seqs       per contig its text
+      unaligned  contigs the aligner reported as unaligned: one unmapped record per name (a refused contig is left out)
+    The first record of a contig in `rec` is the primary (flag 0 / 16), later ones are supplementary (2048 | strand) and keep their soft
+    clips and the full SEQ (minimap2 -Y); a contig with several records carries on each the others, in `rec` order, as its SA tag."""
+    rec, cigar, names, chrom_of, offset_of = records
+    ref_id = {nm: i for i, (nm, _) in enumerate(chrom_names_and_lengths)}
+    rows = []
+    for k, r in enumerate(rec):
+        i = int(r["contig"])
+        ops = [(int(c) & 0xf, int(c) >> 4) for c in cigar[int(r["cigar_off"]): int(r["cigar_off"]) + int(r["n_cigar"])]]
+        rows.append((i, ops, int(r["ref_start"]) + offset_of[i], bool(r["rev"]), int(r["mapq"]), 0 if tags is None else int(tags[0][k]),
+                     None if tags is None else tags[1][k]))
+    of_contig = {}
+    for k, row in enumerate(rows):
+        of_contig.setdefault(row[0], []).append(k)
+    out = []
+    for k, (i, ops, pos, rev, mapq, nm, cs) in enumerate(rows):
+        sib = of_contig[i]
+        sa = "".join("%s,%d,%s,%s,%d,%d;" % (chrom_of[i], rows[j][2] + 1, "-" if rows[j][3] else "+", cigar_string(rows[j][1]), rows[j][4], rows[j][5])
+                     for j in sib if j != k)
+        s = seqs[i].encode() if isinstance(seqs[i], str) else bytes(seqs[i])
+        d = {"ref": ref_id[chrom_of[i]], "pos": pos, "flag": (16 if rev else 0) | (0 if k == sib[0] else 2048), "mapq": mapq, "cigar": ops,
+             "seq": s.translate(_COMP)[::-1] if rev else s, "sa": sa or None}
+        if tags is not None:
+            d["nm"], d["cs"] = nm, cs
+        for name in ([names[i]] if isinstance(names[i], str) else names[i]):
+            out.append(dict(d, qname=name))
+    for i in unaligned:
+        for name in ([names[i]] if isinstance(names[i], str) else names[i]):
+            out.append({"ref": -1, "pos": -1, "flag": 4, "mapq": 0, "cigar": [], "seq": seqs[i], "qname": name})
+    text = "@HD\tVN:1.6\tSO:coordinate\n" + "".join("@SQ\tSN:%s\tLN:%d\n" % (nm, ln) for nm, ln in chrom_names_and_lengths) + \
+        "@PG\tID:focalsv_amd\tPN:focalsv_amd\n"
+    return _lib.bam_write(path, chrom_names_and_lengths, out, header_text=text, threads=threads)

@@ -10,6 +10,7 @@
 //   k_gap_shift         every gap of the stitched CIGAR to its leftmost position (minimap2's mm_fix_cigar rule)
 //   k_nw                dual-affine global DP of one event on anti-diagonals (one workgroup per event), the
 //                       recurrence / tie rules / backtrack of the in-tree ksw2 (ksw2_extz2_sse.c:171-196, ksw2.h:115-150)
+//   k_aln_tags          fsv_aln_tags: NM and the cs difference string of finished records (what minimap2's --cs adds), count / scan / emit
 // The kernels are in k_aln.h; this file is the host path.
 #include "k_aln.h"
 #include <algorithm>
@@ -64,6 +65,14 @@ struct AlnWs {
     Dev<BoxSrc> box_src;
     Dev<CornerTask> corner;
     Dev<int2> corner_out;
+    // fsv_aln_tags: per task its (contig, window), the caller's CIGARs, byte counts / offsets / NM, the cs bytes
+    Dev<uint32_t> tag_q, tag_t, tag_cg;
+    Dev<TagTask> tag_tasks;
+    Dev<uint64_t> tag_cnt, tag_off;
+    Dev<int32_t> tag_nm;
+    Dev<char> tag_cs;
+    // what the last fsv_align_batch left packed in store (n_refs windows, then n_contigs contigs); n_contigs 0: nothing
+    struct Resident { uint32_t n_refs = 0, n_contigs = 0; std::vector<int32_t> len; std::vector<uint32_t> pair_t; } resident;
     fsv_aln_stats stats = {};
     NwLanes lanes;
     std::unique_ptr<AlnWs> sub;   // the workspace of the boxes of oversize events (a second, smaller alignment pass), made by the first box
@@ -625,6 +634,7 @@ static int nw_impl(fsv_ctx *ctx, const char *target, int32_t tl, const char *que
     if ((int64_t)tl * ql > P.max_cells) return fsv_fail(ctx, FSV_EUNSUP, "event larger than max_cells");
     FSV_HIP(ctx, hipSetDevice(ctx->device));
     AlnWs &W = *aln_ws_get(ctx);
+    W.resident = AlnWs::Resident();
     std::vector<uint32_t> word_off; std::vector<int32_t> len;
     TRY(pack_pairs(ctx, W, {query, target}, {(uint64_t)ql, (uint64_t)tl}, word_off, len));
     std::vector<AlnHeader> hdr(1); memset(&hdr[0], 0, sizeof(AlnHeader));
@@ -702,6 +712,7 @@ static int align_batch_impl(fsv_ctx *ctx, const char *contig_seq, const uint64_t
     FSV_HIP(ctx, hipSetDevice(ctx->device));
     AlnWs &W = *aln_ws_get(ctx);
     memset(&W.stats, 0, sizeof(W.stats));
+    W.resident = AlnWs::Resident();
     Timer ttot(ctx);
     PassIn S;
     std::vector<const char *> seq; std::vector<uint64_t> slen;
@@ -712,6 +723,128 @@ static int align_batch_impl(fsv_ctx *ctx, const char *contig_seq, const uint64_t
     W.stats.n_pairs = n_contigs;
     TRY(stitch(ctx, W, S, O, out));
     W.stats.ms_total = ttot.stop();
+    W.resident.n_refs = n_refs; W.resident.n_contigs = n_contigs; W.resident.len = S.len; W.resident.pair_t = S.pair_t;
+    return FSV_OK;
+}
+
+// ---- fsv_aln_tags
+constexpr int64_t TAG_TASK_COLS = 1 << 15;   // a record of more columns is cut into tasks of about this many, at op boundaries
+
+// One record against its sequences' lengths.  Returns FSV_EUNSUP for an op outside M / I / D / S / H (the call fails), FSV_EINVAL for a
+// CIGAR that does not fit (that record fails), else FSV_OK with the record's tasks appended.
+static int tag_tasks_of(const fsv_aln_rec &r, const fsv_alns *alns, uint32_t n_contigs, const int32_t *len, uint32_t n_refs, const uint32_t *pair_t,
+                        std::vector<TagTask> &tasks, std::vector<uint32_t> &tq, std::vector<uint32_t> &tt)
+{
+    if (r.cigar_off > alns->n_cigar || r.n_cigar > alns->n_cigar - r.cigar_off) return FSV_EINVAL;
+    const uint32_t *c = alns->cigar + r.cigar_off;
+    int64_t qsum = 0, tsum = 0;
+    for (uint32_t k = 0; k < r.n_cigar; k++) {
+        const uint32_t op = c[k] & 0xf; const int64_t l = c[k] >> 4;
+        if (op != 0 && op != 1 && op != 2 && op != 4 && op != 5) return FSV_EUNSUP;
+        if (op != 2) qsum += l;
+        if (op == 0 || op == 2) tsum += l;
+    }
+    if (r.contig >= n_contigs) return FSV_EINVAL;
+    const int64_t lenq = len[n_refs + r.contig], lent = len[pair_t[r.contig]];
+    if (qsum != lenq || r.ref_start < 0 || (int64_t)r.ref_start + tsum != (int64_t)r.ref_end || (int64_t)r.ref_end > lent) return FSV_EINVAL;
+    // tasks: cut in front of an op once the task holds TAG_TASK_COLS columns
+    int64_t qp = 0, tp = r.ref_start, cols = 0;
+    TagTask T{r.rev ? 1 : 0, 0, (int32_t)tp, (uint32_t)r.cigar_off, 0};
+    for (uint32_t k = 0; k < r.n_cigar; k++) {
+        const uint32_t op = c[k] & 0xf; const int64_t l = c[k] >> 4;
+        if (cols >= TAG_TASK_COLS) {
+            tasks.push_back(T); tq.push_back(n_refs + r.contig); tt.push_back(pair_t[r.contig]);
+            T.q0 = (int32_t)qp; T.t0 = (int32_t)tp; T.op_off = (uint32_t)(r.cigar_off + k); T.n_ops = 0; cols = 0;
+        }
+        T.n_ops++;
+        if (op != 2) qp += l;
+        if (op == 0 || op == 2) tp += l;
+        if (op <= 2) cols += l;
+    }
+    tasks.push_back(T); tq.push_back(n_refs + r.contig); tt.push_back(pair_t[r.contig]);
+    return FSV_OK;
+}
+
+static int aln_tags_impl(fsv_ctx *ctx, const char *contig_seq, const uint64_t *contig_off, uint32_t n_contigs, const uint32_t *contig_ref,
+                         const char *ref_seq, const uint64_t *ref_off, uint32_t n_refs, const fsv_alns *alns, struct fsv_aln_tags *out)
+{
+    if (!ctx || !alns || !out || !out->nm || !out->cs_off || !out->rec_status || (alns->n_rec && (!alns->rec || !alns->cigar))) return FSV_EINVAL;
+    if ((contig_seq == nullptr) != (ref_seq == nullptr)) return fsv_fail(ctx, FSV_EINVAL, "contig_seq and ref_seq: both or neither");
+    out->cs_bytes = 0; out->ms = 0;
+    const uint32_t n_rec = alns->n_rec;
+    if (alns->n_cigar >= (1ull << 32)) return fsv_fail(ctx, FSV_EUNSUP, "more than 2^32 CIGAR ops; split the batch");
+    const bool resident = contig_seq == nullptr;
+    AlnWs *Wp = (AlnWs *)ctx->aln_ws;
+    std::vector<int32_t> len; std::vector<uint32_t> pair_t;
+    std::vector<const char *> seq; std::vector<uint64_t> slen;
+    if (resident) {
+        if (!Wp || Wp->resident.n_contigs == 0 || Wp->resident.n_contigs != n_contigs || Wp->resident.n_refs != n_refs)
+            return fsv_fail(ctx, FSV_EINVAL, "no sequences of an fsv_align_batch with these counts on this context");
+        len = Wp->resident.len; pair_t = Wp->resident.pair_t;
+    } else {
+        if (!contig_off || !contig_ref || !ref_off || n_contigs == 0 || n_refs == 0) return FSV_EINVAL;
+        seq.resize((size_t)n_refs + n_contigs); slen.resize(seq.size()); len.resize(seq.size()); pair_t.resize(n_contigs);
+        for (uint32_t r = 0; r < n_refs; r++) { seq[r] = ref_seq + ref_off[r]; slen[r] = ref_off[r + 1] - ref_off[r]; }
+        for (uint32_t p = 0; p < n_contigs; p++) {
+            if (contig_ref[p] >= n_refs) return fsv_fail(ctx, FSV_EINVAL, "contig_ref out of range");
+            seq[n_refs + p] = contig_seq + contig_off[p]; slen[n_refs + p] = contig_off[p + 1] - contig_off[p]; pair_t[p] = contig_ref[p];
+        }
+        for (size_t r = 0; r < seq.size(); r++) {
+            if (slen[r] == 0 || slen[r] >= (1ull << 31)) return fsv_fail(ctx, FSV_EINVAL, "empty sequence, or one of 2^31 bases or more");
+            len[r] = (int32_t)slen[r];
+        }
+    }
+    // every record is checked before anything is launched; a record that does not fit its sequences never reaches a kernel
+    std::vector<TagTask> tasks; std::vector<uint32_t> tq, tt, first_task(n_rec + 1, 0);
+    for (uint32_t i = 0; i < n_rec; i++) {
+        first_task[i] = (uint32_t)tasks.size();
+        const int rc = tag_tasks_of(alns->rec[i], alns, n_contigs, len.data(), n_refs, pair_t.data(), tasks, tq, tt);
+        if (rc == FSV_EUNSUP) return fsv_fail(ctx, FSV_EUNSUP, "a CIGAR op outside M / I / D / S / H");
+        out->rec_status[i] = rc; out->nm[i] = rc == FSV_OK ? 0 : -1;
+    }
+    first_task[n_rec] = (uint32_t)tasks.size();
+    const uint32_t nt = (uint32_t)tasks.size();
+    for (uint32_t i = 0; i <= n_rec; i++) out->cs_off[i] = 0;
+    if (nt == 0) return FSV_OK;
+    FSV_HIP(ctx, hipSetDevice(ctx->device));
+    AlnWs &W = *aln_ws_get(ctx);
+    if (!resident) {
+        W.resident = AlnWs::Resident();
+        std::vector<uint32_t> word_off;
+        TRY(pack_pairs(ctx, W, seq, slen, word_off, len));
+    }
+    TRY(upload(ctx, W.tag_q, tq));
+    TRY(upload(ctx, W.tag_t, tt));
+    TRY(upload(ctx, W.tag_tasks, tasks));
+    TRY(ensure(ctx, W.tag_cg, (size_t)alns->n_cigar));
+    FSV_HIP(ctx, hipMemcpyAsync(W.tag_cg.p, alns->cigar, (size_t)alns->n_cigar * 4, hipMemcpyHostToDevice, ctx->stream));
+    TRY(ensure(ctx, W.tag_cnt, nt));
+    TRY(ensure(ctx, W.tag_off, (size_t)nt + 1));
+    TRY(ensure(ctx, W.tag_nm, nt));
+    const PairSeqs S{W.store.p, W.nm(), W.word_off.p, W.len.p, W.tag_q.p, W.tag_t.p};
+    Timer tc(ctx);
+    FSV_LAUNCH(ctx, ctx->stream, k_aln_tags<false>, dim3(nt), dim3(64), 0, S, W.tag_tasks.p, W.tag_cg.p, (const uint64_t *)nullptr, (char *)nullptr, W.tag_cnt.p, W.tag_nm.p);
+    FSV_LAUNCH(ctx, ctx->stream, k_aln_tags_scan, dim3(1), dim3(64), 0, W.tag_cnt.p, nt, W.tag_off.p);
+    out->ms = tc.stop();
+    std::vector<uint64_t> off((size_t)nt + 1); std::vector<int32_t> nm(nt);
+    TRY(download(ctx, off.data(), W.tag_off, (size_t)nt + 1));
+    TRY(download(ctx, nm.data(), W.tag_nm, nt));
+    FSV_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    for (uint32_t i = 0; i < n_rec; i++) {
+        out->cs_off[i] = off[first_task[i]];
+        for (uint32_t t = first_task[i]; t < first_task[i + 1]; t++) out->nm[i] += nm[t];
+    }
+    out->cs_off[n_rec] = off[nt];
+    out->cs_bytes = off[nt];
+    if (!out->cs) return FSV_OK;       // the sizing call
+    if (out->cs_cap < out->cs_bytes) return fsv_fail(ctx, FSV_ECAP, "cs buffer too small (cs_bytes says how many are needed)");
+    if (out->cs_bytes == 0) return FSV_OK;
+    TRY(ensure(ctx, W.tag_cs, out->cs_bytes));
+    Timer te(ctx);
+    FSV_LAUNCH(ctx, ctx->stream, k_aln_tags<true>, dim3(nt), dim3(64), 0, S, W.tag_tasks.p, W.tag_cg.p, W.tag_off.p, W.tag_cs.p, (uint64_t *)nullptr, (int32_t *)nullptr);
+    out->ms += te.stop();
+    TRY(download(ctx, out->cs, W.tag_cs, out->cs_bytes));
+    FSV_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return FSV_OK;
 }
 
@@ -725,4 +858,10 @@ extern "C" int fsv_align_batch(fsv_ctx *ctx, const char *contig_seq, const uint6
                                const char *ref_seq, const uint64_t *ref_off, uint32_t n_refs, const fsv_aln_params *params, fsv_alns *out)
 {
     FSV_GUARD(ctx, align_batch_impl(ctx, contig_seq, contig_off, n_contigs, contig_ref, ref_seq, ref_off, n_refs, params, out));
+}
+
+extern "C" int fsv_aln_tags(fsv_ctx *ctx, const char *contig_seq, const uint64_t *contig_off, uint32_t n_contigs, const uint32_t *contig_ref,
+                            const char *ref_seq, const uint64_t *ref_off, uint32_t n_refs, const fsv_alns *alns, struct fsv_aln_tags *out)
+{
+    FSV_GUARD(ctx, aln_tags_impl(ctx, contig_seq, contig_off, n_contigs, contig_ref, ref_seq, ref_off, n_refs, alns, out));
 }

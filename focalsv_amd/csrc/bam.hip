@@ -16,6 +16,11 @@
 #include <thread>
 #include <atomic>
 #include <future>
+#include <algorithm>
+#include <map>
+#include <numeric>
+#include <unistd.h>
+#include <sys/stat.h>
 
 struct BgzfBlock {
     std::vector<uint8_t> comp, data;
@@ -580,6 +585,223 @@ static int fsv_read_signatures_impl(fsv_ctx *ctx, const fsv_bam_records *rec, in
     }
     for (void *p : {d_pos, d_mq, d_off, d_nop, d_cig, d_out, d_n}) if (p) (void)hipFree(p);
     return rc;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// fsv_bam_write: a coordinate-sorted BAM and its .bai from flat arrays (SAM/BAM specification v1, sections 4.1, 4.2, 5.2, 5.3)
+namespace {
+
+constexpr size_t BGZF_PAYLOAD = 0xff00;
+
+int reg2bin(int64_t beg, int64_t end)
+{
+    --end;
+    if (beg >> 14 == end >> 14) return (int)(((1 << 15) - 1) / 7 + (beg >> 14));
+    if (beg >> 17 == end >> 17) return (int)(((1 << 12) - 1) / 7 + (beg >> 17));
+    if (beg >> 20 == end >> 20) return (int)(((1 << 9) - 1) / 7 + (beg >> 20));
+    if (beg >> 23 == end >> 23) return (int)(((1 << 6) - 1) / 7 + (beg >> 23));
+    if (beg >> 26 == end >> 26) return (int)(((1 << 3) - 1) / 7 + (beg >> 26));
+    return 0;
+}
+
+template <class T> void put_le(std::vector<uint8_t> &v, T x) { const size_t at = v.size(); v.resize(at + sizeof(T)); memcpy(v.data() + at, &x, sizeof(T)); }
+
+// one BGZF block of n payload bytes (n <= BGZF_PAYLOAD; n = 0: the end-of-file marker): header, raw deflate, crc32, isize
+bool bgzf_block(const uint8_t *src, size_t n, std::vector<uint8_t> &out)
+{
+    for (int level : {6, 0}) {   // (a payload that deflate cannot fit into a 64 KiB block goes in stored: 0xff00 bytes always fit)
+        out.assign(18 + compressBound((uLong)n) + 8, 0);
+        z_stream zs;
+        memset(&zs, 0, sizeof(zs));
+        if (deflateInit2(&zs, level, Z_DEFLATED, -15, 8, Z_DEFAULT_STRATEGY) != Z_OK) return false;
+        zs.next_in = const_cast<Bytef *>(src); zs.avail_in = (uInt)n;
+        zs.next_out = out.data() + 18; zs.avail_out = (uInt)(out.size() - 18 - 8);
+        const int rc = deflate(&zs, Z_FINISH);
+        const size_t clen = zs.total_out;
+        deflateEnd(&zs);
+        if (rc != Z_STREAM_END) return false;
+        const size_t bsize = 18 + clen + 8;
+        if (bsize > 65536) continue;
+        static const uint8_t head[16] = {31, 139, 8, 4, 0, 0, 0, 0, 0, 255, 6, 0, 'B', 'C', 2, 0};
+        memcpy(out.data(), head, 16);
+        const uint16_t bs = (uint16_t)(bsize - 1);
+        memcpy(out.data() + 16, &bs, 2);
+        const uint32_t crc = (uint32_t)crc32(crc32(0L, Z_NULL, 0), src, (uInt)n), isize = (uint32_t)n;
+        memcpy(out.data() + 18 + clen, &crc, 4);
+        memcpy(out.data() + 18 + clen + 4, &isize, 4);
+        out.resize(bsize);
+        return true;
+    }
+    return false;
+}
+
+// a file under a temporary name next to its final one: written whole, renamed by commit(), removed if that never happens
+struct TempFile {
+    std::string tmp, final_path; FILE *f = nullptr;
+    explicit TempFile(const std::string &path) : tmp(path + ".tmpXXXXXX"), final_path(path)
+    {
+        const int fd = mkstemp(&tmp[0]);
+        if (fd >= 0) { f = fdopen(fd, "wb"); if (!f) { close(fd); unlink(tmp.c_str()); } }
+    }
+    TempFile(const TempFile &) = delete;
+    TempFile &operator=(const TempFile &) = delete;
+    bool write(const void *p, size_t n) { return f && (n == 0 || fwrite(p, 1, n, f) == n); }
+    bool flush() { if (!f) return false; const bool ok = fclose(f) == 0; f = nullptr; if (ok) { const mode_t m = umask(0); umask(m); (void)chmod(tmp.c_str(), 0666 & ~m); } return ok; }   // (mkstemp makes it 0600)
+    bool commit() { if (tmp.empty() || rename(tmp.c_str(), final_path.c_str()) != 0) return false; tmp.clear(); return true; }
+    ~TempFile() { if (f) fclose(f); if (!tmp.empty()) unlink(tmp.c_str()); }
+};
+
+int bam_write_impl(const char *path, const fsv_bam_out *in, int n_threads)
+{
+    if (!path || !in || (in->n_refs && (!in->ref_name || !in->ref_len))) return FSV_EINVAL;
+    const uint64_t n = in->n_rec;
+    if (n && (!in->ref_id || !in->pos || !in->flag || !in->mapq || !in->qname_off || !in->qname || !in->cigar_off || !in->n_cigar_op || !in->seq_off)) return FSV_EINVAL;
+    if ((in->cs_off == nullptr) != (in->cs == nullptr) || (in->sa_off == nullptr) != (in->sa == nullptr)) return FSV_EINVAL;
+    for (uint32_t r = 0; r < in->n_refs; r++) if (!in->ref_name[r] || in->ref_len[r] < 0) return FSV_EINVAL;
+    // checks, reference spans, the order
+    std::vector<int64_t> ref_span(n, 0);
+    for (uint64_t i = 0; i < n; i++) {
+        const int32_t rid = in->ref_id[i];
+        if (strlen(in->qname + in->qname_off[i]) > 254 || in->seq_off[i + 1] < in->seq_off[i] || in->seq_off[i + 1] - in->seq_off[i] > 0x7fffffffull) return FSV_EINVAL;
+        if (in->n_cigar_op[i] > 65535) return FSV_EUNSUP;
+        if (in->n_cigar_op[i] && !in->cigar) return FSV_EINVAL;
+        if (rid == -1) { if (in->pos[i] != -1 || !(in->flag[i] & 4) || in->n_cigar_op[i]) return FSV_EINVAL; continue; }
+        if (rid < 0 || (uint32_t)rid >= in->n_refs || in->pos[i] < 0 || (in->flag[i] & 4)) return FSV_EINVAL;
+        for (uint32_t k = 0; k < in->n_cigar_op[i]; k++) {
+            const uint32_t c = in->cigar[in->cigar_off[i] + k], op = c & 0xf;
+            if (op > 8) return FSV_EINVAL;
+            if (op == 0 || op == 2 || op == 3 || op == 7 || op == 8) ref_span[i] += c >> 4;
+        }
+        if (ref_span[i] == 0) return FSV_EINVAL;
+        if ((int64_t)in->pos[i] + ref_span[i] > (1ll << 29)) return FSV_EUNSUP;     // beyond what a .bai can index
+    }
+    std::vector<uint64_t> order(n);
+    std::iota(order.begin(), order.end(), 0ull);
+    std::stable_sort(order.begin(), order.end(), [&](uint64_t a, uint64_t b) {
+        const uint32_t ra = (uint32_t)in->ref_id[a], rb = (uint32_t)in->ref_id[b];     // -1 sorts last
+        return ra != rb ? ra < rb : (ra != 0xffffffffu && in->pos[a] < in->pos[b]);
+    });
+    // the uncompressed stream: header, then the records; start[i]: where record order[i] begins
+    std::vector<uint8_t> st;
+    const char *text = in->header_text ? in->header_text : "";
+    st.insert(st.end(), {'B', 'A', 'M', 1});
+    put_le<int32_t>(st, (int32_t)strlen(text));
+    st.insert(st.end(), text, text + strlen(text));
+    put_le<int32_t>(st, (int32_t)in->n_refs);
+    for (uint32_t r = 0; r < in->n_refs; r++) {
+        const size_t l = strlen(in->ref_name[r]) + 1;
+        put_le<int32_t>(st, (int32_t)l);
+        st.insert(st.end(), in->ref_name[r], in->ref_name[r] + l);
+        put_le<int32_t>(st, in->ref_len[r]);
+    }
+    uint8_t nib[256];
+    memset(nib, 15, sizeof(nib));
+    for (int c = 0; c < 16; c++) nib[(uint8_t)"=ACMGRSVTWYHKDBN"[c]] = (uint8_t)c;
+    std::vector<uint64_t> start(n + 1);
+    for (uint64_t k = 0; k < n; k++) {
+        const uint64_t i = order[k];
+        start[k] = st.size();
+        const char *name = in->qname + in->qname_off[i];
+        const size_t l_name = strlen(name) + 1;
+        const int32_t l_seq = (int32_t)(in->seq_off[i + 1] - in->seq_off[i]);
+        const int64_t end = (int64_t)in->pos[i] + std::max<int64_t>(1, ref_span[i]);
+        put_le<int32_t>(st, 0);     // block_size, set below
+        put_le<int32_t>(st, in->ref_id[i]); put_le<int32_t>(st, in->pos[i]);
+        st.push_back((uint8_t)l_name); st.push_back(in->mapq[i]);
+        put_le<uint16_t>(st, (uint16_t)reg2bin(in->pos[i], end)); put_le<uint16_t>(st, (uint16_t)in->n_cigar_op[i]); put_le<uint16_t>(st, in->flag[i]);
+        put_le<int32_t>(st, l_seq); put_le<int32_t>(st, -1); put_le<int32_t>(st, -1); put_le<int32_t>(st, 0);
+        st.insert(st.end(), name, name + l_name);
+        if (in->n_cigar_op[i]) { const uint8_t *c = (const uint8_t *)(in->cigar + in->cigar_off[i]); st.insert(st.end(), c, c + (size_t)in->n_cigar_op[i] * 4); }
+        const uint8_t *sq = (const uint8_t *)(in->seq ? in->seq + in->seq_off[i] : nullptr);
+        const size_t at = st.size();
+        st.resize(at + (size_t)(l_seq + 1) / 2, 0);
+        for (int32_t j = 0; j < l_seq; j++) st[at + (size_t)(j >> 1)] |= (uint8_t)(nib[sq[j]] << ((j & 1) ? 0 : 4));
+        st.insert(st.end(), (size_t)l_seq, 0xff);
+        if (in->nm && in->nm[i] != FSV_BAM_NO_TAG) { st.insert(st.end(), {'N', 'M', 'i'}); put_le<int32_t>(st, in->nm[i]); }
+        if (in->cs && in->cs_off[i + 1] > in->cs_off[i]) {
+            st.insert(st.end(), {'c', 's', 'Z'});
+            st.insert(st.end(), in->cs + in->cs_off[i], in->cs + in->cs_off[i + 1]);
+            st.push_back(0);
+        }
+        if (in->sa && in->sa[in->sa_off[i]]) {
+            const char *sa = in->sa + in->sa_off[i];
+            st.insert(st.end(), {'S', 'A', 'Z'});
+            st.insert(st.end(), sa, sa + strlen(sa) + 1);
+        }
+        const uint64_t body = st.size() - start[k] - 4;
+        if (body > 0x7fffffffull) return FSV_EUNSUP;
+        const int32_t bs = (int32_t)body;
+        memcpy(st.data() + start[k], &bs, 4);
+    }
+    start[n] = st.size();
+    // BGZF: blocks of BGZF_PAYLOAD bytes, deflated side by side, then the end-of-file marker
+    const size_t nb = (st.size() + BGZF_PAYLOAD - 1) / BGZF_PAYLOAD;
+    std::vector<std::vector<uint8_t>> blk(nb + 1);
+    const unsigned nt = (unsigned)std::min<size_t>((size_t)std::min(16, std::max(1, n_threads)), std::max<size_t>(1, nb / 4));
+    std::atomic<bool> ok{true};
+    auto work = [&](unsigned t) {
+        try { for (size_t b = t; b < nb; b += nt) if (!bgzf_block(st.data() + b * BGZF_PAYLOAD, std::min(BGZF_PAYLOAD, st.size() - b * BGZF_PAYLOAD), blk[b])) ok = false; }
+        catch (...) { ok = false; }
+    };
+    if (nt <= 1) work(0);
+    else {
+        std::vector<std::thread> th;
+        try { for (unsigned t = 1; t < nt; t++) th.emplace_back(work, t); }
+        catch (...) { for (auto &t : th) t.join(); throw; }
+        work(0);
+        for (auto &t : th) t.join();
+    }
+    if (!ok || !bgzf_block(nullptr, 0, blk[nb])) return FSV_EINTERNAL;
+    std::vector<uint64_t> caddr(nb + 2, 0);
+    for (size_t b = 0; b <= nb; b++) caddr[b + 1] = caddr[b] + blk[b].size();
+    auto voff = [&](uint64_t u) { return caddr[u / BGZF_PAYLOAD] << 16 | (u % BGZF_PAYLOAD); };
+    // the index: per reference the bins' chunks (neighbours in file order joined) and the linear index
+    std::vector<uint8_t> bai;
+    bai.insert(bai.end(), {'B', 'A', 'I', 1});
+    put_le<int32_t>(bai, (int32_t)in->n_refs);
+    uint64_t k = 0, n_no_coor = 0;
+    for (uint32_t r = 0; r < in->n_refs; r++) {
+        std::map<uint32_t, std::vector<std::pair<uint64_t, uint64_t>>> bins;
+        std::vector<uint64_t> lin;
+        for (; k < n && in->ref_id[order[k]] == (int32_t)r; k++) {
+            const uint64_t i = order[k];
+            const int64_t beg = in->pos[i], end = beg + ref_span[i];
+            const uint64_t v0 = voff(start[k]), v1 = voff(start[k + 1]);
+            auto &ch = bins[(uint32_t)reg2bin(beg, end)];
+            if (!ch.empty() && ch.back().second == v0) ch.back().second = v1; else ch.emplace_back(v0, v1);
+            const size_t w1 = (size_t)((end - 1) >> 14);
+            if (lin.size() <= w1) lin.resize(w1 + 1, ~0ull);
+            for (size_t w = (size_t)(beg >> 14); w <= w1; w++) lin[w] = std::min(lin[w], v0);
+        }
+        put_le<int32_t>(bai, (int32_t)bins.size());
+        for (const auto &b : bins) {
+            put_le<uint32_t>(bai, b.first); put_le<int32_t>(bai, (int32_t)b.second.size());
+            for (const auto &c : b.second) { put_le<uint64_t>(bai, c.first); put_le<uint64_t>(bai, c.second); }
+        }
+        put_le<int32_t>(bai, (int32_t)lin.size());
+        uint64_t last = 0;
+        for (uint64_t v : lin) { if (v != ~0ull) last = v; put_le<uint64_t>(bai, last); }     // an empty window carries the previous offset forward
+    }
+    n_no_coor = n - k;
+    put_le<uint64_t>(bai, n_no_coor);
+    // both files whole under temporary names, then renamed
+    TempFile fb(path), fi(std::string(path) + ".bai");
+    bool w = fb.f && fi.f;
+    for (size_t b = 0; w && b <= nb; b++) w = fb.write(blk[b].data(), blk[b].size());
+    w = w && fi.write(bai.data(), bai.size());
+    w = w && fb.flush() && fi.flush();
+    if (!w || !fb.commit()) return FSV_EINTERNAL;
+    if (!fi.commit()) { unlink(path); return FSV_EINTERNAL; }
+    return FSV_OK;
+}
+
+} // namespace
+
+extern "C" int fsv_bam_write(const char *path, const fsv_bam_out *in, int n_threads)
+{
+    try { return bam_write_impl(path, in, n_threads); }
+    catch (const std::bad_alloc &) { return FSV_ENOMEM; }
+    catch (...) { return FSV_EINTERNAL; }
 }
 
 // no C++ exception crosses the C ABI (a caller through ctypes would see std::terminate)

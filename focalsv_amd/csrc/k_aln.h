@@ -601,6 +601,113 @@ __global__ __launch_bounds__(64) void k_gap_shift(PairSeqs S, const AlnHeader *_
     if (lane == 0) max_shift[blockIdx.x] = res;
 }
 
+// ------------------------------------------------------------------------------------------------ NM / cs tags
+// k_aln_tags: the base-by-base comparison behind a record's NM and cs tags (minimap2 --cs, short form; the grammar and the N and
+// strand conventions: focalsv_hip.h, fsv_aln_tags).  One wavefront per task; a task is a run of consecutive ops of one record (the
+// host cuts a long record at op boundaries, where no token crosses: a run of identical columns ends with its M op).  The CIGAR is
+// walked wave-uniformly.  An M op is compared 64 columns per ballot; the lanes that differ each write their own token -- the
+// `:<n>` of the identical columns in front of them, then `*<ref><query>` -- at an offset from a prefix sum of the token lengths,
+// so a dense stretch of mismatches costs no more steps than a clean one.  I / D bases are copied a lane each.  The same walk runs
+// twice: EMIT = false counts bytes and NM per task, k_aln_tags_scan turns the counts into offsets, EMIT = true writes.
+// The host has checked every record against its sequences' lengths: no position of a task lies outside them.
+struct TagTask { int32_t rev, q0, t0; uint32_t op_off, n_ops; };   // q0 / t0: strand-oriented contig / window position of the first op
+__device__ __forceinline__ int dec_digits(uint32_t v)
+{
+    int n = 1;
+    for (uint32_t p = 10; n < 10 && v >= p; p *= 10) n++;
+    return n;
+}
+// ':' and the nd digits of v
+__device__ __forceinline__ void put_run(char *__restrict__ o, uint32_t v, int nd)
+{
+    o[0] = ':';
+    for (int i = nd; i >= 1; i--) { o[i] = (char)('0' + v % 10u); v /= 10u; }
+}
+// base of the strand-oriented contig, 4 where the contig itself has an N (the mask covers every sequence of the store)
+__device__ __forceinline__ uint32_t tag_qbase(const PairView &V, int p)
+{
+    if (V.nm) {
+        const uint32_t f = (uint32_t)(V.rev ? V.lenq - 1 - p : p);
+        if ((V.nm[V.qw + (f >> 4)] >> (f & 15u)) & 1u) return 4u;
+    }
+    return V.q(p);
+}
+__device__ __forceinline__ char tag_char(uint32_t b) { return (char)(0x6e74676361ull >> (8u * b)); }   // "acgtn"
+
+template <bool EMIT>
+__global__ __launch_bounds__(64) void k_aln_tags(PairSeqs S, const TagTask *__restrict__ tasks, const uint32_t *__restrict__ cigar,
+                                                 const uint64_t *__restrict__ off, char *__restrict__ cs,
+                                                 uint64_t *__restrict__ n_bytes, int32_t *__restrict__ n_diff)
+{
+    const TagTask T = tasks[blockIdx.x];
+    const int lane = threadIdx.x;
+    const PairView V(S, blockIdx.x, T.rev);
+    const uint32_t *cg = cigar + T.op_off;
+    char *out = EMIT ? cs + off[blockIdx.x] : nullptr;
+    int qp = T.q0, tp = T.t0, nm = 0;
+    uint64_t at = 0;
+    for (uint32_t k = 0; k < T.n_ops; k++) {
+        const uint32_t op = cg[k] & 0xf;
+        const int len = (int)(cg[k] >> 4);
+        if (op == 0) {
+            uint32_t run = 0;       // identical columns since the last token of this op
+            for (int base = 0; base < len; base += 64) {
+                const int n = min(64, len - base);
+                bool diff = false; uint32_t qb = 0, tb = 0;
+                if (lane < n) { qb = tag_qbase(V, qp + base + lane); tb = V.t(tp + base + lane); diff = qb != tb || tb > 3u || qb > 3u; }
+                const uint64_t m = __ballot(diff);
+                if (!m) { run += (uint32_t)n; continue; }
+                const uint64_t below = m & ((1ull << lane) - 1ull);
+                const uint32_t gap = below ? (uint32_t)(lane - (63 - __clzll((long long)below)) - 1) : run + (uint32_t)lane;
+                const int nd = gap ? dec_digits(gap) : 0;
+                const int tl = diff ? (gap ? 1 + nd : 0) + 3 : 0;
+                const int incl = wave_incl_sum(tl, lane);
+                if (EMIT && diff) {
+                    char *o = out + at + (uint32_t)(incl - tl);
+                    if (gap) { put_run(o, gap, nd); o += 1 + nd; }
+                    o[0] = '*'; o[1] = tag_char(tb); o[2] = tag_char(qb);
+                }
+                at += (uint32_t)__shfl(incl, 63, 64);
+                nm += __popcll(m);
+                run = (uint32_t)(n - 1 - (63 - __clzll((long long)m)));
+            }
+            if (run) {
+                const int nd = dec_digits(run);
+                if (EMIT && lane == 0) put_run(out + at, run, nd);
+                at += 1u + (uint32_t)nd;
+            }
+            qp += len; tp += len;
+        } else if (op == 1 || op == 2) {
+            if (len) {
+                if (EMIT) {
+                    if (lane == 0) out[at] = op == 1 ? '+' : '-';
+                    for (int i = lane; i < len; i += 64) out[at + 1 + (uint32_t)i] = tag_char(op == 1 ? tag_qbase(V, qp + i) : V.t(tp + i));
+                }
+                at += 1u + (uint32_t)len; nm += len;
+                if (op == 1) qp += len; else tp += len;
+            }
+        } else qp += len;       // S / H: the clipped bases of the contig
+    }
+    if (!EMIT && lane == 0) { n_bytes[blockIdx.x] = at; n_diff[blockIdx.x] = nm; }
+}
+
+// exclusive scan of the tasks' byte counts (one wavefront): off[i] the first byte of task i, off[n] the total
+__global__ __launch_bounds__(64) void k_aln_tags_scan(const uint64_t *__restrict__ cnt, uint32_t n, uint64_t *__restrict__ off)
+{
+    const int lane = threadIdx.x;
+    uint64_t carry = 0;
+    for (uint32_t b = 0; b < n; b += 64) {
+        const uint32_t i = b + (uint32_t)lane;
+        const uint64_t c = i < n ? cnt[i] : 0;
+        uint64_t v = c;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) { const uint64_t u = __shfl_up(v, o, 64); if (lane >= o) v += u; }
+        if (i < n) off[i] = carry + v - c;
+        carry += __shfl(v, 63, 64);
+    }
+    if (lane == 0) off[n] = carry;
+}
+
 // ------------------------------------------------------------------------------------------------ NW
 // One workgroup per event, cells of one anti-diagonal in parallel.  Rolling rows indexed by the query position:
 //   H on diagonals d-1 and d-2, and the E/F/E2/F2 values *leaving* each cell of diagonal d-1.

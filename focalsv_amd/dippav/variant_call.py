@@ -1,7 +1,8 @@
 """dippav_variant_call on the GPU aligner: mirrors focalsv/4_sv_calling/Dippav/DipPAV_variant_call.py:52-171.
 
 Same function name, arguments and output files: <output_dir>/{hp1.fa, hp2.fa, assemblies.fa, dippav_variant_chr<N>.vcf,
-dippav_raw_variant.vcf, dippav_variant_filtered.vcf, final_vcf/dippav_variant_no_redundancy.vcf, signature/*.txt}.
+dippav_raw_variant.vcf, dippav_variant_filtered.vcf, final_vcf/dippav_variant_no_redundancy.vcf, signature/*.txt}, and with
+contig_bam=True the reference's contig alignment file assemblies.sorted.bam with its .bai (NM / cs tags from fsv_aln_tags).
 `minimap2 -a -x asm5 --cs -r2k | samtools sort` (lines 103-112) is replaced by fsv_align_batch: every contig is aligned
 against the reference window of its own region, so contig FASTA headers must carry the region tag
 (Region_<chr>_S<start>_E<end>, which the assembly step's headers do) or `regions=` must map contig index -> window.
@@ -76,18 +77,23 @@ def call_chromosome(records: Sequence[S.AlignedSegment], chrom: str, ref_seq, co
 
 def dippav_variant_call(data_type, read_bam_file, reference_path, hp1_contig_path, hp2_contig_path, output_dir, chr_num,
                         header_file=None, n_thread=10, mem_per_thread='1G', *, regions=None, read_records=None,
-                        ctx: Optional[_lib.Context] = None, device: int = 0):
+                        ctx: Optional[_lib.Context] = None, device: int = 0, contig_bam: bool = False):
     """Drop-in for DipPAV_variant_call.dippav_variant_call.  Extra keyword-only arguments:
       regions       {contig_name: (chrom, win_start, win_end)} when the FASTA headers carry no region tag
       read_records  AlignedSegment-like records of the chromosome's reads, instead of read_bam_file (which is read with the
                     library's own BAM reader, focalsv_amd.bam, and its CIGARs scanned on the GPU)
+      contig_bam    also write <output_dir>/assemblies.sorted.bam and .bai: the contigs' alignment records with NM / cs / SA tags
+                    (focalsv_amd.bam.write_contig_bam).  Off: nothing is launched, allocated or written for it
     """
     assert data_type in ('CCS', 'CLR', 'ONT')
     logger = logging.getLogger(" ")
     os.makedirs(output_dir, exist_ok=True)
     header = open(header_file).readlines() if header_file else vcf.HEADER_LINES
     chrom = 'chr%d' % chr_num
-    chrom_seq = fasta.read_fasta_dict(reference_path)[chrom].upper()
+    ref_dict = fasta.read_fasta_dict(reference_path)
+    chrom_seq = ref_dict[chrom].upper()
+    chroms = [(nm, len(sq)) for nm, sq in ref_dict.items()] if contig_bam else None   # the BAM's @SQ lines
+    del ref_dict
     with open(os.path.join(output_dir, "ref_chr%d.fa" % chr_num), 'w') as f:
         f.write('>' + chrom + '\n' + fasta.fold(chrom_seq, 60) + '\n')
     # reformat_fasta (DipPAV_variant_call.py:14-23): contig_hp{1,2}_<i>, concatenated into assemblies.fa
@@ -117,6 +123,7 @@ def dippav_variant_call(data_type, read_bam_file, reference_path, hp1_contig_pat
     try:
         keep = [i for i, w in enumerate(wins) if w[0] == chrom and seqs[i]]
         rec, cigar, status = ctx.align_batch([seqs[i].encode() for i in keep], [win_index[wins[i]] for i in keep], refs)
+        tags = ctx.aln_tags(rec, cigar, n_contigs=len(keep), n_refs=len(refs))[:2] if contig_bam and keep else None   # on the device-resident sequences
         for i, st in zip(keep, status):      # a refused contig yields no record: say so instead of losing its SVs silently
             if int(st) < 0:
                 logging.getLogger("focalsv_amd").error("%s: the aligner refused this contig (status %d); no alignment record, its SVs are not called", names[i], int(st))
@@ -133,6 +140,11 @@ def dippav_variant_call(data_type, read_bam_file, reference_path, hp1_contig_pat
             ctx.close()
     knames = [names[i] for i in keep]
     records = records_from_alignment(rec, cigar, knames, [chrom] * len(keep), [ref_start[win_index[wins[i]]] for i in keep])
+    if contig_bam:
+        from .. import bam
+        bam.write_contig_bam(os.path.join(output_dir, 'assemblies.sorted.bam'), chroms,
+                             (rec, cigar, knames, [chrom] * len(keep), [ref_start[win_index[wins[i]]] for i in keep]), tags,
+                             [seqs[i] for i in keep], unaligned=[k for k, st in enumerate(status) if int(st) > 0], threads=max(1, min(16, int(n_thread))))
     sig_dir = os.path.join(output_dir, 'signature')
     os.makedirs(sig_dir, exist_ok=True)
     with open(os.path.join(sig_dir, '%s_cigar.txt' % chrom), 'w') as fw:  # CCS.py:726-735

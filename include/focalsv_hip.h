@@ -482,6 +482,66 @@ int fsv_aln_last_stats(const fsv_ctx *ctx, fsv_aln_stats *out);
 int fsv_nw(fsv_ctx *ctx, const char *target, int32_t tl, const char *query, int32_t ql, const fsv_aln_params *params,
            int32_t *score, uint32_t *cigar, uint32_t cigar_cap, uint32_t *n_cigar);
 
+/* ---- NM / cs tags of alignment records (what `--cs` adds to minimap2's output; opt-in, nothing runs unless this is called) ----
+ * alns: records as fsv_align_batch returns them (contig, rev, ref_start / ref_end, cigar_off / n_cigar are read); they are the
+ * caller's: any CIGAR of the ops M, I, D, S, H is taken, another op is FSV_EUNSUP for the call.  The sequences are given as in
+ * fsv_align_batch, or contig_seq == NULL && ref_seq == NULL: the sequences the last fsv_align_batch on this context left packed on
+ * the device (FSV_EINVAL when there are none, or when n_contigs / n_refs differ from that call's; fsv_nw and an fsv_aln_tags call
+ * with sequences replace them).
+ * Every record is checked on the host before anything is launched: its query-consuming ops, clips included, must sum to the
+ * contig's length, ref_start plus its reference-consuming ops must equal ref_end, and ref_end must not exceed the window.  A
+ * record that fails has rec_status FSV_EINVAL, nm -1 and an empty cs, and is not compared; the call still succeeds.
+ * cs is the short form of minimap2's --cs as its manual page defines it: `:<n>` n identical columns, `*<ref><query>` a
+ * substitution, `+<query bases>` an insertion, `-<ref bases>` a deletion; bases lower case (acgtn); clips are not represented; a
+ * run of identical columns ends at the end of its M op.  Conventions of this library (pinned to that grammar, not to a minimap2
+ * run): an N (anything but ACGT / acgt, on either side) pairs with nothing -- the column is written `*n<q>` (or `*<r>n`) and counts
+ * in NM, as the aligner charges it; a record with rev = 1 is compared on the reverse complement of the contig, as SAM shows it.
+ * Two passes on the device (count, scan, emit): a first call with cs == NULL only counts (nm, cs_off, cs_bytes are set); with
+ * cs_cap < cs_bytes the call returns FSV_ECAP with cs_bytes set. */
+struct fsv_aln_tags {     /* (no typedef: the call has the name, as stat() has beside struct stat) */
+    int32_t  *nm;        /* host, n_rec: mismatched columns + inserted + deleted bases */
+    uint64_t *cs_off;    /* host, n_rec + 1 offsets into cs */
+    char     *cs;        /* host, capacity cs_cap: the records' cs strings back to back, no terminators; NULL: only count */
+    uint64_t  cs_cap, cs_bytes;   /* cs_bytes out: bytes needed / written */
+    int32_t  *rec_status;/* host, n_rec: 0, or FSV_EINVAL for a record whose CIGAR does not fit its sequences */
+    double    ms;        /* out: summed kernel time */
+};
+int fsv_aln_tags(fsv_ctx *ctx, const char *contig_seq, const uint64_t *contig_off, uint32_t n_contigs, const uint32_t *contig_ref,
+                 const char *ref_seq, const uint64_t *ref_off, uint32_t n_refs, const fsv_alns *alns, struct fsv_aln_tags *out);
+
+/* ---- BAM output: a coordinate-sorted BAM and its .bai, host only (no GPU, like the rest of fsv_bam_*) -------------------------
+ * Struct of arrays in the reader's style.  The writer sorts the records stably by (ref_id, pos), unmapped ones (ref_id -1, pos -1,
+ * flag & 4, no CIGAR) last in input order; encodes them as SAM v1 section 4.2 (bin by reg2bin, qualities 0xff, mate fields
+ * -1 / -1 / 0, aux in the order NM:i, cs:Z, SA:Z, each only when given); cuts the stream into BGZF blocks of at most 0xff00
+ * payload bytes, deflated with zlib on n_threads host threads (clamped to 1 .. 16), and appends the EOF marker block; writes
+ * path + ".bai" (bins with their chunks, the 16 kb linear index with empty windows carrying the previous offset forward, virtual
+ * offsets at record starts).  Both files are written under temporary names in the same directory and renamed: a failed call leaves
+ * neither.  FSV_EINVAL: a bad argument, ref_id >= n_refs, a mapped record without reference bases in its CIGAR, a name of more
+ * than 254 bytes; FSV_EUNSUP: a CIGAR of more than 65535 ops; FSV_EINTERNAL: the files could not be written. */
+typedef struct fsv_bam_out {
+    uint32_t n_refs;
+    const char *const *ref_name;  /* n_refs NUL-terminated names */
+    const int32_t *ref_len;
+    const char *header_text;      /* SAM header text (may be NULL: empty) */
+    uint64_t n_rec;
+    const int32_t  *ref_id, *pos; /* 0-based position; -1 / -1 unmapped */
+    const uint16_t *flag;
+    const uint8_t  *mapq;
+    const uint64_t *qname_off;    /* NUL-terminated name of record r at qname + qname_off[r] */
+    const char     *qname;
+    const uint64_t *cigar_off;    /* record r owns cigar[cigar_off[r] .. + n_cigar_op[r]) */
+    const uint32_t *n_cigar_op;
+    const uint32_t *cigar;        /* BAM encoding len << 4 | op */
+    const uint64_t *seq_off;      /* n_rec + 1: ASCII bases of record r are seq[seq_off[r] .. seq_off[r + 1]) */
+    const char     *seq;
+    const int32_t  *nm;           /* optional (NULL: no NM tags); FSV_BAM_NO_TAG: none for this record */
+    const uint64_t *cs_off;       /* optional with cs (both or neither): n_rec + 1 offsets; an empty range: no cs tag for this record */
+    const char     *cs;
+    const uint64_t *sa_off;       /* optional with sa: NUL-terminated SA text of record r at sa + sa_off[r], "" for none */
+    const char     *sa;
+} fsv_bam_out;
+int fsv_bam_write(const char *path, const fsv_bam_out *in, int n_threads);
+
 /* ---- BAM input without pysam / samtools --------------------------------------------------------------
  * Replaces, at the reference's pysam boundary, `pysam.AlignmentFile(bam).fetch(chr)` with its per-record fields
  * (extract_reads_signature.py:68-105, 160-209: reference_name, pos, reference_end, cigar, qname, is_reverse, mapq, flag) and the

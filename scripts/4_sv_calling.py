@@ -23,6 +23,8 @@ parser.add_argument('--num_cpus', '-t', type=int, default=10)
 parser.add_argument('--log_dir', '-log', help="Position of log directory", default=None)
 parser.add_argument('--data_type', '-d', type=int, help="HIFI = 0 or CLR = 1 or ONT = 2 data", default=0)
 parser.add_argument('--device', type=int, default=0, help="GPU index (extension)")
+parser.add_argument('--contig-bam', dest='contig_bam', action='store_true',
+                    help="also write assemblies.sorted.bam + .bai, the contig alignments with NM / cs / SA tags (extension; default off)")
 
 
 def gather_haplotype_fasta(regions_dir, hp, out_path):
@@ -50,6 +52,6 @@ if __name__ == "__main__":
     n2 = gather_haplotype_fasta(os.path.join(args.out_dir, "regions"), 2, hp2)
     logger.info(f"contigs: hp1 {n1}, hp2 {n2}")
     dtype = {0: "CCS", 1: "CLR", 2: "ONT"}[args.data_type]
-    final = dippav_variant_call(dtype, args.bam_file, args.reference, hp1, hp2, chrom_dir, args.chr_num, None, args.num_cpus, device=args.device)
+    final = dippav_variant_call(dtype, args.bam_file, args.reference, hp1, hp2, chrom_dir, args.chr_num, None, args.num_cpus, device=args.device, contig_bam=args.contig_bam)
     logger.info(f"final VCF: {final}")
     print(final)
