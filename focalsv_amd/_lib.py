@@ -32,7 +32,7 @@ assert OVL_DTYPE.itemsize == 56
 class AsmParams(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("k", "w", "hpc", "n_rounds", "min_ovlp", "min_anchors", "lookback", "bw_ec", "bw_final",
                                          "min_contig_reads", "win_rate_pm", "k_cap", "accept_err_pm", "bw_rechain", "w_later", "partition", "second_round", "ins_dag",
-                                         "min_anchors_final", "min_ovlp_final", "graph_layout", "junction_cigars", "full_lists", "kmer_filter", "kmer_table", "partial_charge")]
+                                         "min_anchors_final", "min_ovlp_final", "graph_layout", "junction_cigars", "deep_sets", "full_lists", "kmer_filter", "kmer_table", "partial_charge")]
 
 
 class ReadSets(C.Structure):
@@ -78,7 +78,7 @@ class AsmStats(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("n_pairs", "n_overlaps", "n_windows", "n_windows_matched", "n_paths", "n_path_dp",
                                           "dp_columns", "algo_bytes", "n_exact_overlaps", "n_inexact_candidates", "n_path_fr", "n_junction_cigars", "n_junction_used")] + \
                [(n, C.c_double) for n in ("ms_sketch", "ms_chain", "ms_verify", "ms_path", "ms_consensus", "ms_final", "ms_total")] + \
-               [("n_kernels", C.c_uint32), ("pad", C.c_uint32), ("kernels", KernelStat * 16)]
+               [("n_kernels", C.c_uint32), ("pad", C.c_uint32), ("kernels", KernelStat * 24)]     # FSV_MAX_KERNEL_STATS
 
 
 class AlnParams(C.Structure):
@@ -175,6 +175,7 @@ def load():
         "fsv_asm_overlaps": (C.c_int, [vp, C.POINTER(ReadSets), C.POINTER(AsmParams), C.c_int32, vp, C.c_uint32, vp, C.c_uint64, vp, vp, C.c_uint64,
                                        u32p, u32p, vp]),
         "fsv_asm_last_long_lists": (C.c_int, [vp, vp, vp]),
+        "fsv_asm_last_deep_windows": (C.c_int, [vp, vp, vp, vp]),
         "fsv_read_index": (C.c_int, [vp, C.POINTER(ReadSets), C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, C.c_uint64, vp, vp]),
         "fsv_sketch_reads_filtered": (C.c_int, [vp, C.POINTER(ReadSets), C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, C.c_uint64, vp, vp, vp]),
         "fsv_kmer_index": (C.c_int, [vp, C.POINTER(ReadSets), C.c_int32, C.c_int32, C.c_int32, vp, vp, vp]),
@@ -602,7 +603,15 @@ class Context:
         nr, np_ = C.c_uint64(0), C.c_uint64(0)      # full_lists = 1: what the two long-read kernels took (0, 0 otherwise)
         self.check(self._lib.fsv_asm_last_long_lists(self._h, C.byref(nr), C.byref(np_)), "fsv_asm_last_long_lists")
         out["n_long_list_reads"], out["n_spilled_pairs"] = int(nr.value), int(np_.value)
+        out.update(self.deep_windows())
         return out
+
+    def deep_windows(self):
+        """fsv_asm_last_deep_windows: what the last assemble_batch with deep_sets = 1 handed to k_consensus_deep / k_bnd_consensus_deep (all
+        rounds and chunks) -> {"n_deep_windows", "n_deep_junctions", "max_events"}; all 0 after a call with deep_sets = 0"""
+        nw, nj, me = C.c_uint64(0), C.c_uint64(0), C.c_uint32(0)
+        self.check(self._lib.fsv_asm_last_deep_windows(self._h, C.byref(nw), C.byref(nj), C.byref(me)), "fsv_asm_last_deep_windows")
+        return {"n_deep_windows": int(nw.value), "n_deep_junctions": int(nj.value), "max_events": int(me.value)}
 
     def fetch_reads(self, n_reads, total_cap):
         seq = np.empty(total_cap, dtype=np.uint8)

@@ -119,7 +119,7 @@ def assemble_sets(ctx: _lib.Context, sets, logger=None, budget_bytes: Optional[i
 
 def assembly(out_dir: str, cpu: int = 10, threads: int = 8, data_type: int = 0, logger=None, ctx: Optional[_lib.Context] = None,
              device: int = 0, skip_existing: bool = True, kmer_table: bool = False, partial_charge: bool = False, kmer_filter: bool = False,
-             long_reads: bool = False) -> Dict[str, int]:
+             long_reads: bool = False, deep_sets: bool = False) -> Dict[str, int]:
     """3_assembly.py:28-41.  cpu/threads are accepted for CLI compatibility (the GPU batch replaces both).
     kmer_table: run hifiasm's k-mer count table per read set first (fsv_asm_params.kmer_table): a set whose count histogram has no
     coverage peak is left as hifiasm leaves it -- no contig, status bit 128 -- instead of being assembled
@@ -127,7 +127,9 @@ def assembly(out_dir: str, cpu: int = 10, threads: int = 8, data_type: int = 0, 
     times or more in its read set is no minimizer candidate; implies kmer_table, whose filter list it takes
     partial_charge: hifiasm's non_trim_error_rate (fsv_asm_params.partial_charge): an unmatched window beside a matched one costs an overlap
     what two extension alignments leave uncovered, not its whole length; HiFi read sets only (the wide-band profiles refuse it)
-    long_reads: no cap on a read's minimizer list or on a pair's anchors (fsv_asm_params.full_lists): for noisy reads above ~32 kb"""
+    long_reads: no cap on a read's minimizer list or on a pair's anchors (fsv_asm_params.full_lists): for noisy reads above ~32 kb
+    deep_sets: no cap on the inserted-base events of a consensus window (fsv_asm_params.deep_sets): for read sets deeper than ~45 x, where
+    the default drops votes and raises status bit 8"""
     if partial_charge and data_type != 0:
         raise ValueError("partial_charge applies to HiFi read sets (data_type 0) only: the CLR / ONT profiles use thresholds above 31")
     kmer_table = kmer_table or kmer_filter
@@ -152,6 +154,7 @@ def assembly(out_dir: str, cpu: int = 10, threads: int = 8, data_type: int = 0, 
             params.kmer_table = int(bool(kmer_table))
             params.kmer_filter = int(bool(kmer_filter))
             params.full_lists = int(bool(long_reads))
+            params.deep_sets = int(bool(deep_sets))
             per_set = assemble_sets(ctx, sets, logger, params=params)
         finally:
             if own:
@@ -187,8 +190,9 @@ def assembly(out_dir: str, cpu: int = 10, threads: int = 8, data_type: int = 0, 
             params.kmer_filter = int(bool(kmer_filter))
             params.partial_charge = int(bool(partial_charge))
             params.full_lists = int(bool(long_reads))
+            params.deep_sets = int(bool(deep_sets))
             per_set = assemble_sets(ctx, sets, logger, set_flags=[_lib.SET_UNPHASED if 'unphased' in os.path.basename(f) else 0 for f in fas],
-                                    params=params if kmer_table or partial_charge or long_reads else None)
+                                    params=params if kmer_table or partial_charge or long_reads or deep_sets else None)
         finally:
             if own:
                 ctx.close()

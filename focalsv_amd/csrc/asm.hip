@@ -20,10 +20,12 @@ namespace {
 
 enum { KN_SKETCH, KN_UNIQ, KN_CHAIN, KN_BPM, KN_RESCUE, KN_PATH_FAST, KN_PATH_DP, KN_CONSENSUS, KN_REPACK, KN_EXACT, KN_STITCH, KN_PARTITION, KN_BND, KN_BND_CONS,
        KN_UNIQ_LONG, KN_CHAIN_SPILL,   // full_lists = 1: timed on their own, outside the k_uniq / k_chain groups
+       KN_CONS_DEEP, KN_BND_DEEP,      // deep_sets = 1: timed on their own, outside the k_partition / k_consensus / k_bnd_consensus rows
        KN_COUNT,
        ST_SKETCH = KN_COUNT, ST_CHAIN, ST_VERIFY, ST_PATH, ST_CONSENSUS, ST_FINAL };
 const char *const kn_names[KN_COUNT] = {"k_sketch", "k_uniq", "k_chain", "k5_bpm", "k_rescue_accept", "k_path_fast", "k_path_dp", "k_consensus",
-                                        "k_repack", "k_exact", "k_stitch", "k_partition", "k_bnd_tasks", "k_bnd_consensus", "k_uniq_long", "k_chain_spill"};
+                                        "k_repack", "k_exact", "k_stitch", "k_partition", "k_bnd_tasks", "k_bnd_consensus", "k_uniq_long", "k_chain_spill",
+                                        "k_consensus_deep", "k_bnd_consensus_deep"};
 static_assert(KN_COUNT <= FSV_MAX_KERNEL_STATS, "fsv_asm_stats holds every kernel's row");
 // the task lists of a round: its window tasks, the junction tasks of its second consensus pass, the junction cigars of its partition
 // (PASS_NONE: a list outside a batch -- fsv_bpm_paths).  Pass p of round r keeps its device counters in row p (n_rounds + 1) + r.
@@ -79,7 +81,10 @@ enum { CT_TASKS = 0, CT_OVERFLOW = 1, CT_DP = 2, CT_INEXACT = 3, CT_COLS_LO = 4,
        CT_SPILL = 24,        // full_lists = 1: pairs set aside for k_chain_spill (more anchors than the tile in use)
        CT_SPILLED = 25,      // ... summed over the pass's launches (the re-chain starts the list again for either side)
        CT_UQ_LONG = 26,      // full_lists = 1: reads whose list k_uniq_long indexed
-       CT_SLOT = 28 };      // even: the 64-bit sums stay aligned in every slot
+       CT_DEEP_W = 27,       // deep_sets = 1: windows listed for k_consensus_deep (k_consensus and k_consensus_redo: a window can be listed twice)
+       CT_DEEP_B = 28,       // ... junctions listed for k_bnd_consensus_deep
+       CT_DEEP_MAX = 29,     // ... the largest event count of a listed window or junction
+       CT_SLOT = 32 };      // even: the 64-bit sums stay aligned in every slot
 
 template <class... Ts> size_t cap_sum(const Ts &...b) { return (b.cap + ... + 0); }
 
@@ -132,6 +137,7 @@ struct AsmWs {
     Dev<fsv_wtask> tasks, tasks2, tasks3; Dev<fsv_wres> res, res2, res3; Dev<fsv_wpath> paths, paths2;
     Dev<uint4> cols_sb, ovl_c, upair_tab, upair_tab_sw, gwin_tab, bc_rec; Dev<uint2> site_rec; Dev<int8_t> site_vec;
     Dev<uint4> uq_ws, spill_list; Dev<uint8_t> spill_slab;   // full_lists = 1: k_uniq_long's merge buffers; the pairs set aside for k_chain_spill, its slabs
+    Dev<uint2> deep_list, deep_blist; Dev<uint32_t> deep_slab;   // deep_sets = 1: the windows / junctions set aside for the two deep kernels, their event slabs
     Dev<uint64_t> cols;          // k_path_dp's column scratch: 64-bit columns, or 32-bit ones in the same bytes
     Dev<unsigned long long> tmp; // cycle stamps of the diagnostic runs
     Dev<uint8_t> cov3, bnd_bytes, exact_flag, cwin, thr_tab; Dev<uint16_t> cwin_len; Dev<char> contig_out, contig_all;
@@ -148,6 +154,7 @@ struct AsmWs {
     uint32_t n_reads = 0;
     fsv_asm_stats stats;
     uint64_t n_long_reads = 0, n_spilled_pairs = 0;   // full_lists = 1, last call, all rounds and chunks: lists k_uniq_long indexed, pairs k_chain_spill chained
+    uint64_t n_deep_windows = 0, n_deep_junctions = 0; uint32_t deep_max_events = 0;   // deep_sets = 1, last call, all rounds and chunks: what the two deep kernels took
     KTimes kt;
     void *h_pin = nullptr; size_t h_pin_cap = 0; // pinned host staging (exact hits)
     uint32_t *ct_of(int row) { return counters.p + (size_t)row * CT_SLOT; }   // a row of the counter block (valid until counters grows)
@@ -159,7 +166,7 @@ struct AsmWs {
                        site_cursor, redo, site_lists, read_dirty, cov3, lb, sr_store, brel_off, tasks2, res2, paths2, idx2, bc_idx, bc_rec, bc_win, left_list, fix_list,
                        tasks3, res3, src3, bnd_flag, bnd_list, bnd_patch, bnd_bytes, changed, pair_read, wide_list, cols, tmp, gwin_off, gwin_read, sk_ends, sk_low, sk_high,
                        hits, hits_packed, set_hits, ovl_prev, exact_flag, inexact_list, upair_base, upair_tab, upair_tab_sw, ovl_c, gwin_tab, cwin, cwin_len, warn, thr_tab,
-                       pieces, contig_out, new_len, unpack_off, uq_ws, spill_list, spill_slab) + km.held() + fs.held() + ch.held();
+                       pieces, contig_out, new_len, unpack_off, uq_ws, spill_list, spill_slab, deep_list, deep_blist, deep_slab) + km.held() + fs.held() + ch.held();
     }
     // the opt-in stages' state between two calls of fsv_assemble_batch: forgotten when a call begins, valid when it ends well.  stages_ran:
     // false for a call that returned before its first chunk (no set, or no read and no kmer_table) -- the k-mer getters then go on refusing
@@ -263,6 +270,8 @@ struct Round {
     int round = 0; uint32_t task_cap = 0, n_gwin = 0;
     uint32_t *ct = nullptr;          // the round's (or the final pass's) row of device counters
     ConsArgs C;
+    DeepSlabs deep{};                // deep_sets = 1: the event slabs of the round's deep kernels (deep_setup)
+    uint32_t deep_grid = 0;
     std::vector<uint32_t> h_ct;      // the counter rows on the host, as on the device
     uint64_t reads_in_bytes = 0;
     const std::chrono::steady_clock::time_point t_enter = std::chrono::steady_clock::now();
@@ -490,6 +499,7 @@ extern "C" void fsv_asm_default_params(fsv_asm_params *p)
     p->win_rate_pm = 40; p->k_cap = FSV_K_MAX; p->accept_err_pm = 30; p->bw_rechain = 1; p->w_later = 0; p->partition = 1; p->second_round = 1; p->ins_dag = 1;
     p->min_anchors_final = 1; p->min_ovlp_final = 1; p->graph_layout = 1; p->junction_cigars = 1;
     p->full_lists = 0;
+    p->deep_sets = 0;
     p->kmer_filter = 0;
     p->kmer_table = 0;
     p->partial_charge = 0;
@@ -671,6 +681,11 @@ static int second_pass(fsv_ctx *ctx, AsmWs &W, const Round &R)
     A.brel_off = W.brel_off.p; A.b_base = a_words; A.thr_tab = W.thr_tab.p;
     A.tasks2 = W.tasks2.p; A.idx2 = W.idx2.p; A.n_tasks2 = ct2 + CT_TASKS;
     A.bnd_flag = W.bnd_flag.p; A.bnd_list = W.bnd_list.p; A.n_bnd = ct2 + CT_B_LIST; A.store2 = store2;
+    A.deep_list = nullptr; A.deep_n = nullptr; A.deep_cap = 0;
+    if (P.deep_sets) {      // a junction is listed at most once
+        TRY(ensure(ctx, W.deep_blist, (size_t)n_gwin + 2));
+        A.deep_list = W.deep_blist.p; A.deep_n = R.ct + CT_DEEP_B; A.deep_cap = n_gwin + 2;
+    }
     FSV_LAUNCH(ctx, ctx->stream, k_bnd_tasks, dim3((fsv_grid_for(task_cap, 256) + 7u) & ~7u), dim3(256), 0, A);
     W.kt.end(ctx);
     W.kt.begin(ctx, PASS_JUNCTIONS, KN_BPM, 0);
@@ -685,8 +700,20 @@ static int second_pass(fsv_ctx *ctx, AsmWs &W, const Round &R)
     // the junctions' consensus, handed to the windows as patches
     const uint32_t grid_l = std::min<uint32_t>(std::max(1u, n_gwin), (uint32_t)ctx->n_cu * 16);
     W.kt.begin(ctx, PASS_JUNCTIONS, KN_BND_CONS, 0);
-    if (R.wide_bands) FSV_LAUNCH(ctx, ctx->stream, k_bnd_consensus<FSV_EV_CAP_WIDE>, dim3(grid_l), dim3(64), 0, R.C, A, W.paths2.p, store2, W.bnd_patch.p, W.bnd_bytes.p);
-    else FSV_LAUNCH(ctx, ctx->stream, k_bnd_consensus<FSV_EV_CAP>, dim3(grid_l), dim3(64), 0, R.C, A, W.paths2.p, store2, W.bnd_patch.p, W.bnd_bytes.p);
+    if (P.deep_sets) {
+        if (R.wide_bands) FSV_LAUNCH(ctx, ctx->stream, (k_bnd_consensus<FSV_EV_CAP_WIDE, true>), dim3(grid_l), dim3(64), 0, R.C, A, W.paths2.p, store2, W.bnd_patch.p, W.bnd_bytes.p);
+        else FSV_LAUNCH(ctx, ctx->stream, (k_bnd_consensus<FSV_EV_CAP, true>), dim3(grid_l), dim3(64), 0, R.C, A, W.paths2.p, store2, W.bnd_patch.p, W.bnd_bytes.p);
+    } else {
+        if (R.wide_bands) FSV_LAUNCH(ctx, ctx->stream, (k_bnd_consensus<FSV_EV_CAP_WIDE, false>), dim3(grid_l), dim3(64), 0, R.C, A, W.paths2.p, store2, W.bnd_patch.p, W.bnd_bytes.p);
+        else FSV_LAUNCH(ctx, ctx->stream, (k_bnd_consensus<FSV_EV_CAP, false>), dim3(grid_l), dim3(64), 0, R.C, A, W.paths2.p, store2, W.bnd_patch.p, W.bnd_bytes.p);
+    }
+    if (P.deep_sets) {      // the listed junctions once more, before their patches are applied (the list's length is on the device only)
+        W.kt.end(ctx);
+        W.kt.begin(ctx, KN_BND_DEEP, 0);
+        FSV_LAUNCH(ctx, ctx->stream, k_bnd_consensus_deep, dim3(R.deep_grid), dim3(64), 0, R.C, A, W.paths2.p, store2, W.bnd_patch.p, W.bnd_bytes.p, R.deep);
+        W.kt.end(ctx);
+        W.kt.begin(ctx, KN_BND_CONS, 0);
+    }
     FSV_LAUNCH(ctx, ctx->stream, k_bnd_apply, dim3(std::max(1u, n_gwin)), dim3(64), 0, W.gwin_read.p, W.gwin_off.p, W.bnd_patch.p, W.bnd_bytes.p, W.bnd_flag.p, n_gwin,
                W.cwin.p, W.cwin_len.p, W.changed.p, W.warn.p);
     W.kt.end(ctx);
@@ -948,6 +975,30 @@ static int verify_stage(fsv_ctx *ctx, AsmWs &W, const Round &R)
     return FSV_OK;
 }
 
+// deep_sets = 1: the spill list of the round's windows and the event slabs of k_consensus_deep / k_bnd_consensus_deep, sized from what the
+// host knows.  Events of one window or junction: an overlap votes with at most one path there (one window task per overlap and grid
+// window, one junction task per overlap and junction).  A path holds at most FSV_PATH_CAP ops and an event is a maximal run of y-only
+// ops, so two events of a path have an op of another kind between them: at most (FSV_PATH_CAP + 1) / 2 runs.  A window path can add one
+// event in front of its first column (the junction vote).  So FSV_DEEP_EV_PER_OVL events per overlap, times the overlaps a read can have:
+// the largest set's reads minus one.  Tally::add_event checks the bound all the same.  The grid is as many blocks as 256 MB of slabs
+// allow, at most one per CU; the lists' lengths are on the device only, so the launches are unconditional.
+#define FSV_DEEP_EV_PER_OVL ((FSV_PATH_CAP + 1) / 2 + 1)
+static int deep_setup(fsv_ctx *ctx, AsmWs &W, Round &R)
+{
+    const Batch &B = R.B;
+    uint32_t max_set = 1;
+    for (uint32_t s = 0; s < B.n_sets; s++) max_set = std::max(max_set, B.set_start[s + 1] - B.set_start[s]);
+    const uint64_t cap = (uint64_t)FSV_DEEP_EV_PER_OVL * (max_set - 1) + 64;
+    if (cap >= EvSlab::NIL) return fsv_fail(ctx, FSV_EUNSUP, "deep_sets: a set too large for 31-bit event links");
+    const uint64_t per_block = cap * 3 * sizeof(uint32_t);
+    R.deep_grid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>({(uint64_t)ctx->n_cu, (uint64_t)std::max(1u, R.n_gwin), (256ull << 20) / per_block}));
+    TRY(ensure(ctx, W.deep_slab, (size_t)R.deep_grid * cap * 3));
+    TRY(ensure(ctx, W.deep_list, (size_t)R.n_gwin * 2 + 2));      // k_consensus and k_consensus_redo list a window once each
+    R.deep = DeepSlabs{W.deep_slab.p, (uint32_t)cap, R.ct + CT_DEEP_MAX};
+    R.C.deep_list = W.deep_list.p; R.C.deep_n = R.ct + CT_DEEP_W; R.C.deep_cap = R.n_gwin * 2 + 2;
+    return FSV_OK;
+}
+
 // room for the corrected windows, the per-window table, the consensus kernels' arguments (R.C), the reads whose overlaps changed
 static int consensus_setup(fsv_ctx *ctx, AsmWs &W, Round &R)
 {
@@ -980,6 +1031,8 @@ static int consensus_setup(fsv_ctx *ctx, AsmWs &W, Round &R)
         FSV_LAUNCH(ctx, ctx->stream, k_read_dirty, dim3(B.n_reads), dim3(64), 0, W.ovl_c.p, W.paths.p, W.read_set.p, W.set_start.p, W.pair_base.p, B.n_reads, W.read_dirty.p);
         C.read_dirty = W.read_dirty.p;
     }
+    C.deep_list = nullptr; C.deep_n = nullptr; C.deep_cap = 0;
+    if (P.deep_sets && B.n_pairs) TRY(deep_setup(ctx, W, R));
     return FSV_OK;
 }
 
@@ -1070,6 +1123,11 @@ static int consensus_stage(fsv_ctx *ctx, AsmWs &W, Round &R)
         FSV_LAUNCH(ctx, ctx->stream, k_hap_partition, dim3(B.n_reads), dim3(64), 0, C, SA, W.ovl.p, W.ovl_c.p, SL);
         if (R.wide_bands) FSV_LAUNCH(ctx, ctx->stream, k_consensus_redo<FSV_EV_CAP_WIDE>, dim3(grid_l), dim3(64), 0, C, SL);
         else FSV_LAUNCH(ctx, ctx->stream, k_consensus_redo<FSV_EV_CAP>, dim3(grid_l), dim3(64), 0, C, SL);
+        W.kt.end(ctx);
+    }
+    if (C.deep_list) {      // the listed windows once more, from the partition's final accepted bits
+        W.kt.begin(ctx, KN_CONS_DEEP, 0);
+        FSV_LAUNCH(ctx, ctx->stream, k_consensus_deep, dim3(R.deep_grid), dim3(64), 0, C, SL, R.deep);
         W.kt.end(ctx);
     }
     return FSV_OK;
@@ -1370,6 +1428,7 @@ static void fill_stats(AsmWs &W, const Round &R, const Final &F)
         const uint32_t *c = h_ct.data() + (size_t)sl * CT_SLOT;
         mz_total[sl] = (uint64_t)c[CT_MZ_LO] | (uint64_t)c[CT_MZ_HI] << 32;
         W.n_long_reads += c[CT_UQ_LONG]; W.n_spilled_pairs += c[CT_SPILLED];
+        W.n_deep_windows += c[CT_DEEP_W]; W.n_deep_junctions += c[CT_DEEP_B]; W.deep_max_events = std::max(W.deep_max_events, c[CT_DEEP_MAX]);
         if (sl == P.n_rounds) { W.stats.n_inexact_candidates = c[CT_INEXACT]; break; }
         W.stats.n_windows += c[CT_TASKS];
         W.stats.dp_columns += (uint64_t)c[CT_COLS_LO] | (uint64_t)c[CT_COLS_HI] << 32;      // rescue re-runs (k_rescue_accept)
@@ -1918,6 +1977,7 @@ static int check_asm_params(fsv_ctx *ctx, const fsv_asm_params &P)
         P.w_later < 0 || P.w_later > 64)
         return fsv_fail(ctx, FSV_EINVAL, "fsv_asm_params error model out of range (k_cap <= 95, 375 x win_rate_pm / 1000 <= k_cap)");
     if (P.full_lists != 0 && P.full_lists != 1) return fsv_fail(ctx, FSV_EINVAL, "full_lists is 0 or 1");
+    if (P.deep_sets != 0 && P.deep_sets != 1) return fsv_fail(ctx, FSV_EINVAL, "deep_sets is 0 or 1");
     if (P.kmer_filter && !P.kmer_table)
         return fsv_fail(ctx, FSV_EINVAL, "kmer_filter = 1 needs kmer_table = 1: the filter is the list the k-mer count table stage leaves");
     if (P.partial_charge && P.k_cap > FSV_K_MAX)
@@ -1938,6 +1998,7 @@ static int fsv_assemble_batch_impl(fsv_ctx *ctx, const fsv_readsets *sets, const
     // what the opt-in stages leave on the context belongs to this call from here on (its chunks add to it)
     W.reset_stages();
     W.n_long_reads = W.n_spilled_pairs = 0;
+    W.n_deep_windows = W.n_deep_junctions = 0; W.deep_max_events = 0;
     // (without reads a kmer_table call still goes on: every set gets its verdict -- no k-mer, no peak)
     if (sets->n_sets == 0 || (sets->n_reads == 0 && !P.kmer_table)) { for (uint32_t s = 0; s < sets->n_sets; s++) out->set_status[s] = 0; memset(&W.stats, 0, sizeof(W.stats)); W.mark_valid(P, false); return FSV_OK; }
     TRY(check_readsets(ctx, sets, RS_SETS | RS_LEN));   // (the word offsets: per chunk, assemble_chunk)
@@ -2199,6 +2260,14 @@ extern "C" int fsv_asm_last_long_lists(const fsv_ctx *ctx, uint64_t *n_reads, ui
     if (!ctx || !ctx->asm_ws || !n_reads || !n_pairs) return FSV_EINVAL;
     const AsmWs &W = *(const AsmWs *)ctx->asm_ws;
     *n_reads = W.n_long_reads; *n_pairs = W.n_spilled_pairs;
+    return FSV_OK;
+}
+
+extern "C" int fsv_asm_last_deep_windows(const fsv_ctx *ctx, uint64_t *n_windows, uint64_t *n_junctions, uint32_t *max_events)
+{
+    if (!ctx || !ctx->asm_ws || !n_windows || !n_junctions || !max_events) return FSV_EINVAL;
+    const AsmWs &W = *(const AsmWs *)ctx->asm_ws;
+    *n_windows = W.n_deep_windows; *n_junctions = W.n_deep_junctions; *max_events = W.deep_max_events;
     return FSV_OK;
 }
 

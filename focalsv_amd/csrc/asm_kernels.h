@@ -28,7 +28,8 @@
 #define FSV_SB_QUADS ((FSV_WINDOW + 3) / 4)
 #define FSV_FR_MAXERR    3   // k_path_fr: distances it walks without the DP matrix
 #define FSV_EV_CAP_WIDE 2048 // ... for ONT-profile batches (wide bands): ~25 inserted-base events per overlap and window
-#define FSV_EV_CAP     256   // insertion events per grid window (HiFi at 30x: ~8; more sets the read's warning bit 8 and drops the excess)
+#define FSV_EV_CAP     256   // insertion events per grid window in LDS (overlaps x indel rate x 375 x 2 -- HiFi at 30x: a few dozen, 48 reads at 1.2 % indels: 462; more sets
+                             // the read's warning bit 8 and drops the excess, or with deep_sets = 1 sends the window to k_consensus_deep)
 
 // fsv_wpath (include/focalsv_hip.h): 128 bytes per window task; state 2 = queued for the DP kernel (internal)
 static_assert(sizeof(fsv_wpath) == 128, "fsv_wpath layout");

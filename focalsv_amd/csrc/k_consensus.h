@@ -31,7 +31,15 @@ struct ConsArgs {
     uint8_t *cov3;               // per grid window: at least three overlaps voted (the window went through window_consensus); nullptr: not kept
     int junction_vote;           // 1: bases skipped between two windows of an overlap are voted as an insertion (the stand-in for the second pass)
     int ins_dag;                 // 1: inserted strings that disagree go through hifiasm's DAG (lane 0); 0: the most frequent string (ONT profile)
+    // deep_sets = 1 (nullptr: off): a window with more insertion events than its LDS buffer holds, or with more than 255 overlaps, is not
+    // flagged but listed here as {grid window, events} for k_consensus_deep; deep_n counts every attempt, deep_cap entries fit
+    uint2 *deep_list; uint32_t *deep_n; uint32_t deep_cap;
 };
+__device__ __forceinline__ void deep_push(uint2 *list, uint32_t *n, uint32_t cap, uint32_t gw, uint32_t events)
+{
+    const uint32_t k = atomicAdd(n, 1u);
+    if (k < cap) list[k] = make_uint2(gw, events);
+}
 
 __device__ __forceinline__ bool vote_wins(int cnt, int total, bool homo)
 {
@@ -81,7 +89,7 @@ __global__ void k_gwin_tab(const uint32_t *__restrict__ gwin_read, const uint32_
     tab[gw] = make_uint4(r, pair_base[s] + (r - r0) * (ns - 1), ns - 1, gw - gwin_off[r]);
 }
 
-// EVC: insertion events a window can hold (HiFi at 30x: ~8 -> FSV_EV_CAP; ONT-profile reads: hundreds -> FSV_EV_CAP_WIDE)
+// EVC: insertion events a window can hold in LDS (FSV_EV_CAP; ONT-profile reads: FSV_EV_CAP_WIDE; beyond it: deep_sets, k_consensus_deep)
 // MODE 0: every window.  MODE 1: every window, and a window with a column that split_sub_list would keep as a site of the
 // haplotype partition is marked (site_cnt[gw] = FSV_SITE_MARK) -- the consensus written here is then provisional: k_snp_sites and
 // k_hap_partition run next, and the windows of a read that lost overlaps to the partition are redone.  MODE 2: that redo.
@@ -294,15 +302,63 @@ __device__ __forceinline__ bool poa_decide(const int W[4], const int Ifl[4], int
     return kept;
 }
 
+// ---- where a window's insertion events live -------------------------------------------------------------------------------------
+// An event is (key, link to the next event of its column); the tally goes through one of two stores, as chain_core goes through
+// ChainTile and ChainSlab.  EvLds<EVC>: EVC events in LDS with 16-bit links -- the kernels of every call; an event beyond EVC is counted
+// and dropped.  EvSlab (deep_sets = 1, k_consensus_deep / k_bnd_consensus_deep): the block's slab in HBM with 32-bit links, sized by
+// the host so that no window can fill it (asm.hip: deep_slab_events), and a third array the wave gathers a column's keys into.
+// NIL ends a list; ANSWERED marks a column head whose first event holds the insertion consensus; FLW: words per column of Tally::fl.
+template <int EVC>
+struct EvLds {
+    static constexpr bool deep = false;
+    static constexpr int FLW = 1;                      // 8 bits per base
+    static constexpr uint32_t NIL = 0xffffu, ANSWERED = 0x10000u;
+    uint32_t k[EVC];
+    uint16_t n[EVC];
+    __device__ __forceinline__ uint32_t cap() const { return (uint32_t)EVC; }
+    __device__ __forceinline__ uint32_t key(uint32_t i) const { return k[i]; }
+    __device__ __forceinline__ uint32_t next(uint32_t i) const { return n[i]; }
+    __device__ __forceinline__ void put(uint32_t i, uint32_t key_, uint32_t next_) { k[i] = key_; n[i] = (uint16_t)next_; }
+};
+struct EvSlab {
+    static constexpr bool deep = true;
+    static constexpr int FLW = 2;                      // 16 bits per base, as cnt: a field holds the votes of every overlap of a set
+    static constexpr uint32_t NIL = 0x7fffffffu, ANSWERED = 0x80000000u;
+    uint32_t *k, *n, *g;                               // keys, links, the gathered keys of the column being answered: cap_ entries each
+    uint32_t cap_;
+    __device__ __forceinline__ uint32_t cap() const { return cap_; }
+    __device__ __forceinline__ uint32_t key(uint32_t i) const { return k[i]; }
+    __device__ __forceinline__ uint32_t next(uint32_t i) const { return n[i]; }
+    __device__ __forceinline__ void put(uint32_t i, uint32_t key_, uint32_t next_) { k[i] = key_; n[i] = next_; }
+};
+
 // the most frequent inserted string of a column's event list, the smaller key on a tie
-__device__ __forceinline__ void most_frequent_insertion(const uint32_t *s_evkey, const uint16_t *s_evnext, uint32_t head, int &mi, uint32_t &key)
+template <class EV>
+__device__ __forceinline__ void most_frequent_insertion(const EV &ev, uint32_t head, int &mi, uint32_t &key)
 {
     int bc = 0; uint32_t bk = 0;
-    for (uint32_t i = head; i != 0xffffu; i = s_evnext[i]) {
-        const uint32_t k1 = s_evkey[i];
+    for (uint32_t i = head; i != EV::NIL; i = ev.next(i)) {
+        const uint32_t k1 = ev.key(i);
         int cn = 0;
-        for (uint32_t j2 = head; j2 != 0xffffu; j2 = s_evnext[j2]) cn += (s_evkey[j2] == k1);
+        for (uint32_t j2 = head; j2 != EV::NIL; j2 = ev.next(j2)) cn += (ev.key(j2) == k1);
         if (cn > bc || (cn == bc && k1 < bk)) { bc = cn; bk = k1; }
+    }
+    mi = bc; key = bk;
+}
+// the same on the nk keys of a column gathered into g, the wave sharing the quadratic count: a lane counts every 64th key against
+// all of them, then the lanes' answers meet (most votes, the smaller key on a tie: what the list order gives, whatever that order)
+__device__ __forceinline__ void most_frequent_gathered(const uint32_t *g, int nk, int lane, int &mi, uint32_t &key)
+{
+    int bc = 0; uint32_t bk = 0;
+    for (int a = lane; a < nk; a += 64) {
+        const uint32_t k1 = g[a];
+        int cn = 0;
+        for (int j = 0; j < nk; j++) cn += (g[j] == k1);
+        if (cn > bc || (cn == bc && k1 < bk)) { bc = cn; bk = k1; }
+    }
+    for (int d = 32; d >= 1; d >>= 1) {
+        const int oc = __shfl_xor(bc, d); const uint32_t ok = __shfl_xor(bk, d);
+        if (oc > bc || (oc == bc && ok < bk)) { bc = oc; bk = ok; }
     }
     mi = bc; key = bk;
 }
@@ -337,7 +393,7 @@ __device__ __forceinline__ bool homo_strict(F B, int site, int len)
 
 // ---- the column tally of one window: its LDS state and the steps every kernel of the family takes on it ------------------------------
 // TallyCols is what k_snp_sites needs: per-column counters, the coverage difference array, a row of op words per lane and the
-// backbone's bases.  Tally<EVC> (k_consensus, k_consensus_redo, k_bnd_consensus) adds the inserted strings, the "after an insertion"
+// backbone's bases.  Tally<EV> (k_consensus, k_consensus_redo, k_bnd_consensus) adds the inserted strings, the "after an insertion"
 // votes and the lists of the columns to look at.  One __shared__ object per kernel; members are ordered by alignment so that the
 // struct has no padding.
 __device__ __forceinline__ void load_path_ops(const fsv_wpath *P, uint2 (&pv)[13])
@@ -405,13 +461,12 @@ __device__ __forceinline__ bool split_sub_site(const int oa[4], int occ2, int ar
     return (double)(occ0 + 1 + mx) / (double)(arrived + 1) >= 0.95 && (double)mx / (double)(arrived + 1 - (occ0 + 1)) >= 0.70;
 }
 
-template <int EVC>
+template <class EV>
 struct Tally : TallyCols {
-    uint32_t evkey[EVC];               // insertion events of a column form a list: evhead[column] -> event -> evnext[event] ...
-    uint32_t evhead[FSV_WINDOW + 1];
-    uint32_t fl[FSV_WINDOW + 1];       // votes of the mismatch runs that follow an insertion, 8 bits per base (the match runs: cov's upper halves)
+    uint32_t evhead[FSV_WINDOW + 1];   // insertion events of a column form a list: evhead[column] -> event -> ev.next(event) ...
+    uint32_t fl[FSV_WINDOW + 1][EV::FLW];   // votes of the mismatch runs that follow an insertion, 8 (EvSlab: 16) bits per base (the match runs: cov's upper halves)
     uint32_t evn, nins, ndev;
-    uint16_t evnext[EVC];
+    EV ev;
     uint16_t inslist[FSV_INSLIST];     // columns whose inserted strings disagree
     uint16_t devlist[FSV_WINDOW + 1];  // columns some vote deviates at
     static_assert(sizeof(DagLds) <= sizeof(uint32_t) * 64 * 27 && (FSV_WINDOW + 1) * 14 <= sizeof(uint32_t) * 64 * 27,
@@ -424,34 +479,61 @@ struct Tally : TallyCols {
     __device__ __forceinline__ void reset(int lane)
     {
         TallyCols::reset(lane);
-        for (int i = lane; i < FSV_WINDOW + 1; i += 64) evhead[i] = 0xffffu;
-        for (int i = lane; i < FSV_WINDOW + 1; i += 64) fl[i] = 0;
+        for (int i = lane; i < FSV_WINDOW + 1; i += 64) evhead[i] = EV::NIL;
+        for (int i = lane; i < (FSV_WINDOW + 1) * EV::FLW; i += 64) (&fl[0][0])[i] = 0;
         if (lane == 0) { evn = 0; nins = 0; ndev = 0; }
     }
     __device__ __forceinline__ void add_event(int c, uint32_t key)
     {
-        const uint32_t ev = atomicAdd(&evn, 1u);
-        if (ev < (uint32_t)EVC) { evkey[ev] = key; evnext[ev] = (uint16_t)atomicExch(&evhead[c], ev); }
+        const uint32_t e = atomicAdd(&evn, 1u);
+        if (e < ev.cap()) ev.put(e, key, atomicExch(&evhead[c], e));
+    }
+    __device__ __forceinline__ void fl_add(uint32_t c, uint32_t b)
+    {
+        if (EV::FLW == 1) atomicAdd(&fl[c][0], 1u << (b << 3));
+        else atomicAdd(&fl[c][(b >> 1) & (EV::FLW - 1)], 1u << ((b & 1u) << 4));
+    }
+    __device__ __forceinline__ int fl_get(int c, int b) const
+    {
+        return EV::FLW == 1 ? (int)((fl[c][0] >> (b << 3)) & 0xffu) : (int)((fl[c][(b >> 1) & (EV::FLW - 1)] >> ((b & 1) << 4)) & 0xffffu);
     }
 
     // the insertion consensus of every column that has insertions, by lane 0 (a handful per window): the column's keyed events are
     // gathered from its list, the DAG (or, beyond its bounds, the most frequent string) answers, and the answer replaces the list's head
-    // event (key, count); bit 16 of the head marks the column as answered
-    __device__ __forceinline__ void answer_insertions(int n_cols)
+    // event (key, count); EV::ANSWERED in the head marks the column as answered.  EvSlab: the whole wave comes here -- a column can hold
+    // hundreds of events, so the walk also gathers its keys into ev.g and the lanes share the count of the most frequent string; with
+    // ins_dag 0 that string is the answer
+    __device__ __forceinline__ void answer_insertions(int lane, int n_cols, int ins_dag)
     {
         DagLds &D = dag();
         const int n_list = (int)nins, n = n_list > FSV_INSLIST ? n_cols : n_list;      // the list overflowed: every column
         for (int li = 0; li < n; li++) {
             const int c = n_list > FSV_INSLIST ? li : (int)inslist[li];
-            const uint32_t head = evhead[c] & 0xffffu;
-            if (head == 0xffffu || (evhead[c] & 0x10000u)) continue;
+            const uint32_t head = evhead[c] & (EV::ANSWERED - 1u);
+            if (head == EV::NIL || (evhead[c] & EV::ANSWERED)) continue;
             int nk = 0;
-            for (uint32_t i = head; i != 0xffffu; i = evnext[i]) { if (nk < FSV_DG_K) D.keys[nk] = evkey[i]; nk++; }
             uint32_t key = 0;
-            int mi = dag_insertion(D, nk, key);
-            if (mi < 0) most_frequent_insertion(evkey, evnext, head, mi, key);
-            evkey[head] = key; evnext[head] = (uint16_t)mi;
-            evhead[c] |= 0x10000u;
+            if constexpr (EV::deep) {
+                for (uint32_t i = head; i != EV::NIL; i = ev.next(i)) {
+                    const uint32_t kv = ev.key(i);
+                    if (lane == 0 && nk < FSV_DG_K) D.keys[nk] = kv;
+                    if ((nk & 63) == lane) ev.g[nk] = kv;
+                    nk++;
+                }
+                __syncthreads();
+                int mi = -1;
+                if (ins_dag && lane == 0) mi = dag_insertion(D, nk, key);
+                mi = __shfl(mi, 0); key = __shfl(key, 0);
+                if (mi < 0) most_frequent_gathered(ev.g, nk, lane, mi, key);
+                if (lane == 0) { ev.put(head, key, (uint32_t)mi); evhead[c] |= EV::ANSWERED; }
+                __syncthreads();
+            } else {
+                for (uint32_t i = head; i != EV::NIL; i = ev.next(i)) { if (nk < FSV_DG_K) D.keys[nk] = ev.key(i); nk++; }
+                int mi = dag_insertion(D, nk, key);
+                if (mi < 0) most_frequent_insertion(ev, head, mi, key);
+                ev.put(head, key, (uint32_t)mi);
+                evhead[c] |= EV::ANSWERED;
+            }
         }
     }
 
@@ -471,13 +553,14 @@ struct Tally : TallyCols {
             if (cnt_get(c, 5u)) {       // inserted strings that disagree go through the DAG (lane 0, below); one string answers itself
                 const uint32_t head = evhead[c];
                 bool same = true;
-                if (head != 0xffffu) { const uint32_t k0 = evkey[head]; for (uint32_t i = evnext[head]; i != 0xffffu; i = evnext[i]) if (evkey[i] != k0) { same = false; break; } }
-                if (!same && ins_dag) { const uint32_t k = atomicAdd(&nins, 1u); if (k < FSV_INSLIST) inslist[k] = (uint16_t)c; }
+                if (head != EV::NIL) { const uint32_t k0 = ev.key(head); for (uint32_t i = ev.next(head); i != EV::NIL; i = ev.next(i)) if (ev.key(i) != k0) { same = false; break; } }
+                // (EvSlab: listed without the DAG too -- the wave then finds the most frequent string together, below)
+                if (!same && (ins_dag || EV::deep)) { const uint32_t k = atomicAdd(&nins, 1u); if (k < FSV_INSLIST) inslist[k] = (uint16_t)c; }
             }
         }
         int arrived = wave_incl_sum(run, lane) - run, farrived = wave_incl_sum(frun, lane) - frun;
         __syncthreads();
-        if (lane == 0 && nins) answer_insertions(n_cols);
+        if ((EV::deep || lane == 0) && nins) answer_insertions(lane, n_cols, ins_dag);
         __syncthreads();
         uint8_t (*o)[14] = out();      // paths are done
         // Columns nobody deviates at (no vote in cnt: nine in ten even in the first round) keep the backbone's base: poa_decide then
@@ -502,18 +585,18 @@ struct Tally : TallyCols {
             const bool homo = c > 0 && homo_strict([&](int pp) { return xb(org, pp); }, org + c - 1, len);
             int W[4], Ifl[4], dev = 0;
 #pragma unroll
-            for (int b = 0; b < 4; b++) { W[b] = (int)cnt_get(c, (uint32_t)b); dev += W[b]; Ifl[b] = (int)((fl[c] >> (b << 3)) & 0xffu); }
+            for (int b = 0; b < 4; b++) { W[b] = (int)cnt_get(c, (uint32_t)b); dev += W[b]; Ifl[b] = fl_get(c, b); }
             const int dl = (int)cnt_get(c, 4u), ni = (int)cnt_get(c, 5u);
 #pragma unroll
             for (int b = 0; b < 4; b++) if ((int)own == b) { W[b] += arrived - dev - dl + 1; Ifl[b] = farrived; }
             int mi = 0; uint32_t ikey = 0;
             if (ni) {
-                const uint32_t hv = evhead[c], head = hv & 0xffffu;
-                if (head != 0xffffu) {
-                    ikey = evkey[head];
-                    if (hv & 0x10000u) mi = (int)evnext[head];                                   // the DAG's answer
-                    else if (ins_dag) { for (uint32_t i = head; i != 0xffffu; i = evnext[i]) mi++; }   // one string, mi times
-                    else most_frequent_insertion(evkey, evnext, head, mi, ikey);
+                const uint32_t hv = evhead[c], head = hv & (EV::ANSWERED - 1u);
+                if (head != EV::NIL) {
+                    ikey = ev.key(head);
+                    if (hv & EV::ANSWERED) mi = (int)ev.next(head);                              // the DAG's answer (EvSlab: or the wave's)
+                    else if (ins_dag || EV::deep) { for (uint32_t i = head; i != EV::NIL; i = ev.next(i)) mi++; }   // one string, mi times
+                    else most_frequent_insertion(ev, head, mi, ikey);
                 }
             }
             const bool kept = poa_decide(W, Ifl, dl, ni, mi, ikey, (int)own, homo, &o[c][0]);
@@ -533,8 +616,8 @@ struct Tally : TallyCols {
 // row: the lane's 26 op words in LDS (fields past plen are 0), nz: bit w set = word w is not all matches.
 // pend: an insertion in front of column xs is already pending (the junction vote).  Returns the number of y-only ops (n2).
 #define FSV_PEND_N 4
-template <int EVC>
-__device__ __forceinline__ void cons_flush(Tally<EVC> &S, const uint32_t *__restrict__ store, uint32_t y_word, int y_len, int y_rev, int ry_start,
+template <class T>
+__device__ __forceinline__ void cons_flush(T &S, const uint32_t *__restrict__ store, uint32_t y_word, int y_len, int y_rev, int ry_start,
                                            const uint32_t (&ent)[FSV_PEND_N], int n)
 {
     // entry: column | (y position - ry_start) << 9 | L << 19 (0: a mismatch) | flagged << 23
@@ -548,18 +631,18 @@ __device__ __forceinline__ void cons_flush(Tally<EVC> &S, const uint32_t *__rest
         if (L == 0u) {
             const uint32_t yb = bits[i] & 3u;
             S.cnt_add((int)xp, yb);
-            if (e >> 23) atomicAdd(&S.fl[xp], 1u << (yb << 3));
+            if (e >> 23) S.fl_add(xp, yb);
         } else S.add_event((int)xp, (L << 24) | (bits[i] & ((1u << (2u * L)) - 1u)));
     }
 }
-template <int EVC>
-__device__ __forceinline__ int cons_walk(Tally<EVC> &S, const uint32_t *row, uint32_t nz, int plen, int xs, int xlim, bool pend,
+template <class T>
+__device__ __forceinline__ int cons_walk(T &S, const uint32_t *row, uint32_t nz, int plen, int xs, int xlim, bool pend,
                                          const uint32_t *__restrict__ store, uint32_t y_word, int y_len, int y_rev, int ry_start)
 {
     int n2 = 0, n3 = 0, fstart = -1, fmm_pos = -1, np = 0, p = 0;
     uint32_t ent[FSV_PEND_N] = {0u, 0u, 0u, 0u};
     while (true) {
-        if (np == FSV_PEND_N) { cons_flush<EVC>(S, store, y_word, y_len, y_rev, ry_start, ent, np); np = 0; }
+        if (np == FSV_PEND_N) { cons_flush(S, store, y_word, y_len, y_rev, ry_start, ent, np); np = 0; }
         if (!pend) {       // on to the next op that is not a match
             int w = p >> 4;
             if (w >= 26) break;
@@ -606,7 +689,7 @@ __device__ __forceinline__ int cons_walk(Tally<EVC> &S, const uint32_t *row, uin
         p++;
     }
     if (fstart >= 0) { atomicAdd(&S.cov[fstart], 65536); atomicAdd(&S.cov[xs + plen - n2], -65536); }
-    if (np) cons_flush<EVC>(S, store, y_word, y_len, y_rev, ry_start, ent, np);
+    if (np) cons_flush(S, store, y_word, y_len, y_rev, ry_start, ent, np);
     return n2;
 }
 
@@ -620,14 +703,15 @@ struct SiteLists {
     // window cigar ([1] > [2]: none)
     const int32_t *bc_win;
 };
-template <int EVC, int MODE>
-__device__ __forceinline__ void consensus_window(const ConsArgs &A, const uint32_t gw, const SiteLists &L)
+// EV: the event store (above); slab: the block's EvSlab when EV is one
+template <class EV, int MODE>
+__device__ __forceinline__ void consensus_window(const ConsArgs &A, const uint32_t gw, const SiteLists &L, const EvSlab *slab = nullptr)
 {
     // Per-column votes of one 375-bp grid window.  A match op votes for the backbone's own base, so a lane (= one
     // overlap) only contributes (a) its coverage interval, through a difference array, and (b) its deviations --
     // mismatches, deleted columns, insertions -- which it finds by skipping the all-match words of its 2-bit path.
     // Deviations are sparse (HiFi: ~1.5 per window), so their LDS atomics do not collide the way per-step votes would.
-    __shared__ Tally<EVC> S;
+    __shared__ Tally<EV> S;
     __shared__ uint32_t s_anydev;      // some overlap deviates from the backbone somewhere in this window
     const int lane = threadIdx.x;
     const uint4 gt = A.gwin_tab[gw];
@@ -646,6 +730,7 @@ __device__ __forceinline__ void consensus_window(const ConsArgs &A, const uint32
         return;
     }
     S.reset(lane);
+    if constexpr (EV::deep) { if (lane == 0) S.ev = *slab; }
     if (lane == 0) s_anydev = 0;
     __syncthreads();
     for (uint32_t oi = lane; oi < n_ovl; oi += 64) {
@@ -688,7 +773,7 @@ __device__ __forceinline__ void consensus_window(const ConsArgs &A, const uint32
         if (pend || nz) s_anydev = 1u;
         int n2 = 0;
         if (clean_path) { if (pend) S.cnt_add(xs, 5u); }      // the first op is a match at column xs
-        else n2 = cons_walk<EVC>(S, S.path[lane], nz, plen, xs, glen, pend, A.store, y_word, y_len, y_rev, ry_start);
+        else n2 = cons_walk(S, S.path[lane], nz, plen, xs, glen, pend, A.store, y_word, y_len, y_rev, ry_start);
         // coverage interval: every x base of the task is consumed exactly once
         atomicAdd(&S.cov[xs], 1);
         atomicAdd(&S.cov[xs + plen - n2], -1);
@@ -697,7 +782,14 @@ __device__ __forceinline__ void consensus_window(const ConsArgs &A, const uint32
     // fewer than three overlaps: the reference leaves the window alone; no deviation anywhere: every vote is for the backbone
     const bool verbatim = S.cover < 3u || s_anydev == 0u;
     if (A.cov3 && lane == 0) A.cov3[gw] = S.cover >= 3u ? 1 : 0;
-    if (S.evn > (uint32_t)EVC && lane == 0) atomicOr(&A.warn[r], (uint32_t)FSV_W_INS_EVENTS);
+    // more events than the buffer holds: flagged, the excess dropped -- or, with deep_sets, the window is listed for k_consensus_deep
+    // (so is one whose fl fields could wrap) and what is written below is provisional
+    if constexpr (!EV::deep) {
+        if (lane == 0 && (S.evn > S.ev.cap() || (A.deep_list && S.cover > 255u))) {
+            if (!A.deep_list) atomicOr(&A.warn[r], (uint32_t)FSV_W_INS_EVENTS);
+            else if (!verbatim) deep_push(A.deep_list, A.deep_n, A.deep_cap, gw, S.evn);
+        }
+    }
     const int bc_lo = (MODE == 1 && L.bc_win) ? L.bc_win[3 * (size_t)gw + 1] : 1, bc_hi = (MODE == 1 && L.bc_win) ? L.bc_win[3 * (size_t)gw + 2] : 0;
     bool site = false;
     int c0, c1;
@@ -741,7 +833,7 @@ template <int EVC, int MODE>
 __global__ __launch_bounds__(64) void k_consensus(ConsArgs A, uint32_t n_gwin, SiteLists L)
 {
     uint32_t gw;
-    if (xcd_block(n_gwin, gw)) consensus_window<EVC, MODE>(A, gw, L);
+    if (xcd_block(n_gwin, gw)) consensus_window<EvLds<EVC>, MODE>(A, gw, L);
 }
 
 // the redo: a fixed grid walks the list k_hap_partition left
@@ -750,7 +842,32 @@ __global__ __launch_bounds__(64) void k_consensus_redo(ConsArgs A, SiteLists L)
 {
     const uint32_t n = L.win_n[1];
     for (uint32_t i = blockIdx.x; i < n; i += gridDim.x) {
-        consensus_window<EVC, 0>(A, L.redo_list[i], L);
+        consensus_window<EvLds<EVC>, 0>(A, L.redo_list[i], L);
+        __syncthreads();
+    }
+}
+
+// deep_sets = 1, once per round after k_consensus_redo (the partition's accepted bits are final): a fixed grid walks the windows the two
+// kernels above listed, a wavefront per entry, and writes each one's cwin / cwin_len / changed again from a tally that drops nothing:
+// the events in the block's slab of HBM, fl in 16-bit fields.  A window listed twice (by k_consensus and by the redo) comes out the
+// same twice.  MODE 1's site marking reads cnt only and stands.  max_events: the largest event count of a listed window.
+struct DeepSlabs {
+    uint32_t *base; uint32_t cap;      // per block 3 x cap words: keys, links, gathered keys
+    uint32_t *max_events;
+    __device__ __forceinline__ EvSlab of_block(uint32_t b) const
+    {
+        uint32_t *p = base + (size_t)b * 3u * cap;
+        return EvSlab{p, p + cap, p + 2 * (size_t)cap, cap};
+    }
+};
+__global__ __launch_bounds__(64) void k_consensus_deep(ConsArgs A, SiteLists L, DeepSlabs D)
+{
+    const uint32_t n = min(*A.deep_n, A.deep_cap);
+    const EvSlab ev = D.of_block(blockIdx.x);
+    for (uint32_t i = blockIdx.x; i < n; i += gridDim.x) {
+        const uint2 e = A.deep_list[i];
+        if (threadIdx.x == 0) atomicMax(D.max_events, e.y);
+        consensus_window<EvSlab, 0>(A, e.x, L, &ev);
         __syncthreads();
     }
 }
@@ -1330,6 +1447,7 @@ struct BndArgs {
     fsv_wtask *tasks2; int32_t *idx2; uint32_t *n_tasks2;      // junction tasks; idx2[window task] = its junction task or -1
     uint32_t *bnd_flag, *bnd_list, *n_bnd;                    // per junction: bit 0 = has a task (and is in the list), the rest = alignments that match base for base
     const uint32_t *store2;                                   // the second-pass store: the round's reads, then the first pass's result
+    uint2 *deep_list; uint32_t *deep_n; uint32_t deep_cap;    // deep_sets = 1 (nullptr: off): junctions set aside for k_bnd_consensus_deep, as ConsArgs::deep_list
 };
 
 __global__ __launch_bounds__(256) void k_bnd_tasks(BndArgs A)
@@ -1417,94 +1535,125 @@ __global__ __launch_bounds__(256) void k_bnd_scatter(fsv_wres *__restrict__ res2
 // gw the bases [hs, hs + hold) become hnew bytes (the tail bytes first in the junction's byte slot)
 struct BndPatch { uint16_t ts, told, tnew, hs, hold, hnew, valid, pad; };
 
-template <int EVC>
+template <class EV>
+struct BndLds : Tally<EV> {
+    uint32_t terr;
+    uint16_t off[FSV_WINDOW + 2];   // where a column's output starts in the consensus
+    uint8_t own[FSV_WINDOW + 1];    // the column keeps a base (its own or another one)
+};
+// the junction in front of grid window gw: its patch, or patch[gw].valid = 0.  SPILL: deep_sets = 1 (B.deep_list is there)
+template <class EV, bool SPILL>
+__device__ __forceinline__ void bnd_junction(const ConsArgs &A, const BndArgs &B, const fsv_wpath *__restrict__ paths2, const uint32_t *__restrict__ store2,
+                                             BndPatch *__restrict__ patch, uint8_t *__restrict__ patch_bytes, const uint32_t gw, const EvSlab *slab = nullptr)
+{
+    static_assert(2 * FSV_BND_HALF + 1 <= FSV_WINDOW, "a junction's backbone fits the tally of a window");
+    __shared__ BndLds<EV> S;
+    const int lane = threadIdx.x;
+    const uint4 gt = A.gwin_tab[gw];
+    const uint32_t r = gt.x, pbase = gt.y, n_ovl = gt.z;
+    const int g = (int)gt.w;
+    const int gs = g * FSV_WINDOW;
+    const int LB = (int)B.lb[gw], len_now = LB + (int)B.cwin_len[gw];
+    const int cws = max(0, LB - FSV_BND_HALF), cwe = min(len_now - 1, LB + FSV_BND_HALF - 1), blen = cwe - cws + 1;
+    if (lane == 0) { patch[gw].valid = 0; S.terr = 0; }
+    S.stage_backbone(lane, store2 + B.b_base + B.brel_off[r], cws, len_now);
+    S.reset(lane);
+    if constexpr (EV::deep) { if (lane == 0) S.ev = *slab; }
+    __syncthreads();
+    for (uint32_t oi = lane; oi < n_ovl; oi += 64) {
+        const uint4 oc = A.ovl_c[pbase + oi];
+        const int o_x_s = (int)oc.x, o_n_win = (int)(oc.z & 0x7fffffffu);
+        const int j = g - o_x_s / FSV_WINDOW;
+        if (!(oc.z >> 31) || j < 0 || j >= o_n_win || o_x_s > gs) continue;
+        const int32_t slot = B.idx2[oc.y + (uint32_t)j];
+        if (slot == -2) { atomicAdd(&S.cover, 1u); atomicAdd(&S.cov[0], 1); atomicAdd(&S.cov[blen], -1); continue; }   // matches base for base
+        if (slot < 0) continue;
+        const fsv_wpath *P = paths2 + slot;
+        const uint4 h0 = *reinterpret_cast<const uint4 *>(P);
+        if ((h0.w & 0xffu) != 1u) continue;
+        const uint2 h1 = *reinterpret_cast<const uint2 *>((const uint8_t *)P + 16);
+        const int perr = (int)(int16_t)(h0.z >> 16);
+        atomicAdd(&S.cover, 1u);
+        const int ry_start = (int)h0.x, plen = (int)(int16_t)(h0.z & 0xffffu);
+        int n2 = 0;
+        if (perr != 0) {
+            atomicAdd(&S.terr, (uint32_t)perr);
+            uint2 pv[13];
+            load_path_ops(P, pv);
+            const uint32_t nz = S.stage_path(lane, pv);
+            n2 = cons_walk(S, S.path[lane], nz, plen, 0, blen, false, A.store, h1.x, (int)h1.y, (int)((h0.w >> 8) & 0xffu), ry_start);
+        }
+        atomicAdd(&S.cov[0], 1);
+        atomicAdd(&S.cov[plen - n2], -1);
+    }
+    __syncthreads();
+    if (S.cover < 3u || S.terr == 0u) return;         // MIN_COVERAGE_THRESHOLD; "if there are no error, we do not need correction"
+    // as in consensus_window: flagged, or with deep_sets listed for k_bnd_consensus_deep and the patch below provisional.  (SPILL is a
+    // template parameter here: as a run-time test of B.deep_list the branch cost the kernel a VGPR)
+    if constexpr (!EV::deep) {
+        if (lane == 0 && (S.evn > S.ev.cap() || (SPILL && S.cover > 255u))) {
+            if (!SPILL) atomicOr(&A.warn[r], (uint32_t)FSV_W_INS_EVENTS);
+            else deep_push(B.deep_list, B.deep_n, B.deep_cap, gw, S.evn);
+        }
+    }
+    int c0, c1;
+    lane_columns(lane, blen, c0, c1);
+    for (int c = c0; c < c1; c++) S.own[c] = 1;
+    const bool differs = S.decide_columns(lane, c0, c1, cws, blen, len_now, false, A.ins_dag, [&](int c, int, bool kept) { S.own[c] = kept; });
+    uint8_t (*s_out)[14] = S.out();
+    int mine = 0;
+    for (int c = c0; c < c1; c++) mine += s_out[c][0];
+    if (__ballot(differs) == 0ull) return;            // the new cigar is one run of matches
+    int off = wave_incl_sum(mine, lane) - mine;
+    for (int c = c0; c < c1; c++) { S.off[c] = (uint16_t)off; off += s_out[c][0]; }
+    // the first and the last column to replace: the first kept column at or after 25 / at or after blen - 1 - 25
+    const int sb = FSV_BND_SIDE, eb = blen - 1 - FSV_BND_SIDE;
+    int fs = 0x7fffffff, fe = 0x7fffffff;
+    for (int c = c0; c < c1; c++) { if (S.own[c] && c >= sb && c < fs) fs = c; if (S.own[c] && c >= eb && c < fe) fe = c; }
+    for (int d = 32; d >= 1; d >>= 1) { fs = min(fs, __shfl_xor(fs, d)); fe = min(fe, __shfl_xor(fe, d)); }
+    __syncthreads();
+    if (eb <= sb || fs == 0x7fffffff || fe == 0x7fffffff) return;     // "if there are some gap at the end of x, it very likely miscorrection"
+    const int o0 = (int)S.off[fs] + s_out[fs][0] - 1, o1 = (int)S.off[fe] + s_out[fe][0] - 1;   // the two kept bases in the consensus
+    const int R0 = cws + fs, R1 = cws + fe, sc = LB - cws;    // first-pass coordinates of the stretch; sc: the later window's first column
+    const int o_split = sc <= fs ? o0 : (sc > fe ? o1 + 1 : (int)S.off[sc]);
+    const int lb_prev = (int)B.lb[gw - 1];
+    BndPatch bp;
+    bp.valid = 1; bp.pad = 0;
+    bp.ts = (uint16_t)max(0, R0 - lb_prev); bp.told = (uint16_t)max(0, min(R1, LB - 1) - R0 + 1); bp.tnew = (uint16_t)(o_split - o0);
+    bp.hs = (uint16_t)(max(R0, LB) - LB); bp.hold = (uint16_t)max(0, R1 - max(R0, LB) + 1); bp.hnew = (uint16_t)(o1 + 1 - o_split);
+    if (R0 < lb_prev || o1 + 1 - o0 > FSV_CW_STRIDE) {     // the stretch would reach a third window / outgrow its slot: left as the first pass had it
+        if (lane == 0) atomicOr(&A.warn[r], (uint32_t)FSV_W_WINDOW_KEPT);
+        return;
+    }
+    uint8_t *dst = patch_bytes + (size_t)gw * FSV_CW_STRIDE;
+    for (int c = c0; c < c1; c++)
+        for (int b = 0; b < s_out[c][0]; b++) { const int pos = (int)S.off[c] + b; if (pos >= o0 && pos <= o1) dst[pos - o0] = s_out[c][1 + b]; }
+    if (lane == 0) patch[gw] = bp;
+}
+
+template <int EVC, bool SPILL>
 __global__ __launch_bounds__(64) void k_bnd_consensus(ConsArgs A, BndArgs B, const fsv_wpath *__restrict__ paths2, const uint32_t *__restrict__ store2,
                                                       BndPatch *__restrict__ patch, uint8_t *__restrict__ patch_bytes)
 {
-    static_assert(2 * FSV_BND_HALF + 1 <= FSV_WINDOW, "a junction's backbone fits the tally of a window");
-    struct Lds : Tally<EVC> {
-        uint32_t terr;
-        uint16_t off[FSV_WINDOW + 2];   // where a column's output starts in the consensus
-        uint8_t own[FSV_WINDOW + 1];    // the column keeps a base (its own or another one)
-    };
-    __shared__ Lds S;
-    const int lane = threadIdx.x;
     const uint32_t n_list = *B.n_bnd;
     for (uint32_t li = blockIdx.x; li < n_list; li += gridDim.x) {
         __syncthreads();
-        const uint32_t gw = B.bnd_list[li];
-        const uint4 gt = A.gwin_tab[gw];
-        const uint32_t r = gt.x, pbase = gt.y, n_ovl = gt.z;
-        const int g = (int)gt.w;
-        const int gs = g * FSV_WINDOW;
-        const int LB = (int)B.lb[gw], len_now = LB + (int)B.cwin_len[gw];
-        const int cws = max(0, LB - FSV_BND_HALF), cwe = min(len_now - 1, LB + FSV_BND_HALF - 1), blen = cwe - cws + 1;
-        if (lane == 0) { patch[gw].valid = 0; S.terr = 0; }
-        S.stage_backbone(lane, store2 + B.b_base + B.brel_off[r], cws, len_now);
-        S.reset(lane);
+        bnd_junction<EvLds<EVC>, SPILL>(A, B, paths2, store2, patch, patch_bytes, B.bnd_list[li]);
+    }
+}
+
+// deep_sets = 1, before k_bnd_apply: the junctions k_bnd_consensus listed get their patch again from a tally that drops nothing (see
+// k_consensus_deep)
+__global__ __launch_bounds__(64) void k_bnd_consensus_deep(ConsArgs A, BndArgs B, const fsv_wpath *__restrict__ paths2, const uint32_t *__restrict__ store2,
+                                                           BndPatch *__restrict__ patch, uint8_t *__restrict__ patch_bytes, DeepSlabs D)
+{
+    const uint32_t n = min(*B.deep_n, B.deep_cap);
+    const EvSlab ev = D.of_block(blockIdx.x);
+    for (uint32_t i = blockIdx.x; i < n; i += gridDim.x) {
         __syncthreads();
-        for (uint32_t oi = lane; oi < n_ovl; oi += 64) {
-            const uint4 oc = A.ovl_c[pbase + oi];
-            const int o_x_s = (int)oc.x, o_n_win = (int)(oc.z & 0x7fffffffu);
-            const int j = g - o_x_s / FSV_WINDOW;
-            if (!(oc.z >> 31) || j < 0 || j >= o_n_win || o_x_s > gs) continue;
-            const int32_t slot = B.idx2[oc.y + (uint32_t)j];
-            if (slot == -2) { atomicAdd(&S.cover, 1u); atomicAdd(&S.cov[0], 1); atomicAdd(&S.cov[blen], -1); continue; }   // matches base for base
-            if (slot < 0) continue;
-            const fsv_wpath *P = paths2 + slot;
-            const uint4 h0 = *reinterpret_cast<const uint4 *>(P);
-            if ((h0.w & 0xffu) != 1u) continue;
-            const uint2 h1 = *reinterpret_cast<const uint2 *>((const uint8_t *)P + 16);
-            const int perr = (int)(int16_t)(h0.z >> 16);
-            atomicAdd(&S.cover, 1u);
-            const int ry_start = (int)h0.x, plen = (int)(int16_t)(h0.z & 0xffffu);
-            int n2 = 0;
-            if (perr != 0) {
-                atomicAdd(&S.terr, (uint32_t)perr);
-                uint2 pv[13];
-                load_path_ops(P, pv);
-                const uint32_t nz = S.stage_path(lane, pv);
-                n2 = cons_walk<EVC>(S, S.path[lane], nz, plen, 0, blen, false, A.store, h1.x, (int)h1.y, (int)((h0.w >> 8) & 0xffu), ry_start);
-            }
-            atomicAdd(&S.cov[0], 1);
-            atomicAdd(&S.cov[plen - n2], -1);
-        }
-        __syncthreads();
-        if (S.cover < 3u || S.terr == 0u) continue;       // MIN_COVERAGE_THRESHOLD; "if there are no error, we do not need correction"
-        if (S.evn > (uint32_t)EVC && lane == 0) atomicOr(&A.warn[r], (uint32_t)FSV_W_INS_EVENTS);
-        int c0, c1;
-        lane_columns(lane, blen, c0, c1);
-        for (int c = c0; c < c1; c++) S.own[c] = 1;
-        const bool differs = S.decide_columns(lane, c0, c1, cws, blen, len_now, false, A.ins_dag, [&](int c, int, bool kept) { S.own[c] = kept; });
-        uint8_t (*s_out)[14] = S.out();
-        int mine = 0;
-        for (int c = c0; c < c1; c++) mine += s_out[c][0];
-        if (__ballot(differs) == 0ull) continue;          // the new cigar is one run of matches
-        int off = wave_incl_sum(mine, lane) - mine;
-        for (int c = c0; c < c1; c++) { S.off[c] = (uint16_t)off; off += s_out[c][0]; }
-        // the first and the last column to replace: the first kept column at or after 25 / at or after blen - 1 - 25
-        const int sb = FSV_BND_SIDE, eb = blen - 1 - FSV_BND_SIDE;
-        int fs = 0x7fffffff, fe = 0x7fffffff;
-        for (int c = c0; c < c1; c++) { if (S.own[c] && c >= sb && c < fs) fs = c; if (S.own[c] && c >= eb && c < fe) fe = c; }
-        for (int d = 32; d >= 1; d >>= 1) { fs = min(fs, __shfl_xor(fs, d)); fe = min(fe, __shfl_xor(fe, d)); }
-        __syncthreads();
-        if (eb <= sb || fs == 0x7fffffff || fe == 0x7fffffff) continue;   // "if there are some gap at the end of x, it very likely miscorrection"
-        const int o0 = (int)S.off[fs] + s_out[fs][0] - 1, o1 = (int)S.off[fe] + s_out[fe][0] - 1;   // the two kept bases in the consensus
-        const int R0 = cws + fs, R1 = cws + fe, sc = LB - cws;    // first-pass coordinates of the stretch; sc: the later window's first column
-        const int o_split = sc <= fs ? o0 : (sc > fe ? o1 + 1 : (int)S.off[sc]);
-        const int lb_prev = (int)B.lb[gw - 1];
-        BndPatch bp;
-        bp.valid = 1; bp.pad = 0;
-        bp.ts = (uint16_t)max(0, R0 - lb_prev); bp.told = (uint16_t)max(0, min(R1, LB - 1) - R0 + 1); bp.tnew = (uint16_t)(o_split - o0);
-        bp.hs = (uint16_t)(max(R0, LB) - LB); bp.hold = (uint16_t)max(0, R1 - max(R0, LB) + 1); bp.hnew = (uint16_t)(o1 + 1 - o_split);
-        if (R0 < lb_prev || o1 + 1 - o0 > FSV_CW_STRIDE) {     // the stretch would reach a third window / outgrow its slot: left as the first pass had it
-            if (lane == 0) atomicOr(&A.warn[r], (uint32_t)FSV_W_WINDOW_KEPT);
-            continue;
-        }
-        uint8_t *dst = patch_bytes + (size_t)gw * FSV_CW_STRIDE;
-        for (int c = c0; c < c1; c++)
-            for (int b = 0; b < s_out[c][0]; b++) { const int pos = (int)S.off[c] + b; if (pos >= o0 && pos <= o1) dst[pos - o0] = s_out[c][1 + b]; }
-        if (lane == 0) patch[gw] = bp;
+        const uint2 e = B.deep_list[i];
+        if (threadIdx.x == 0) atomicMax(D.max_events, e.y);
+        bnd_junction<EvSlab, false>(A, B, paths2, store2, patch, patch_bytes, e.x, &ev);
     }
 }
 

@@ -178,6 +178,12 @@ typedef struct fsv_asm_params {
                                * for every set that is not flagged FSV_SET_UNPHASED; 0: best-buddy chains (ONT profile, unphased sets) */
     int32_t junction_cigars;  /* 1 (default): the haplotype partition reads the ~50 columns on each side of a window junction off the re-aligned
                                * junction cigar, as hifiasm does (calculate_boundary_cigars, Correct.cpp:2310; markSNP_advance :5054); 0: window cigars */
+    int32_t deep_sets;        /* 0 (default in all three profiles): a consensus window or junction holds 256 inserted-base events in LDS (2 048 with the
+                               * wide-band profiles); a deeper one drops the rest and its read gets FSV_W_INS_EVENTS.  1: no vote is dropped and the bit
+                               * is never raised -- such a window, and one with more than 255 overlaps (whose 8-bit "after an insertion" counters
+                               * could wrap), is listed on the device and redone by k_consensus_deep / k_bnd_consensus_deep with its events in a slab
+                               * of HBM and 16-bit counters; corrected reads and contigs are the oracle's at any depth.  Any other value is FSV_EINVAL.
+                               * What the two kernels took: fsv_asm_last_deep_windows.  (In front of full_lists: the struct's tail is pinned, see there.) */
     int32_t full_lists;       /* 0 (default in all three profiles): a read's per-read index holds its first 4 096 minimizers (FSV_W_MZ_TRUNC beyond) and a
                                * pair's chain the anchors its LDS tile holds (FSV_W_ANCHOR_TRUNC beyond).  1: neither is cut and neither bit is raised --
                                * lists above 4 096 entries are sorted through HBM (k_uniq_long), pairs above the tile are chained in an HBM slab
@@ -253,7 +259,8 @@ typedef struct fsv_contigs {
 #define FSV_W_MZ_TRUNC     1  /* a read had more minimizers than the per-read cap; the rest were ignored */
 #define FSV_W_ANCHOR_TRUNC 2  /* a read pair had more anchors than the chaining tile holds */
 #define FSV_W_NO_LAYOUT    4  /* no chain of min_contig_reads reads: the set has no contig (hifiasm writes an empty GFA for it too) */
-#define FSV_W_INS_EVENTS   8  /* a consensus window saw more inserted-base events than its buffer holds; the extra votes were dropped */
+#define FSV_W_INS_EVENTS   8  /* a consensus window saw more inserted-base events than its buffer holds; the extra votes were dropped
+                                 * (never with fsv_asm_params.deep_sets = 1) */
 #define FSV_W_WINDOW_KEPT 16  /* a corrected window would have outgrown its slot; the read keeps that window uncorrected */
 #define FSV_W_INTERNAL    32  /* a minimizer slot overflowed (cannot happen: one minimizer per base at most) */
 #define FSV_W_SITES       64  /* haplotype partition: more than 255 candidate sites in a window, 1 024 in a read (512 once sites beside another site are
@@ -268,7 +275,7 @@ int fsv_assemble_batch(fsv_ctx *ctx, const fsv_readsets *sets, const fsv_asm_par
 
 /* Optional per-stage counters of the last fsv_assemble_batch on this context (for the roofline accounting):
  * window tasks verified (K5), paths computed (K6), DP column steps, algorithmic bytes (SURVEY.md 8d model). */
-#define FSV_MAX_KERNEL_STATS 16
+#define FSV_MAX_KERNEL_STATS 24
 typedef struct fsv_kernel_stat {
     char     name[24];
     double   ms;           /* summed HIP-event time of this kernel's launches on the context's stream */
@@ -294,6 +301,11 @@ int fsv_asm_last_stats(const fsv_ctx *ctx, fsv_asm_stats *out);
  * k_uniq_long indexed, and pairs beyond the chaining tile that k_chain_spill chained (their kernel times: the rows "k_uniq_long" and
  * "k_chain_spill" of fsv_asm_stats.kernels, outside the k_uniq / k_chain rows).  Both 0 after a call with full_lists = 0. */
 int fsv_asm_last_long_lists(const fsv_ctx *ctx, uint64_t *n_reads, uint64_t *n_pairs);
+/* deep_sets = 1, the last fsv_assemble_batch on this context, all rounds and chunks: windows that k_consensus_deep and junctions that
+ * k_bnd_consensus_deep redid (list entries: a window that both k_consensus and the redo after the haplotype partition set aside counts
+ * twice), and the largest number of inserted-base events one of them held (their kernel times: the rows "k_consensus_deep" and
+ * "k_bnd_consensus_deep" of fsv_asm_stats.kernels).  All 0 after a call with deep_sets = 0. */
+int fsv_asm_last_deep_windows(const fsv_ctx *ctx, uint64_t *n_windows, uint64_t *n_junctions, uint32_t *max_events);
 
 /* Test hook: after fsv_assemble_batch(...) with n_rounds = r, the corrected reads of the last round
  * can be fetched as ASCII (same order as the input reads). */

@@ -27,6 +27,9 @@ parser.add_argument('--partial-charge', action='store_true',
 parser.add_argument('--long-reads', action='store_true',
                     help="index every minimizer of a read and chain every anchor of a pair (fsv_asm_params.full_lists): noisy reads above ~32 kb "
                          "keep the seeds beyond their first 4 096 minimizers (extension; default off)")
+parser.add_argument('--deep-sets', action='store_true',
+                    help="keep every inserted-base vote of a consensus window (fsv_asm_params.deep_sets): read sets deeper than ~45 x per haplotype "
+                         "no longer drop votes beyond a window's 256 events and raise status bit 8 (extension; default off)")
 
 if __name__ == "__main__":
     args = parser.parse_args()
@@ -35,7 +38,7 @@ if __name__ == "__main__":
     if args.data_type != 0:
         logger.warning("CLR/ONT read sets go through the same GPU assembler (the reference uses Flye/Shasta there)")
     st = assembly(args.out_dir, args.num_cpus, args.num_threads, args.data_type, logger, device=args.device, kmer_table=args.kmer_table or args.kmer_filter,
-                  partial_charge=args.partial_charge, kmer_filter=args.kmer_filter, long_reads=args.long_reads)
+                  partial_charge=args.partial_charge, kmer_filter=args.kmer_filter, long_reads=args.long_reads, deep_sets=args.deep_sets)
     bad = {k: v for k, v in st.items() if v}
     if bad:
         logger.warning(f"read sets with a non-zero status: {bad}")
