@@ -2,7 +2,7 @@
 //
 // Replaces the process boundary `hifiasm -o <prefix> -t T <reads.fa>` + GFA read-back
 // (focalsv/3_assembly/run_assembly.py:15-44, post_assembly.py:79-95).  All base-level work runs in the
-// kernels of asm_kernels.h, k_consensus.h and k_sketch.h; the host only sizes buffers between stages and walks the (tiny, <= a few
+// kernels of asm_kernels.h and the stage files it includes; the host only sizes buffers between stages and walks the (tiny, <= a few
 // hundred nodes per set) overlap graph, which is host code in hifiasm as well (Overlaps.cpp).
 #include "asm_kernels.h"
 #include "k_kmer.h"
@@ -910,7 +910,7 @@ static int begin_round(fsv_ctx *ctx, AsmWs &W, Round &R)
     return FSV_OK;
 }
 
-// partial_charge = 1, after K6: the final verdict on every overlap the rescue kernels let through provisionally (asm_kernels.h,
+// partial_charge = 1, after K6: the final verdict on every overlap the rescue kernels let through provisionally (k_verify.h,
 // "partial charge").  Nothing here waits for the GPU; the counters are read when the chunk ends.
 static int charge_stage(fsv_ctx *ctx, AsmWs &W, const Round &R)
 {

@@ -18,7 +18,7 @@ struct ConsArgs {
     const uint32_t *pair_base;
     const uint32_t *gwin_off;    // n_reads + 1: first grid window of every read
     const uint32_t *gwin_read;   // n_gwin: read of every grid window
-    const uint4 *ovl_c;          // per ordered pair: {x_s, first window task, n_win | accepted << 31, -}  (k_rescue_accept)
+    const uint4 *ovl_c;          // per ordered pair: an OvlC (k_verify.h)
     const uint4 *gwin_tab;       // per grid window: {read, first pair slot of the read, overlaps of the read, window index}  (k_gwin_tab)
     const fsv_wtask *tasks;
     const fsv_wpath *paths;
@@ -60,17 +60,17 @@ __global__ __launch_bounds__(64) void k_read_dirty(const uint4 *__restrict__ ovl
     const uint32_t pbase = pair_base[s] + (r - r0) * (ns - 1), n_ovl = ns - 1;
     bool dirty = false;
     for (uint32_t oi = threadIdx.x; oi < n_ovl; oi += 64) {
-        const uint4 oc = ovl_c[pbase + oi];
-        if (!(oc.z >> 31)) continue;
-        const int n_win = (int)(oc.z & 0x7fffffffu);
+        const OvlC oc = OvlC::load(&ovl_c[pbase + oi]);
+        if (!oc.accepted()) continue;
+        const int n_win = oc.n_win();
         int prev_end = 0; bool prev_ok = false;
         for (int j = 0; j < n_win && !dirty; j++) {
-            const uint4 h0 = *reinterpret_cast<const uint4 *>(paths + (oc.y + (uint32_t)j));
-            const bool ok = (h0.w & 0xffu) == 1u;
+            const PathHead h0 = PathHead::load(paths + (oc.first_task() + (uint32_t)j));
+            const bool ok = h0.present();
             if (ok) {
-                if ((int16_t)(h0.z >> 16) != 0) dirty = true;
-                if (prev_ok && (int)h0.x - prev_end - 1 != 0) dirty = true;     // bases of y skipped, or used twice
-                prev_end = (int)h0.y;
+                if (h0.err() != 0) dirty = true;
+                if (prev_ok && h0.ry_start() - prev_end - 1 != 0) dirty = true;     // bases of y skipped, or used twice
+                prev_end = h0.ry_end();
             }
             prev_ok = ok;
         }
@@ -734,32 +734,32 @@ __device__ __forceinline__ void consensus_window(const ConsArgs &A, const uint32
     if (lane == 0) s_anydev = 0;
     __syncthreads();
     for (uint32_t oi = lane; oi < n_ovl; oi += 64) {
-        const uint4 oc = A.ovl_c[pbase + oi];
-        const int o_x_s = (int)oc.x, o_n_win = (int)(oc.z & 0x7fffffffu);
+        const OvlC oc = OvlC::load(&A.ovl_c[pbase + oi]);
+        const int o_x_s = oc.x_s(), o_n_win = oc.n_win();
         const int j = g - o_x_s / FSV_WINDOW;
-        if (!(oc.z >> 31) || j < 0 || j >= o_n_win) continue;
-        const uint32_t ti = oc.y + (uint32_t)j;
+        if (!oc.accepted() || j < 0 || j >= o_n_win) continue;
+        const uint32_t ti = oc.first_task() + (uint32_t)j;
         const fsv_wpath *P = A.paths + ti;
-        const uint4 h0 = *reinterpret_cast<const uint4 *>(P);                      // ry_start, ry_end, path_len|err, state|rev|pad
-        const uint2 h1 = *reinterpret_cast<const uint2 *>((const uint8_t *)P + 16); // y_word, y_len
+        const PathHead h0 = PathHead::load(P);
+        const PathY h1 = PathY::load(P);
         // In a read somebody deviates from (the only reads that get here) most paths carry deviations, so the 104 op bytes are
         // requested together with the header: waiting for the header first to learn whether the path is clean cost a second
         // memory round trip per overlap on the window's critical path
         uint2 pv[13];
         load_path_ops(P, pv);
         atomicAdd(&S.cover, 1u);       // get_available_interval (Correct.cpp:113): every accepted overlap that overlaps the window counts, matched there or not
-        if ((h0.w & 0xffu) != 1u) continue;
+        if (!h0.present()) continue;
         // a path at distance 0 is all matches: it only adds its coverage interval
-        const bool clean_path = (int16_t)(h0.z >> 16) == 0;
+        const bool clean_path = h0.err() == 0;
         const uint32_t nz = clean_path ? 0u : S.stage_path(lane, pv);
-        const int ry_start = (int)h0.x, plen = (int)(int16_t)(h0.z & 0xffffu);
-        const uint32_t y_word = h1.x; const int y_len = (int)h1.y, y_rev = (int)((h0.w >> 8) & 0xffu);
+        const int ry_start = h0.ry_start(), plen = h0.len();
+        const uint32_t y_word = h1.y_word(); const int y_len = h1.y_len(), y_rev = h0.y_rev();
         const int xs = max(gs, o_x_s) - gs;
         bool pend = false;
         if (j > 0 && A.junction_vote) {
-            const uint4 hp = *reinterpret_cast<const uint4 *>(A.paths + ti - 1);
-            if ((hp.w & 0xffu) == 1u) {
-                const int gap = ry_start - (int)hp.y - 1;
+            const PathHead hp = PathHead::load(A.paths + ti - 1);
+            if (hp.present()) {
+                const int gap = ry_start - hp.ry_end() - 1;
                 if (gap > 0 && xs == 0) {
                     pend = true;
                     if (gap <= FSV_INS_MAXLEN) {
@@ -948,14 +948,14 @@ __global__ __launch_bounds__(256) void k_bcig_tasks(BcigArgs A)
     // a clean read (most reads from the second round on): every path at distance 0, every junction met -- its path records (a 128-byte
     // line each for 16 bytes of header) are not even looked at
     if (!A.read_dirty[A.pair_read[t0.ovl]]) return;
-    const uint4 h0 = *reinterpret_cast<const uint4 *>(A.paths + ti), h1 = *reinterpret_cast<const uint4 *>(A.paths + ti + 1);
-    if ((h0.w & 0xffu) != 1u || (h1.w & 0xffu) != 1u) return;     // (a path only exists for a matched window of an accepted overlap)
-    const int y_distance = (int)h1.x - (int)h0.y - 1;
+    const PathHead h0 = PathHead::load(A.paths + ti), h1 = PathHead::load(A.paths + ti + 1);
+    if (!h0.present() || !h1.present()) return;     // (a path only exists for a matched window of an accepted overlap)
+    const int y_distance = h1.ry_start() - h0.ry_end() - 1;
     // nothing to re-align where the two alignments meet and neither shows an error within ten columns of the junction
-    if (y_distance == 0 && !((h0.w >> 16) & 2u) && !((h1.w >> 16) & 1u)) return;
+    if (y_distance == 0 && !h0.dev_tail() && !h1.dev_head()) return;
     const fsv_wtask t1 = A.tasks[ti + 1];
     if (t1.ovl != t0.ovl) return;                           // the overlap's last window
-    int y_start = (int)h0.y, x_start = t0.x_start + (int)t0.x_len - 1;
+    int y_start = h0.ry_end(), x_start = t0.x_start + (int)t0.x_len - 1;
     const int leftLen = min(min(x_start - t0.x_start, y_start), FSV_BC_SIDE);
     const int rightLen = min(min(t1.x_start + (int)t1.x_len - x_start, t0.y_len - y_start), FSV_BC_SIDE);
     const int xLen = leftLen + rightLen;
@@ -983,14 +983,15 @@ __global__ __launch_bounds__(256) void k_bcig_accept(BcigArgs A)
     const fsv_wres r = A.res2[slot];
     const uint32_t ti = w.win;
     const fsv_wpath *PB = A.paths2 + slot, *P0 = A.paths + ti, *P1 = A.paths + ti + 1;
-    const uint4 hb = *reinterpret_cast<const uint4 *>(PB);
-    if (r.err < 0 || (hb.w & 0xffu) != 1u) return;
+    if (r.err < 0) return;      // (before the record is asked for: K6 left none)
+    const PathHead hb = PathHead::load(PB);
+    if (!hb.present()) return;
     const int xLen = w.x_len, thr = w.k;
     if (xLen + 2 * thr - r.extra_begin - r.extra_end < xLen) return;      // o_len < xLen
     const fsv_wtask t0 = A.tasks[ti], t1 = A.tasks[ti + 1];
-    const uint4 h0 = *reinterpret_cast<const uint4 *>(P0), h1 = *reinterpret_cast<const uint4 *>(P1);
+    const PathHead h0 = PathHead::load(P0), h1 = PathHead::load(P1);
     const int x_end0 = t0.x_start + (int)t0.x_len - 1, leftLen = x_end0 - w.x_start, rightLen = xLen - leftLen;
-    int y_distance = (int)h1.x - (int)h0.y - 1;
+    int y_distance = h1.ry_start() - h0.ry_end() - 1;
     if (y_distance < 0) y_distance = -y_distance;
     int L = FSV_BC_USELESS, R = FSV_BC_USELESS;
     const uint32_t first_ti = ti - t0.win;                  // (window tasks carry their index inside the overlap)
@@ -1002,8 +1003,8 @@ __global__ __launch_bounds__(256) void k_bcig_accept(BcigArgs A)
     }
     (void)first_ti;
     if (leftLen <= L || rightLen <= R) return;
-    const int plb = (int)(int16_t)(hb.z & 0xffffu), eb = (int)(int16_t)(hb.z >> 16);
-    const int pl0 = (int)(int16_t)(h0.z & 0xffffu), e0 = (int)(int16_t)(h0.z >> 16), pl1 = (int)(int16_t)(h1.z & 0xffffu), e1 = (int)(int16_t)(h1.z >> 16);
+    const int plb = hb.len(), eb = hb.err();
+    const int pl0 = h0.len(), e0 = h0.err(), pl1 = h1.len(), e1 = h1.err();
     const int m_err = scan_ops_interval(PB, plb, eb, L, xLen - R - 1);
     const int b_err = scan_ops(P0, pl0, e0, leftLen - L, 1), f_err = scan_ops(P1, pl1, e1, rightLen - R, 0);
     if (f_err + b_err + y_distance + 1 < m_err) return;
@@ -1015,10 +1016,10 @@ __global__ __launch_bounds__(256) void k_bcig_accept(BcigArgs A)
         // columns of the junction cigar that stand for window 0: [L, leftLen] (its last column included); for window 1:
         // [leftLen + 1, leftLen + 1 + (rightLen - 1 - R) - 1] (markSNP_advance's intervals, restated in snp_sites_window)
         OpReader RB(PB), R0(P0), R1(P1);
-        int pb = 0, xb = 0, yb = (int)hb.x;
+        int pb = 0, xb = 0, yb = hb.ry_start();
         // window 0 from its column x0c on: skip its ops in front of that column
         const int x0c = (w.x_start + L) - t0.x_start;
-        int p0 = 0, x0 = 0, y0 = (int)h0.x;
+        int p0 = 0, x0 = 0, y0 = h0.ry_start();
         if (e0 != 0) { while (p0 < pl0 && x0 < x0c) { const uint32_t op = R0.get(p0++); if (op == 2u) y0++; else { x0++; if (op != 3u) y0++; } } }
         else { x0 = x0c; y0 += x0c; p0 = x0c; }
         if (eb != 0) { while (pb < plb && xb < L) { const uint32_t op = RB.get(pb++); if (op == 2u) yb++; else { xb++; if (op != 3u) yb++; } } }
@@ -1038,7 +1039,7 @@ __global__ __launch_bounds__(256) void k_bcig_accept(BcigArgs A)
             if (ob == 1u || ow == 1u) mm0 = true;
         }
         // window 1: junction columns leftLen + 1 .. leftLen + (rightLen - 1 - R)
-        int p1 = 0, y1 = (int)h1.x;
+        int p1 = 0, y1 = h1.ry_start();
         const int hi1 = leftLen + (rightLen - 1 - R);
         for (; xb <= hi1; xb++) {
             uint32_t ob, ow; int ybp, ywp;
@@ -1120,28 +1121,27 @@ __device__ __forceinline__ void snp_sites_window(const ConsArgs &A, const uint32
     const uint32_t vstride = (n_ovl + 3u) & ~3u;
     for (int pass = 0; pass < 2; pass++) {
         for (uint32_t oi = lane; oi < n_ovl; oi += 64) {
-            const uint4 oc = A.ovl_c[pbase + oi];
-            const int o_x_s = (int)oc.x, o_n_win = (int)(oc.z & 0x7fffffffu);
+            const OvlC oc = OvlC::load(&A.ovl_c[pbase + oi]);
+            const int o_x_s = oc.x_s(), o_n_win = oc.n_win();
             const int j = g - o_x_s / FSV_WINDOW;
-            if (!(oc.z >> 31) || j < 0 || j >= o_n_win) continue;
-            const uint32_t ti = oc.y + (uint32_t)j;
+            if (!oc.accepted() || j < 0 || j >= o_n_win) continue;
+            const uint32_t ti = oc.first_task() + (uint32_t)j;
             const fsv_wpath *P = A.paths + ti;
-            const uint4 h0 = *reinterpret_cast<const uint4 *>(P);
-            if ((h0.w & 0xffu) != 1u) continue;
+            if (!PathHead::load(P).present()) continue;
             const int xs = max(gs, o_x_s) - gs;
             if (pass == 0) atomicAdd(&T.cover, 1u);
             // What the overlap shows at the columns [lo, hi] (counted from the cigar's first column, which is column x0 of the read)
             // of one cigar.  pass 0: mismatches and x bases without a partner are tallied (markSNP_detail, Correct.cpp:4998);
             // pass 1: the kept sites get their evidence (addSNPtohaplotype_details :5247).  Returns the cigar's x columns.
             auto walk = [&](const fsv_wpath *Q, int x0, int lo, int hi) -> int {
-                const uint4 q0 = *reinterpret_cast<const uint4 *>(Q);
-                const int plen = (int)(int16_t)(q0.z & 0xffffu), ry0 = (int)q0.x, col0 = x0 - gs;
-                if ((int16_t)(q0.z >> 16) == 0) {          // distance 0: all matches, the record carries no ops
+                const PathHead q0 = PathHead::load(Q);
+                const int plen = q0.len(), ry0 = q0.ry_start(), col0 = x0 - gs;
+                if (q0.err() == 0) {          // distance 0: all matches, the record carries no ops
                     if (pass == 1) for (int xi = max(lo, -col0); xi <= min(hi, plen - 1) && col0 + xi < glen; xi++) if (s_alt[col0 + xi]) S.vec[s_vbase + (uint32_t)s_sidx[col0 + xi] * vstride + oi] = 0;
                     return plen;
                 }
-                const uint2 q1 = *reinterpret_cast<const uint2 *>((const uint8_t *)Q + 16);
-                const uint32_t y_word = q1.x; const int y_len = (int)q1.y, y_rev = (int)((q0.w >> 8) & 0xffu);
+                const PathY q1 = PathY::load(Q);
+                const uint32_t y_word = q1.y_word(); const int y_len = q1.y_len(), y_rev = q0.y_rev();
                 uint2 pv[13];
                 load_path_ops(Q, pv);
                 T.stage_path(lane, pv);
@@ -1310,7 +1310,7 @@ __global__ __launch_bounds__(64) void k_hap_partition(ConsArgs A, SiteArgs S, fs
     if (nS > FSV_SITE_READ_CAP) { if (lane == 0) atomicOr(&A.warn[r], (uint32_t)FSV_W_SITES); return; }
     // informative, not informative, informative again: the overlap is set aside
     for (uint32_t i = lane; i < n_ovl; i += 64) {
-        if (!(ovl_c[pbase + i].z >> 31)) continue;
+        if (!OvlC::load(&ovl_c[pbase + i]).accepted()) continue;
         int st = -1;
         for (int j = 0; j < nS; j++) {
             const int8_t v = S.vec[s_voff[j] + i];
@@ -1322,7 +1322,7 @@ __global__ __launch_bounds__(64) void k_hap_partition(ConsArgs A, SiteArgs S, fs
         if (st == 3) {
             for (int j = 0; j < nS; j++) S.vec[s_voff[j] + i] = 2;
             ovl[pbase + i].is_match = 4;
-            ovl_c[pbase + i].z &= 0x7fffffffu;
+            OvlC::clear_accepted(&ovl_c[pbase + i]);
             s_redo = 1u;
         }
     }
@@ -1402,7 +1402,7 @@ __global__ __launch_bounds__(64) void k_hap_partition(ConsArgs A, SiteArgs S, fs
                         for (uint32_t o = lane; o < n_ovl; o += 64) {
                             int8_t rv = -1;
                             for (int k = 0; k < plen && rv == -1; k++) { const int8_t v = S.vec[s_voff[s_buf[k]] + o]; if (v == 0 || v == 1) rv = v; }
-                            if (rv == 1 && (ovl_c[pbase + o].z >> 31)) { ovl[pbase + o].is_match = 2; ovl_c[pbase + o].z &= 0x7fffffffu; s_redo = 1u; }
+                            if (rv == 1 && OvlC::load(&ovl_c[pbase + o]).accepted()) { ovl[pbase + o].is_match = 2; OvlC::clear_accepted(&ovl_c[pbase + o]); s_redo = 1u; }
                         }
                     n_groups++;
                 }
@@ -1463,18 +1463,20 @@ __global__ __launch_bounds__(256) void k_bnd_tasks(BndArgs A)
     // the tests are grouped so that the loads they need are in flight together: one test per load is one memory round trip per test
     const uint32_t p = t.ovl;
     const uint32_t r = A.pair_read[p];
-    const uint4 oc = A.ovl_c[p];
-    const uint4 h0 = *reinterpret_cast<const uint4 *>(A.paths + ti);
     const uint32_t dirty = A.read_dirty[r], gwo = A.gwin_off[r];
-    // a clean read: every overlap matches it base for base, every junction alignment has distance 0
-    if (!(dirty && (oc.z >> 31) && (h0.w & 0xffu) == 1u)) return;
+    // a clean read: every overlap matches it base for base, every junction alignment has distance 0 -- its overlap record and its path
+    // header (a 128-byte line for 16 bytes) are not asked for
+    if (!dirty) return;
+    const OvlC oc = OvlC::load(&A.ovl_c[p]);
+    const PathHead h0 = PathHead::load(A.paths + ti);
+    if (!(oc.accepted() && h0.present())) return;
     const uint32_t gw = gwo + (uint32_t)(t.x_start / FSV_WINDOW);
     const uint32_t cov = A.cov3[gw], cwl = A.cwin_len[gw];
     const int LB = (int)A.lb[gw];
     if (!cov || LB == 0) return;
     const int len_now = LB + (int)cwl;
     const int cws = max(0, LB - FSV_BND_HALF), cwe = min(len_now - 1, LB + FSV_BND_HALF - 1), blen = cwe - cws + 1;
-    const int y_start = (int)h0.x - FSV_BND_HALF;
+    const int y_start = h0.ry_start() - FSV_BND_HALF;
     if (y_start < 0 || blen < 1) return;
     // about half of the partner reads match the first pass's result base for base on the predicted diagonal (K5 would report distance 0
     // ending on that diagonal, K6 an all-match path): such an alignment only counts towards the junction's coverage
@@ -1561,27 +1563,27 @@ __device__ __forceinline__ void bnd_junction(const ConsArgs &A, const BndArgs &B
     if constexpr (EV::deep) { if (lane == 0) S.ev = *slab; }
     __syncthreads();
     for (uint32_t oi = lane; oi < n_ovl; oi += 64) {
-        const uint4 oc = A.ovl_c[pbase + oi];
-        const int o_x_s = (int)oc.x, o_n_win = (int)(oc.z & 0x7fffffffu);
+        const OvlC oc = OvlC::load(&A.ovl_c[pbase + oi]);
+        const int o_x_s = oc.x_s(), o_n_win = oc.n_win();
         const int j = g - o_x_s / FSV_WINDOW;
-        if (!(oc.z >> 31) || j < 0 || j >= o_n_win || o_x_s > gs) continue;
-        const int32_t slot = B.idx2[oc.y + (uint32_t)j];
+        if (!oc.accepted() || j < 0 || j >= o_n_win || o_x_s > gs) continue;
+        const int32_t slot = B.idx2[oc.first_task() + (uint32_t)j];
         if (slot == -2) { atomicAdd(&S.cover, 1u); atomicAdd(&S.cov[0], 1); atomicAdd(&S.cov[blen], -1); continue; }   // matches base for base
         if (slot < 0) continue;
         const fsv_wpath *P = paths2 + slot;
-        const uint4 h0 = *reinterpret_cast<const uint4 *>(P);
-        if ((h0.w & 0xffu) != 1u) continue;
-        const uint2 h1 = *reinterpret_cast<const uint2 *>((const uint8_t *)P + 16);
-        const int perr = (int)(int16_t)(h0.z >> 16);
+        const PathHead h0 = PathHead::load(P);
+        if (!h0.present()) continue;
+        const PathY h1 = PathY::load(P);
+        const int perr = h0.err();
         atomicAdd(&S.cover, 1u);
-        const int ry_start = (int)h0.x, plen = (int)(int16_t)(h0.z & 0xffffu);
+        const int ry_start = h0.ry_start(), plen = h0.len();
         int n2 = 0;
         if (perr != 0) {
             atomicAdd(&S.terr, (uint32_t)perr);
             uint2 pv[13];
             load_path_ops(P, pv);
             const uint32_t nz = S.stage_path(lane, pv);
-            n2 = cons_walk(S, S.path[lane], nz, plen, 0, blen, false, A.store, h1.x, (int)h1.y, (int)((h0.w >> 8) & 0xffu), ry_start);
+            n2 = cons_walk(S, S.path[lane], nz, plen, 0, blen, false, A.store, h1.y_word(), h1.y_len(), h0.y_rev(), ry_start);
         }
         atomicAdd(&S.cov[0], 1);
         atomicAdd(&S.cov[plen - n2], -1);

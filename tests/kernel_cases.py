@@ -50,7 +50,7 @@ MAIN_RATES = (0.0, 0.003, 0.01, 0.03, 0.06)
 WIDE_RATES = (0.02, 0.1, 0.2, 0.25)
 WIDE_KS = (40, 63, 80, 93, 95)
 K6_CLASSES = ("gap-free", "err 1", "err 2", "err 3", "k<=15 err 4..7", "k<=15 err>7", "16<=k<=31 err>3", "k>31")
-# the kernel that settles each class (asm_kernels.h: k_path_fast sorts the windows, one walk kernel per list)
+# the kernel that settles each class (k_path.h: k_path_fast sorts the windows, one walk kernel per list)
 K6_KERNEL = {"gap-free": "k_path_fast/path_gapfree", "err 1": "k_path_fr<1>", "err 2": "k_path_fr<2>", "err 3": "k_path_fr<3>",
              "k<=15 err 4..7": "k_path_sb", "k<=15 err>7": "k_path_dp<uint32_t>", "16<=k<=31 err>3": "k_path_dp<uint64_t>",
              "k>31": "k_path_wide"}
@@ -87,7 +87,7 @@ def padded_window(y_read, y_rev, y_start, x_len, k):
 
 
 def k6_class(k, err, gapfree):
-    """the list k_path_fast puts a hit on (asm_kernels.h), from the oracle's numbers alone"""
+    """the list k_path_fast puts a hit on (k_path.h), from the oracle's numbers alone"""
     if gapfree:
         return "gap-free"
     if k > 31:
