@@ -97,6 +97,19 @@ class AlnTags(C.Structure):
                 ("rec_status", C.c_void_p), ("ms", C.c_double)]
 
 
+class RefStats(C.Structure):
+    """fsv_ref_stats"""
+    _fields_ = [(n, C.c_uint64) for n in ("tiles", "owned", "dropped_n", "keys", "keys_above", "stored", "slots", "max_count")] + [("ms", C.c_double)]
+
+
+class ContigMapq(C.Structure):
+    """struct fsv_contig_mapq"""
+    _fields_ = [(n, C.c_void_p) for n in ("f1", "f2", "m", "cutoff", "thin", "flags", "rec_status")] + [("ms", C.c_double)]
+
+
+MQ_TRUNC = 1   # FSV_MQ_TRUNC
+
+
 class BamOut(C.Structure):
     """fsv_bam_out"""
     _fields_ = [("n_refs", C.c_uint32), ("ref_name", C.POINTER(C.c_char_p)), ("ref_len", C.c_void_p), ("header_text", C.c_char_p),
@@ -190,6 +203,12 @@ def load():
         "fsv_align_batch": (C.c_int, [vp, vp, vp, C.c_uint32, vp, vp, vp, C.c_uint32, C.POINTER(AlnParams), C.POINTER(Alns)]),
         "fsv_aln_last_stats": (C.c_int, [vp, C.POINTER(AlnStats)]),
         "fsv_aln_tags": (C.c_int, [vp, vp, vp, C.c_uint32, vp, vp, vp, C.c_uint32, C.POINTER(Alns), C.POINTER(AlnTags)]),
+        "fsv_ref_index_build": (C.c_int, [vp, vp, C.c_uint64, C.c_int32, C.c_int32, C.c_int32]),
+        "fsv_ref_index_stats": (C.c_int, [vp, C.POINTER(RefStats)]),
+        "fsv_ref_index_drop": (C.c_int, [vp]),
+        "fsv_ref_index_lookup": (C.c_int, [vp, vp, C.c_uint32, vp, vp, vp, C.c_uint64]),
+        "fsv_mapq_of": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32]),
+        "fsv_contig_mapq": (C.c_int, [vp, vp, vp, C.c_uint32, vp, vp, C.c_uint32, C.POINTER(Alns), C.POINTER(AlnParams), C.POINTER(ContigMapq)]),
         "fsv_bam_write": (C.c_int, [C.c_char_p, C.POINTER(BamOut), C.c_int]),
         "fsv_bam_open": (C.c_int, [C.c_char_p, C.POINTER(vp)]),
         "fsv_bam_close": (None, [vp]),
@@ -295,6 +314,12 @@ def kmer_peaks(hist, start_cnt=5):
     if hom < -1:
         raise FsvError(hom, "fsv_kmer_peaks")
     return hom, het.value, low.value, mx.value
+
+
+def mapq_of(f1, f2, m):
+    """fsv_mapq_of (host only, no GPU): the mapping quality of Li 2018, section 2.1.4, from the best chain score at a record's own locus, the
+    best elsewhere and the own chain's anchors"""
+    return int(load().fsv_mapq_of(int(f1), int(f2), int(m)))
 
 
 def partial_charge(n, al0, er0, al1, er1, terr):
@@ -687,6 +712,64 @@ class Context:
             ms = out.ms
         del keep
         return nm[:n].copy(), [cs[int(off[i]):int(off[i + 1])].tobytes() for i in range(n)], status[:n].copy(), ms
+
+    # chromosome-level mapping quality (opt-in) ------------------------------------
+    def ref_index(self, seq, k=19, w=19, max_occ=50):
+        """fsv_ref_index_build: the chromosome's minimizer index on this context (it replaces an earlier one) -> its statistics as a dict"""
+        b = seq.encode() if isinstance(seq, str) else seq
+        a = np.frombuffer(b, dtype=np.uint8) if not isinstance(b, np.ndarray) else np.ascontiguousarray(b, dtype=np.uint8)
+        self.check(self._lib.fsv_ref_index_build(self._h, _ptr(a) if len(a) else None, len(a), int(k), int(w), int(max_occ)), "fsv_ref_index_build")
+        return self.ref_index_stats()
+
+    def ref_index_stats(self):
+        st = RefStats()
+        self.check(self._lib.fsv_ref_index_stats(self._h, C.byref(st)), "fsv_ref_index_stats")
+        return {n: getattr(st, n) for n, _ in RefStats._fields_}
+
+    def ref_index_drop(self):
+        self.check(self._lib.fsv_ref_index_drop(self._h), "fsv_ref_index_drop")
+
+    def ref_index_lookup(self, hashes):
+        """fsv_ref_index_lookup -> (count uint32[n], off uint64[n + 1], occ uint32[]: pos | rev << 31, ascending position per hash; a hash
+        whose count is above the index's max_occ has its count and no occurrences)"""
+        h = np.ascontiguousarray(hashes, dtype=np.uint64)
+        n = len(h)
+        cnt = np.zeros(max(1, n), dtype=np.uint32)
+        off = np.zeros(n + 1, dtype=np.uint64)
+        cap = 64 * n + 1      # max_occ <= 64
+        occ = np.zeros(cap, dtype=np.uint32)
+        self.check(self._lib.fsv_ref_index_lookup(self._h, _ptr(h) if n else None, n, _ptr(cnt), _ptr(off), _ptr(occ), cap), "fsv_ref_index_lookup")
+        return cnt[:n].copy(), off, occ[: int(off[n])].copy()
+
+    def contig_mapq(self, rec, cigar, ref_origin, contigs=None, contig_ref=None, n_contigs=None, params=None):
+        """fsv_contig_mapq on the records of align_batch.  ref_origin[r]: chromosome position of window r's first base.  contigs / contig_ref
+        as align_batch takes them, or contigs = None with n_contigs: the contigs the last align_batch left on the device.
+        -> (rec with mapq set, dict of int32 arrays f1 f2 m cutoff thin flags rec_status, and ms)"""
+        rec = np.ascontiguousarray(rec, dtype=ALN_REC_DTYPE).copy()
+        cigar = np.ascontiguousarray(cigar, dtype=np.uint32)
+        n = len(rec)
+        cg = cigar if len(cigar) else np.zeros(1, np.uint32)
+        alns = Alns(_ptr(rec).value if n else None, n, n, _ptr(cg).value, len(cigar), len(cigar), None)
+        origin = np.ascontiguousarray(ref_origin, dtype=np.int64)
+        if contigs is None:
+            args = (None, None, int(n_contigs), None)
+            keep = ()
+        else:
+            coff = np.zeros(len(contigs) + 1, dtype=np.uint64)
+            np.cumsum([len(c) for c in contigs], out=coff[1:])
+            cseq = np.frombuffer(b"".join(contigs) + b"\0", dtype=np.uint8)
+            cref = np.ascontiguousarray(contig_ref, dtype=np.uint32)
+            keep = (coff, cseq, cref)
+            args = (_ptr(cseq), _ptr(coff), len(contigs), _ptr(cref))
+        names = ("f1", "f2", "m", "cutoff", "thin", "flags", "rec_status")
+        arr = {k: np.zeros(max(1, n), dtype=np.int32) for k in names}
+        out = ContigMapq(*[_ptr(arr[k]).value for k in names], 0.0)
+        p = params if params is not None else self.default_aln_params()
+        self.check(self._lib.fsv_contig_mapq(self._h, *args, _ptr(origin), len(origin), C.byref(alns), C.byref(p), C.byref(out)), "fsv_contig_mapq")
+        del keep
+        res = {k: arr[k][:n].copy() for k in names}
+        res["ms"] = out.ms
+        return rec, res
 
     def aln_stats(self):
         st = AlnStats()

@@ -11,8 +11,10 @@
 //   k_nw                dual-affine global DP of one event on anti-diagonals (one workgroup per event), the
 //                       recurrence / tie rules / backtrack of the in-tree ksw2 (ksw2_extz2_sse.c:171-196, ksw2.h:115-150)
 //   k_aln_tags          fsv_aln_tags: NM and the cs difference string of finished records (what minimap2's --cs adds), count / scan / emit
-// The kernels are in k_aln.h; this file is the host path.
+//   k_ref_* / k_place   fsv_ref_index_* / fsv_contig_mapq: a chromosome-wide minimizer index and the records' mapping quality from it (opt-in)
+// The kernels are in k_aln.h and k_place.h; this file is the host path, with aln_mapq.h (included at the end) for the last line above.
 #include "k_aln.h"
+#include "k_place.h"
 #include <algorithm>
 #include <memory>
 #include <cstdio>
@@ -865,3 +867,5 @@ extern "C" int fsv_aln_tags(fsv_ctx *ctx, const char *contig_seq, const uint64_t
 {
     FSV_GUARD(ctx, aln_tags_impl(ctx, contig_seq, contig_off, n_contigs, contig_ref, ref_seq, ref_off, n_refs, alns, out));
 }
+
+#include "aln_mapq.h"

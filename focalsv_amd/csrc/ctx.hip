@@ -61,6 +61,7 @@ void fsv_ctx_destroy(fsv_ctx *ctx)
     if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
     if (ctx->asm_ws_free) ctx->asm_ws_free(ctx);
     if (ctx->aln_ws_free) ctx->aln_ws_free(ctx);
+    if (ctx->ref_ws && ctx->ref_ws_free) ctx->ref_ws_free(ctx);
     if (ctx->own_stream && ctx->stream) {
         (void)hipSetDevice(ctx->device);
         (void)hipStreamSynchronize(ctx->stream);

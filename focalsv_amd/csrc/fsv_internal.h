@@ -27,6 +27,8 @@ struct fsv_ctx {
     std::vector<uint64_t> last_contig_off;
     void *aln_ws = nullptr;                 // alignment workspace (aln.hip)
     void (*aln_ws_free)(fsv_ctx *) = nullptr;
+    void *ref_ws = nullptr;                 // chromosome index and the workspace of fsv_contig_mapq (aln_mapq.h), or nothing
+    void (*ref_ws_free)(fsv_ctx *) = nullptr;
 };
 
 #define FSV_HIP(ctx, call)                                                              \

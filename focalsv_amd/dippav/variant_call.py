@@ -77,13 +77,17 @@ def call_chromosome(records: Sequence[S.AlignedSegment], chrom: str, ref_seq, co
 
 def dippav_variant_call(data_type, read_bam_file, reference_path, hp1_contig_path, hp2_contig_path, output_dir, chr_num,
                         header_file=None, n_thread=10, mem_per_thread='1G', *, regions=None, read_records=None,
-                        ctx: Optional[_lib.Context] = None, device: int = 0, contig_bam: bool = False):
+                        ctx: Optional[_lib.Context] = None, device: int = 0, contig_bam: bool = False, chrom_mapq: bool = False):
     """Drop-in for DipPAV_variant_call.dippav_variant_call.  Extra keyword-only arguments:
       regions       {contig_name: (chrom, win_start, win_end)} when the FASTA headers carry no region tag
       read_records  AlignedSegment-like records of the chromosome's reads, instead of read_bam_file (which is read with the
                     library's own BAM reader, focalsv_amd.bam, and its CIGARs scanned on the GPU)
       contig_bam    also write <output_dir>/assemblies.sorted.bam and .bai: the contigs' alignment records with NM / cs / SA tags
                     (focalsv_amd.bam.write_contig_bam).  Off: nothing is launched, allocated or written for it
+      chrom_mapq    give every contig record its mapping quality on the whole chromosome (fsv_ref_index_build on the chromosome's
+                    sequence, fsv_contig_mapq on the records) in place of the constant 60: a contig from a segmental duplication then
+                    fails the reference's mapq >= 50 tests as it does behind minimap2, and signature/chr*_cigar.txt, the contig BAM and
+                    TIG_MAPQ show the value.  Off: nothing is launched, allocated or written for it
     """
     assert data_type in ('CCS', 'CLR', 'ONT')
     logger = logging.getLogger(" ")
@@ -123,6 +127,18 @@ def dippav_variant_call(data_type, read_bam_file, reference_path, hp1_contig_pat
     try:
         keep = [i for i, w in enumerate(wins) if w[0] == chrom and seqs[i]]
         rec, cigar, status = ctx.align_batch([seqs[i].encode() for i in keep], [win_index[wins[i]] for i in keep], refs)
+        if chrom_mapq and keep:
+            ctx.ref_index(chrom_seq.encode())
+            try:
+                rec, _ = ctx.contig_mapq(rec, cigar, ref_start, n_contigs=len(keep))   # on the contigs align_batch left on the device
+            finally:
+                ctx.ref_index_drop()
+            primary = {}
+            for r in rec:
+                primary.setdefault(int(r["contig"]), int(r["mapq"]))
+            for k, q in sorted(primary.items()):
+                if q < 50:
+                    logging.getLogger("focalsv_amd").warning("%s: mapping quality %d on %s (below 50): its SVs are not called", names[keep[k]], q, chrom)
         tags = ctx.aln_tags(rec, cigar, n_contigs=len(keep), n_refs=len(refs))[:2] if contig_bam and keep else None   # on the device-resident sequences
         for i, st in zip(keep, status):      # a refused contig yields no record: say so instead of losing its SVs silently
             if int(st) < 0:

@@ -521,6 +521,55 @@ struct fsv_aln_tags {     /* (no typedef: the call has the name, as stat() has b
 int fsv_aln_tags(fsv_ctx *ctx, const char *contig_seq, const uint64_t *contig_off, uint32_t n_contigs, const uint32_t *contig_ref,
                  const char *ref_seq, const uint64_t *ref_off, uint32_t n_refs, const fsv_alns *alns, struct fsv_aln_tags *out);
 
+/* ---- chromosome-level mapping quality of the contig records (opt-in, nothing runs or is allocated unless these are called) ----
+ * fsv_align_batch aligns a contig to the window of its own region and stamps mapq 60.  The reference pipeline aligns to the whole
+ * chromosome (minimap2 -x asm5) and drops records below mapq 50 (extract_contig_signature_CCS.py:679-680).  These calls give a record
+ * the mapping quality of minimap2's published formula (Li 2018, Bioinformatics 34:3094, section 2.1.4) from this library's own chaining:
+ * f1 the best chain score of the record's seeds at its own locus, f2 the best anywhere else on the chromosome, m the anchors of the
+ * former.  Pinned to that formula and to tests/mapq_model.py, not to a minimap2 run; a paralog on another chromosome is not seen.
+ *
+ * The index (one per context; a new build replaces it, fsv_ref_index_drop or fsv_ctx_destroy frees it): the chromosome packed as one
+ * sequence (an N holds a base hashed from its position, as in a window), cut into tiles that own FSV_REF_TILE k-mer end positions each
+ * and are sketched with 64 bases of context on either side, HPC off; a minimizer is kept by the tile that owns its end, unless its k
+ * bases cover an N.  The kept ones fill one open-addressed table by hash: a key's count, and for a count <= max_occ its occurrences
+ * pos | rev << 31 in ascending position.  k odd, 1 <= k <= 31, 1 <= w <= 32, 1 <= max_occ <= 64, 0 < len < 2^31: FSV_EINVAL otherwise. */
+#define FSV_REF_TILE 65536
+typedef struct fsv_ref_stats {
+    uint64_t tiles, owned, dropped_n;       /* minimizers whose end a tile owns; of those, dropped for an N */
+    uint64_t keys, keys_above, stored;      /* distinct hashes; those with count > max_occ; occurrences stored */
+    uint64_t slots, max_count;              /* of the table: a power of two, at least twice owned - dropped_n; the largest count */
+    double ms;                              /* summed kernel time of the build */
+} fsv_ref_stats;
+int fsv_ref_index_build(fsv_ctx *ctx, const char *seq, uint64_t len, int32_t k, int32_t w, int32_t max_occ);
+int fsv_ref_index_stats(const fsv_ctx *ctx, fsv_ref_stats *out);     /* FSV_EINVAL without an index */
+int fsv_ref_index_drop(fsv_ctx *ctx);
+/* stage hook: count_out[i] the count of hashes[i] (0: not a key), its occurrences at occ_out[off_out[i] .. off_out[i + 1]) -- none for a
+ * count above max_occ.  off_out: n + 1.  FSV_ECAP when cap is too small (off_out[n] says how many are needed), FSV_EINVAL without an index. */
+int fsv_ref_index_lookup(fsv_ctx *ctx, const uint64_t *hashes, uint32_t n, uint32_t *count_out, uint64_t *off_out, uint32_t *occ_out, uint64_t cap);
+
+#define FSV_MQ_TRUNC 1      /* flags: the occurrence cutoff is below max_occ (a class of hits would not fit the chain's anchor array) */
+struct fsv_contig_mapq {    /* all host, n_rec entries each */
+    int32_t *f1, *f2, *m;   /* best chain score at the record's own locus, best elsewhere (0: no hit elsewhere), anchors of the former */
+    int32_t *cutoff, *thin; /* c*: seeds with a higher count are ignored; t: every t-th seed by hash is used (1: all) */
+    int32_t *flags;         /* FSV_MQ_* */
+    int32_t *rec_status;    /* 0, or FSV_EINVAL for a record that does not fit its sequences (mapq 0, nothing else set) */
+    double   ms;            /* out: summed kernel time */
+};
+/* 0 when f1 <= 0, m <= 0 or f2 >= f1; else (int)(40 (1 - f2 / f1) min(1, m / 10) ln f1) in double arithmetic, clamped to [0, 60].  Host only. */
+int32_t fsv_mapq_of(int32_t f1, int32_t f2, int32_t m);
+/* Writes alns->rec[i].mapq.  alns: records as fsv_align_batch returned them; ref_origin[r]: the chromosome position of window r's first
+ * base.  Every record is checked on the host as fsv_aln_tags checks it, the chromosome taking the window's place: its query-consuming
+ * ops must sum to the contig's length, ref_start plus its reference-consuming ops must equal ref_end, origin + ref_end must not exceed
+ * the chromosome, and 0 <= q_start <= q_end <= the contig's length; a record that fails has rec_status FSV_EINVAL and mapq 0 and reaches
+ * no kernel.  contig_seq == NULL: the contigs the last fsv_align_batch left on the device (FSV_EINVAL when there are none or n_contigs /
+ * n_refs differ from that call's; contig_off and contig_ref are then not read).  Every contig is sketched once with the index's (w, k); one workgroup per record then takes the minimizers whose end
+ * lies in the record's interval of the forward contig (every t-th by hash beyond 4 096), splits their hits into own locus (relative strand
+ * = rev, position inside [origin + ref_start, origin + ref_end)), elsewhere forward and elsewhere reverse, finds the largest occurrence
+ * count c* <= max_occ up to which every class has at most 8 192 hits, and chains each class (anchors sorted by chromosome, then contig
+ * coordinate; params: k, max_gap, look-back 64; the chain DP of fsv_align_batch). */
+int fsv_contig_mapq(fsv_ctx *ctx, const char *contig_seq, const uint64_t *contig_off, uint32_t n_contigs, const uint32_t *contig_ref,
+                    const int64_t *ref_origin, uint32_t n_refs, fsv_alns *alns, const fsv_aln_params *params, struct fsv_contig_mapq *out);
+
 /* ---- BAM output: a coordinate-sorted BAM and its .bai, host only (no GPU, like the rest of fsv_bam_*) -------------------------
  * Struct of arrays in the reader's style.  The writer sorts the records stably by (ref_id, pos), unmapped ones (ref_id -1, pos -1,
  * flag & 4, no CIGAR) last in input order; encodes them as SAM v1 section 4.2 (bin by reg2bin, qualities 0xff, mate fields

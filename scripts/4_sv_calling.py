@@ -25,6 +25,9 @@ parser.add_argument('--data_type', '-d', type=int, help="HIFI = 0 or CLR = 1 or 
 parser.add_argument('--device', type=int, default=0, help="GPU index (extension)")
 parser.add_argument('--contig-bam', dest='contig_bam', action='store_true',
                     help="also write assemblies.sorted.bam + .bai, the contig alignments with NM / cs / SA tags (extension; default off)")
+parser.add_argument('--chrom-mapq', dest='chrom_mapq', action='store_true',
+                    help="mapping quality of every contig record on the whole chromosome instead of the constant 60: contigs of segmental "
+                         "duplications then fail the mapq >= 50 tests (extension; default off)")
 
 
 def gather_haplotype_fasta(regions_dir, hp, out_path):
@@ -52,6 +55,7 @@ if __name__ == "__main__":
     n2 = gather_haplotype_fasta(os.path.join(args.out_dir, "regions"), 2, hp2)
     logger.info(f"contigs: hp1 {n1}, hp2 {n2}")
     dtype = {0: "CCS", 1: "CLR", 2: "ONT"}[args.data_type]
-    final = dippav_variant_call(dtype, args.bam_file, args.reference, hp1, hp2, chrom_dir, args.chr_num, None, args.num_cpus, device=args.device, contig_bam=args.contig_bam)
+    final = dippav_variant_call(dtype, args.bam_file, args.reference, hp1, hp2, chrom_dir, args.chr_num, None, args.num_cpus, device=args.device, contig_bam=args.contig_bam,
+                                chrom_mapq=args.chrom_mapq)
     logger.info(f"final VCF: {final}")
     print(final)
