@@ -6,11 +6,17 @@
 // (structure of arrays, CIGARs back to back in BAM encoding), region start through the .bai linear index when there is one; the
 // CIGAR scan for read-level DEL / INS signatures (extract_sig_from_cigar of extract_reads_signature.py:11-44) runs as a kernel,
 // one thread per record.  Format: SAM/BAM specification v1, sections 4.1 (BGZF), 4.2 (BAM), 5.2 (BAI).
+//
+// In file order: what the reader and the writer share (the base alphabet and its tables, the CIGAR ops that consume the reference,
+// the thread fan-out, the guard of the C entry points); the BGZF stream; the header and the .bai; the aux walk; fsv_bam_fetch
+// in stages (seek_to_query, view_record, judge, append_record); fsv_read_signatures; fsv_bam_write in stages (check_records,
+// stable_order, encode_stream, deflate_blocks, build_bai, write_files).
 #include "fsv_internal.h"
 #include <zlib.h>
 #include <cstdio>
 #include <cstring>
 #include <string>
+#include <memory>
 #include <new>
 #include <vector>
 #include <thread>
@@ -21,6 +27,57 @@
 #include <numeric>
 #include <unistd.h>
 #include <sys/stat.h>
+
+namespace {
+
+// ---- shared by the reader and the writer ------------------------------------------------------------------------------------------
+// the 4-bit base codes of a BAM record, and the tables over them: a packed byte (two bases) -> 4 bits of the read store (A C G T,
+// the rest A) and -> its two letters; a letter -> its code (an unknown one: N)
+constexpr char BAM_BASES[17] = "=ACMGRSVTWYHKDBN";
+struct BaseTabs {
+    uint8_t pair2[256], nib[256];
+    uint16_t pairc[256];
+    BaseTabs()
+    {
+        static const uint8_t code[16] = {0, 0, 1, 0, 2, 0, 0, 0, 3, 0, 0, 0, 0, 0, 0, 0};
+        memset(nib, 15, sizeof(nib));
+        for (int c = 0; c < 16; c++) nib[(uint8_t)BAM_BASES[c]] = (uint8_t)c;
+        for (int v = 0; v < 256; v++) {
+            pair2[v] = (uint8_t)(code[v >> 4] | code[v & 15] << 2);
+            pairc[v] = (uint16_t)((uint8_t)BAM_BASES[v >> 4] | (uint16_t)(uint8_t)BAM_BASES[v & 15] << 8);
+        }
+    }
+};
+const BaseTabs base_tabs;
+
+// M, D, N, = and X advance the reference (mapq_rec_fits of aln_mapq.h has a narrower set of its own: what the aligner writes)
+inline bool cigar_consumes_ref(uint32_t op) { return op == 0 || op == 2 || op == 3 || op == 7 || op == 8; }
+
+// fn(i) for every i in [0, n) on up to nt threads, the caller's included; false when a call answered false or threw (a worker
+// keeps what it throws to itself: an exception that leaves a thread function ends the process).  When a thread cannot start,
+// those already running are joined before the error goes on to the caller.
+template <class F> bool fan_out(size_t n, unsigned nt, F fn)
+{
+    std::atomic<bool> ok{true};
+    auto work = [&](unsigned t) {
+        try { for (size_t i = t; i < n; i += nt) if (!fn(i)) ok = false; }
+        catch (...) { ok = false; }
+    };
+    if (nt <= 1) { work(0); return ok; }
+    std::vector<std::thread> th;
+    try { for (unsigned t = 1; t < nt; t++) th.emplace_back(work, t); }
+    catch (...) { for (auto &t : th) t.join(); throw; }
+    work(0);
+    for (auto &t : th) t.join();
+    return ok;
+}
+
+// no C++ exception crosses the C ABI (a caller through ctypes would see std::terminate).  Not FSV_GUARD: there is no context
+// here, and the reader answers FSV_EINVAL for what it cannot name where the writer answers FSV_EINTERNAL.
+#define BAM_GUARD(fallback, call)                                   \
+    try { return (call); }                                          \
+    catch (const std::bad_alloc &) { return FSV_ENOMEM; }           \
+    catch (...) { return (fallback); }
 
 struct BgzfBlock {
     std::vector<uint8_t> comp, data;
@@ -48,11 +105,16 @@ struct BamCache {
     void clear() { *this = BamCache(); }
 };
 
+struct FileCloser { void operator()(FILE *f) const { fclose(f); } };
+
+} // namespace
+
 struct fsv_bam {
-    FILE *f = nullptr;
+    std::unique_ptr<FILE, FileCloser> f;
     std::string path, err;
     std::vector<std::string> ref_name;
     std::vector<int32_t> ref_len;
+    uint64_t first_record_voff = 0;  // virtual offset behind the header: where a scan without an index starts
     // BGZF stream state
     std::vector<uint8_t> block;      // inflated data of the current block
     size_t block_pos = 0;
@@ -61,18 +123,23 @@ struct fsv_bam {
     bool eof = false;
     BgzfWindow win;                  // blocks read ahead and inflated in parallel; win_i = the next one to hand out
     size_t win_i = 0, run_blocks = 16;
-    std::future<BgzfWindow> pending; // the run after `win`, being read and inflated in the background
-    bool has_pending = false;
+    std::future<BgzfWindow> pending; // the run after `win`, being read and inflated in the background (valid() while there is one)
     int n_threads = 1;
     BamCache cache;                  // the records of the last sizing call, until the caller has taken them
     // .bai: per reference the smallest virtual offset of its chunks (where a scan of that reference starts), and the linear index
     bool have_index = false;
     std::vector<uint64_t> ref_first_voff;
     std::vector<std::vector<uint64_t>> linear;
+
+    // wait for the read-ahead and let go of its blocks; what it stored as an error is thrown here
+    void drop_pending() { if (pending.valid()) (void)pending.get(); }
+    // (an error the read-ahead stored concerns blocks nobody asked for: it ends with the handle; the file closes after the read-ahead is done with it)
+    ~fsv_bam() { try { drop_pending(); } catch (...) {} }
 };
 
 namespace {
 
+// ---- the BGZF stream ----------------------------------------------------------------------------------------------------------------
 // one BGZF block: header parsed and compressed bytes read by the (serial) file scan, inflated by whichever thread takes it
 bool inflate_block(BgzfBlock &k)
 {
@@ -88,69 +155,59 @@ bool inflate_block(BgzfBlock &k)
     return rc == Z_STREAM_END && zs.total_out == k.isize;
 }
 
+// the next block of the file, header and compressed bytes, into k: nullptr when it is whole (or, with *at_end, when nothing is left),
+// else what is wrong with it
+const char *read_raw_block(FILE *f, BgzfBlock &k, bool *at_end)
+{
+    uint8_t hdr[18];
+    const size_t got = fread(hdr, 1, 18, f);
+    *at_end = got == 0;
+    if (got == 0) return nullptr;
+    if (got != 18 || hdr[0] != 31 || hdr[1] != 139 || hdr[2] != 8 || !(hdr[3] & 4)) return "not a BGZF block";
+    const unsigned xlen = hdr[10] | hdr[11] << 8;
+    // the BC subfield is the first extra subfield in every BGZF writer; tolerate others in front of it
+    std::vector<uint8_t> extra(xlen);
+    if (xlen) memcpy(extra.data(), hdr + 12, std::min<size_t>(6, xlen));
+    if (xlen > 6 && fread(extra.data() + 6, 1, xlen - 6, f) != xlen - 6) return "truncated BGZF header";
+    int bsize = -1;
+    for (size_t p = 0; p + 4 <= extra.size();) {
+        const unsigned slen = extra[p + 2] | extra[p + 3] << 8;
+        if (extra[p] == 'B' && extra[p + 1] == 'C' && slen == 2 && p + 6 <= extra.size()) bsize = (extra[p + 4] | extra[p + 5] << 8) + 1;
+        p += 4 + slen;
+    }
+    const int clen = bsize - 12 - (int)xlen - 8;   // block = 12-byte header + extra + deflate data + crc32 + isize
+    if (bsize < 0) return "BGZF block without BC subfield";
+    if (clen < 0) return "bad BGZF block size";
+    k.comp.resize((size_t)clen + 8);
+    if (fread(k.comp.data(), 1, k.comp.size(), f) != k.comp.size()) return "truncated BGZF block";
+    k.clen = (uint32_t)clen;
+    k.isize = k.comp[clen + 4] | k.comp[clen + 5] << 8 | k.comp[clen + 6] << 16 | (uint32_t)k.comp[clen + 7] << 24;
+    if (k.isize > 65536) return "bad BGZF block size";
+    k.bsize = bsize;
+    return nullptr;
+}
+
 // read a run of up to `want` blocks starting at file offset addr and inflate them on the reader's threads.  A malformed block behind
 // at least one good one ends the run: the next run starts at it and reports it.
 BgzfWindow load_window(fsv_bam *b, int64_t addr, size_t want)
 {
     BgzfWindow w;
     w.next_addr = addr;
-    if (fseeko(b->f, (off_t)addr, SEEK_SET) != 0) { w.err = "seek failed"; return w; }
+    if (fseeko(b->f.get(), (off_t)addr, SEEK_SET) != 0) { w.err = "seek failed"; return w; }
     while (w.blk.size() < want) {
-        const char *bad = nullptr;
-        uint8_t hdr[18];
-        const size_t got = fread(hdr, 1, 18, b->f);
-        if (got == 0) break;                       // end of file
         BgzfBlock k;
-        int bsize = -1;
-        if (got != 18 || hdr[0] != 31 || hdr[1] != 139 || hdr[2] != 8 || !(hdr[3] & 4)) bad = "not a BGZF block";
-        else {
-            const unsigned xlen = hdr[10] | hdr[11] << 8;
-            // the BC subfield is the first extra subfield in every BGZF writer; tolerate others in front of it
-            std::vector<uint8_t> extra(xlen);
-            memcpy(extra.data(), hdr + 12, std::min<size_t>(6, xlen));
-            if (xlen > 6 && fread(extra.data() + 6, 1, xlen - 6, b->f) != xlen - 6) bad = "truncated BGZF header";
-            for (size_t p = 0; !bad && p + 4 <= extra.size();) {
-                const unsigned slen = extra[p + 2] | extra[p + 3] << 8;
-                if (extra[p] == 'B' && extra[p + 1] == 'C' && slen == 2 && p + 6 <= extra.size()) bsize = (extra[p + 4] | extra[p + 5] << 8) + 1;
-                p += 4 + slen;
-            }
-            const int clen = bsize - 12 - (int)xlen - 8;   // block = 12-byte header + extra + deflate data + crc32 + isize
-            if (!bad && bsize < 0) bad = "BGZF block without BC subfield";
-            else if (!bad && clen < 0) bad = "bad BGZF block size";
-            if (!bad) {
-                k.comp.resize((size_t)clen + 8);
-                if (fread(k.comp.data(), 1, k.comp.size(), b->f) != k.comp.size()) bad = "truncated BGZF block";
-                else {
-                    k.clen = (uint32_t)clen;
-                    k.isize = k.comp[clen + 4] | k.comp[clen + 5] << 8 | k.comp[clen + 6] << 16 | (uint32_t)k.comp[clen + 7] << 24;
-                    if (k.isize > 65536) bad = "bad BGZF block size";
-                }
-            }
-        }
+        bool at_end = false;
+        const char *bad = read_raw_block(b->f.get(), k, &at_end);
+        if (at_end) break;
         if (bad) { if (w.blk.empty()) w.err = bad; break; }
         k.addr = w.next_addr;
-        k.bsize = bsize;
-        w.next_addr += bsize;
+        w.next_addr += k.bsize;
         w.blk.push_back(std::move(k));
     }
     const size_t n = w.blk.size();
     const unsigned nt = (unsigned)std::min<size_t>((size_t)std::max(1, b->n_threads), (n + 7) / 8);
-    std::atomic<bool> ok{true};
-    auto work = [&](unsigned t) { for (size_t i = t; i < n; i += nt) if (!inflate_block(w.blk[i])) ok = false; };
-    if (nt <= 1) work(0);
-    else {
-        std::vector<std::thread> th;
-        for (unsigned t = 1; t < nt; t++) th.emplace_back(work, t);
-        work(0);
-        for (auto &t : th) t.join();
-    }
-    if (!ok) { w.blk.clear(); w.err = "inflate failed"; }
+    if (!fan_out(n, nt, [&](size_t i) { return inflate_block(w.blk[i]); })) { w.blk.clear(); w.err = "inflate failed"; }
     return w;
-}
-
-void drop_pending(fsv_bam *b)
-{
-    if (b->has_pending) { (void)b->pending.get(); b->has_pending = false; }
 }
 
 // The run grows from 16 to 512 blocks as a scan goes on, so a region query touches little beyond its blocks while a chromosome scan
@@ -158,7 +215,7 @@ void drop_pending(fsv_bam *b)
 bool bgzf_read_block(fsv_bam *b)
 {
     if (b->win_i == b->win.blk.size()) {
-        if (b->has_pending) { b->win = b->pending.get(); b->has_pending = false; }
+        if (b->pending.valid()) b->win = b->pending.get();
         else b->win = load_window(b, b->win.next_addr, b->run_blocks);
         b->win_i = 0;
         if (!b->win.err.empty()) { b->err = b->win.err; return false; }
@@ -168,7 +225,6 @@ bool bgzf_read_block(fsv_bam *b)
             const int64_t at = b->win.next_addr;
             const size_t want = b->run_blocks;
             b->pending = std::async(std::launch::async, [b, at, want] { return load_window(b, at, want); });
-            b->has_pending = true;
         }
     }
     BgzfBlock &k = b->win.blk[b->win_i++];
@@ -199,7 +255,7 @@ bool bgzf_read(fsv_bam *b, void *dst, size_t n)
 
 bool bgzf_seek(fsv_bam *b, uint64_t voff)
 {
-    drop_pending(b);
+    b->drop_pending();
     b->win = BgzfWindow();
     b->win.next_addr = (int64_t)(voff >> 16);
     b->win_i = 0; b->run_blocks = 16;
@@ -211,18 +267,37 @@ bool bgzf_seek(fsv_bam *b, uint64_t voff)
     return true;
 }
 
+// (at a block's end: the start of the next block, which is also right at the end of the file)
 inline uint64_t bgzf_tell(const fsv_bam *b)
 {
     return b->block_pos == b->block.size() && !b->block.empty() ? (uint64_t)b->next_addr << 16 : ((uint64_t)b->block_addr << 16 | (uint64_t)b->block_pos);
+}
+
+// ---- the header and the index ---------------------------------------------------------------------------------------------------------
+// magic, text, reference names and lengths, from the start of the stream; read once, at open
+bool read_header(fsv_bam *b)
+{
+    char magic[4]; int32_t l_text = 0, n_ref = 0;
+    bool ok = bgzf_read(b, magic, 4) && !memcmp(magic, "BAM\1", 4) && bgzf_read(b, &l_text, 4) && l_text >= 0;
+    if (ok) { std::vector<char> text((size_t)l_text); ok = l_text == 0 || bgzf_read(b, text.data(), (size_t)l_text); }
+    ok = ok && bgzf_read(b, &n_ref, 4) && n_ref >= 0;
+    for (int32_t r = 0; ok && r < n_ref; r++) {
+        int32_t l_name = 0, l_ref = 0;
+        ok = bgzf_read(b, &l_name, 4) && l_name > 0 && l_name < (1 << 16);
+        std::vector<char> nm((size_t)std::max(1, l_name));
+        ok = ok && bgzf_read(b, nm.data(), (size_t)l_name) && bgzf_read(b, &l_ref, 4);
+        if (ok) { b->ref_name.emplace_back(nm.data(), strnlen(nm.data(), (size_t)l_name)); b->ref_len.push_back(l_ref); }   // the name may lack its NUL
+    }
+    return ok;
 }
 
 void load_bai(fsv_bam *b)
 {
     for (const std::string &p : {b->path + ".bai", b->path.size() > 4 ? b->path.substr(0, b->path.size() - 4) + ".bai" : std::string()}) {
         if (p.empty()) continue;
-        FILE *f = fopen(p.c_str(), "rb");
+        const std::unique_ptr<FILE, FileCloser> f(fopen(p.c_str(), "rb"));
         if (!f) continue;
-        auto rd = [&](void *d, size_t n) { return fread(d, 1, n, f) == n; };
+        auto rd = [&](void *d, size_t n) { return fread(d, 1, n, f.get()) == n; };
         char magic[4]; int32_t n_ref = 0;
         bool ok = rd(magic, 4) && !memcmp(magic, "BAI\1", 4) && rd(&n_ref, 4) && n_ref == (int32_t)b->ref_name.size();
         std::vector<uint64_t> first((size_t)std::max(0, n_ref), ~0ull);
@@ -243,51 +318,22 @@ void load_bai(fsv_bam *b)
             ok = ok && rd(&n_intv, 4) && n_intv >= 0 && n_intv <= (1 << 24);   // 2^24 x 16 kb windows = 2^38 bases
             if (ok) { lin[r].resize((size_t)n_intv); ok = n_intv == 0 || rd(lin[r].data(), (size_t)n_intv * 8); }
         }
-        fclose(f);
         if (ok) { b->have_index = true; b->ref_first_voff = first; b->linear = lin; return; }
     }
 }
 
-// integer value of a two-letter tag in the aux block; false when the tag is absent (or not an integer)
-bool aux_int(const uint8_t *p, const uint8_t *end, char t0, char t1, int32_t *out)
-{
-    while (p + 3 <= end) {
-        const char a = (char)p[0], b = (char)p[1], ty = (char)p[2];
-        p += 3;
-        size_t sz = 0;
-        int64_t v = 0; bool is_int = true;
-        switch (ty) {
-        case 'A': sz = 1; is_int = false; break;
-        case 'c': sz = 1; if (p + 1 <= end) v = (int8_t)p[0]; break;
-        case 'C': sz = 1; if (p + 1 <= end) v = p[0]; break;
-        case 's': sz = 2; if (p + 2 <= end) { int16_t x; memcpy(&x, p, 2); v = x; } break;
-        case 'S': sz = 2; if (p + 2 <= end) { uint16_t x; memcpy(&x, p, 2); v = x; } break;
-        case 'i': sz = 4; if (p + 4 <= end) { int32_t x; memcpy(&x, p, 4); v = x; } break;
-        case 'I': sz = 4; if (p + 4 <= end) { uint32_t x; memcpy(&x, p, 4); v = x; } break;
-        case 'f': sz = 4; is_int = false; break;
-        case 'Z': case 'H': { const uint8_t *q = p; while (q < end && *q) q++; sz = (size_t)(q - p) + 1; is_int = false; break; }
-        case 'B': {
-            if (p + 5 > end) return false;
-            uint32_t cnt; memcpy(&cnt, p + 1, 4);
-            const char st = (char)p[0];
-            const size_t es = (st == 'c' || st == 'C') ? 1 : (st == 's' || st == 'S') ? 2 : 4;
-            sz = 5 + (size_t)cnt * es; is_int = false; break;
-        }
-        default: return false;   // unknown type: the rest cannot be walked
-        }
-        if (p + sz > end) return false;
-        if (a == t0 && b == t1) { if (!is_int) return false; *out = (int32_t)v; return true; }
-        p += sz;
-    }
-    return false;
-}
+// ---- aux tags -------------------------------------------------------------------------------------------------------------------------
+struct AuxField { char type = 0; const uint8_t *val = nullptr; size_t size = 0; };   // type 0: absent
 
-// value of a two-letter string (Z) tag: pointer into the record and its length; false when absent
-bool aux_str(const uint8_t *p, const uint8_t *end, char t0, char t1, const char **out, size_t *len)
+// The two-letter tag (t0, t1) in the aux block [p, end): its type byte, where its value starts and the bytes the value takes (a
+// string's NUL, a B array's sub-type and count included).  Absent: no such tag, a field of unknown type in front of it or as its own
+// (the rest cannot be walked), or a value -- its own or one in front -- that runs past end.
+AuxField aux_find(const uint8_t *p, const uint8_t *end, char t0, char t1)
 {
-    while (p + 3 <= end) {
+    while (end - p >= 3) {
         const char a = (char)p[0], b = (char)p[1], ty = (char)p[2];
         p += 3;
+        const size_t left = (size_t)(end - p);
         size_t sz = 0;
         switch (ty) {
         case 'A': case 'c': case 'C': sz = 1; break;
@@ -295,25 +341,47 @@ bool aux_str(const uint8_t *p, const uint8_t *end, char t0, char t1, const char 
         case 'i': case 'I': case 'f': sz = 4; break;
         case 'Z': case 'H': { const uint8_t *q = p; while (q < end && *q) q++; sz = (size_t)(q - p) + 1; break; }
         case 'B': {
-            if (p + 5 > end) return false;
+            if (left < 5) return {};
             uint32_t cnt; memcpy(&cnt, p + 1, 4);
             const char st = (char)p[0];
             sz = 5 + (size_t)cnt * ((st == 'c' || st == 'C') ? 1 : (st == 's' || st == 'S') ? 2 : 4);
             break;
         }
-        default: return false;
+        default: return {};
         }
-        if (p + sz > end) return false;
-        if (a == t0 && b == t1) { if (ty != 'Z') return false; *out = (const char *)p; *len = sz - 1; return true; }
+        if (sz > left) return {};
+        if (a == t0 && b == t1) return {ty, p, sz};
         p += sz;
     }
-    return false;
+    return {};
 }
 
-} // namespace
+// integer value of a tag; false when the tag is absent or not an integer
+bool aux_int(const uint8_t *p, const uint8_t *end, char t0, char t1, int32_t *out)
+{
+    const AuxField f = aux_find(p, end, t0, t1);
+    switch (f.type) {
+    case 'c': *out = (int8_t)f.val[0]; return true;
+    case 'C': *out = f.val[0]; return true;
+    case 's': { int16_t x; memcpy(&x, f.val, 2); *out = x; return true; }
+    case 'S': { uint16_t x; memcpy(&x, f.val, 2); *out = x; return true; }
+    case 'i': case 'I': memcpy(out, f.val, 4); return true;   // (an I above 2^31 wraps, as a cast does)
+    default: return false;
+    }
+}
 
+// value of a string (Z) tag: pointer into the record and its length; false when the tag is absent or not a string
+bool aux_str(const uint8_t *p, const uint8_t *end, char t0, char t1, const char **out, size_t *len)
+{
+    const AuxField f = aux_find(p, end, t0, t1);
+    if (f.type != 'Z') return false;
+    *out = (const char *)f.val; *len = f.size - 1;
+    return true;
+}
+
+// ---- fsv_bam_fetch in stages ------------------------------------------------------------------------------------------------------
 // counts to the caller; with buffers (pos != NULL) also the arrays, after which the reader lets go of them
-static int copy_out(fsv_bam *b, fsv_bam_records *out, int want_seq)
+int copy_out(fsv_bam *b, fsv_bam_records *out, int want_seq)
 {
     BamCache &c = b->cache;
     const size_t n = c.pos.size();
@@ -343,41 +411,194 @@ static int copy_out(fsv_bam *b, fsv_bam_records *out, int want_seq)
     return FSV_OK;
 }
 
-static int fsv_bam_open_impl(const char *path, fsv_bam **out)
+// what a fetch asks for, normalised: reference ref_id over [beg, end), or (all) every record of the file, unmapped ones included
+struct Query { int ref_id; int64_t beg, end; bool all; };
+
+// Put the stream where the query's scan starts: with an index, the linear-index entry of the window that holds beg (or the
+// reference's first chunk); without one, or for the whole file, the first record.
+enum class Seek { ok, no_records, failed };
+Seek seek_to_query(fsv_bam *b, const Query &q)
+{
+    uint64_t v = b->first_record_voff;
+    if (b->have_index && !q.all) {
+        v = b->ref_first_voff[(size_t)q.ref_id];
+        const auto &lin = b->linear[(size_t)q.ref_id];
+        const size_t w = (size_t)(q.beg >> 14);
+        if (w < lin.size() && lin[w] != 0 && (v == ~0ull || lin[w] > v)) v = lin[w];
+        if (v == ~0ull) return Seek::no_records;   // no records on this reference
+    }
+    return bgzf_seek(b, v) ? Seek::ok : Seek::failed;
+}
+
+// one record (block_size bytes behind the length word): the fixed 32 bytes, and where its parts lie
+struct RecView {
+    int32_t ref_id, pos, l_seq;
+    uint8_t l_name, mapq;
+    uint16_t n_cigar_op, flag;
+    bool fits;                       // name + CIGAR + packed bases lie inside the record (and l_seq >= 0): only then are the pointers set
+    const char *qname;
+    const uint8_t *cigar, *seq, *aux, *rend;   // (aux: nullptr when the qualities are cut short, a record without tags)
+    int64_t ref_end() const
+    {
+        int64_t e = pos;
+        for (uint32_t k = 0; k < n_cigar_op; k++) { uint32_t v; memcpy(&v, cigar + 4 * k, 4); if (cigar_consumes_ref(v & 0xf)) e += v >> 4; }
+        return e;
+    }
+};
+
+RecView view_record(const uint8_t *rec, int32_t block_size)
+{
+    RecView v{};
+    memcpy(&v.ref_id, rec, 4); memcpy(&v.pos, rec + 4, 4);
+    v.l_name = rec[8]; v.mapq = rec[9];
+    memcpy(&v.n_cigar_op, rec + 12, 2); memcpy(&v.flag, rec + 14, 2); memcpy(&v.l_seq, rec + 16, 4);
+    v.rend = rec + block_size;
+    const size_t nb = v.l_seq >= 0 ? ((size_t)v.l_seq + 1) / 2 : 0, seq_at = (size_t)32 + v.l_name + (size_t)v.n_cigar_op * 4;
+    v.fits = v.l_seq >= 0 && seq_at + nb <= (size_t)block_size;
+    if (!v.fits) return v;
+    v.qname = (const char *)rec + 32;
+    v.cigar = rec + 32 + v.l_name;
+    v.seq = rec + seq_at;
+    if (seq_at + nb + (size_t)v.l_seq <= (size_t)block_size) v.aux = v.seq + nb + (size_t)v.l_seq;
+    return v;
+}
+
+// Whether the query takes the record, in this order (`samtools view` overlap semantics): a sorted file is past the query at a later
+// reference, at an unmapped record (they come last) or at pos >= end; a record that does not fit its block is an error wherever the
+// scan gets to it; one that ends at or before beg is skipped, unless it has no CIGAR and starts inside; so is a placed unmapped one.
+enum class Verdict { take, skip, stop, bad };
+Verdict judge(const RecView &v, const Query &q, int64_t *ref_end)
+{
+    if (!q.all) {
+        if (v.ref_id != q.ref_id) return (v.ref_id > q.ref_id || v.ref_id < 0) ? Verdict::stop : Verdict::skip;
+        if (v.pos >= q.end) return Verdict::stop;
+    }
+    if (!v.fits) return Verdict::bad;
+    *ref_end = v.ref_end();
+    if (!q.all) {
+        if (*ref_end <= q.beg && !(v.n_cigar_op == 0 && v.pos >= q.beg)) return Verdict::skip;   // ends before the window
+        if (v.flag & 4) return Verdict::skip;                                                      // unmapped but placed: fetch() skips it too
+    }
+    return Verdict::take;
+}
+
+// l_seq bases, two per byte -> 2 bits each, 16 per word; the padding nibble of an odd-length read is not a base
+void unpack_words(const uint8_t *sq, int32_t l_seq, std::vector<uint32_t> &out)
+{
+    const size_t nb = (size_t)(l_seq + 1) / 2, w0 = out.size(), nw = (size_t)(l_seq + 15) / 16;
+    out.resize(w0 + nw);
+    uint32_t *w = out.data() + w0;
+    for (size_t i = 0; i < nw; i++) {
+        uint32_t x = 0;
+        const size_t k1 = std::min<size_t>(8, nb - i * 8);
+        for (size_t k = 0; k < k1; k++) x |= (uint32_t)base_tabs.pair2[sq[i * 8 + k]] << (4 * k);
+        w[i] = x;
+    }
+    if (l_seq & 1) w[nw - 1] &= ~(3u << ((l_seq & 15) << 1));
+}
+
+// l_seq bases, two per byte -> text (what pysam's read.seq gives)
+void unpack_text(const uint8_t *sq, int32_t l_seq, std::vector<char> &out)
+{
+    const size_t nb = (size_t)(l_seq + 1) / 2, a0 = out.size();
+    out.resize(a0 + nb * 2);
+    char *w = out.data() + a0;
+    for (size_t i = 0; i < nb; i++) memcpy(w + 2 * i, &base_tabs.pairc[sq[i]], 2);
+    out.resize(a0 + (size_t)l_seq);
+}
+
+void append_record(BamCache &c, const RecView &v, int64_t ref_end, int want_seq)
+{
+    c.pos.push_back(v.pos); c.ref_end.push_back((int32_t)ref_end); c.flag.push_back(v.flag); c.mapq.push_back(v.mapq); c.ref.push_back(v.ref_id);
+    c.cigar_off.push_back(c.cigar.size()); c.n_cigar_op.push_back(v.n_cigar_op); c.qname_off.push_back(c.qname.size()); c.l_seq.push_back(v.l_seq);
+    const bool has_aux = v.aux != nullptr;
+    int32_t t;
+    c.ps.push_back(has_aux && aux_int(v.aux, v.rend, 'P', 'S', &t) ? t : FSV_BAM_NO_TAG);
+    c.hp.push_back(has_aux && aux_int(v.aux, v.rend, 'H', 'P', &t) ? t : FSV_BAM_NO_TAG);
+    const size_t c0 = c.cigar.size();
+    c.cigar.resize(c0 + v.n_cigar_op);
+    if (v.n_cigar_op) memcpy(c.cigar.data() + c0, v.cigar, (size_t)v.n_cigar_op * 4);
+    c.qname.insert(c.qname.end(), v.qname, v.qname + v.l_name);
+    if (want_seq & 4) {   // the SA tag's text + NUL; a record without one takes the NUL alone
+        const char *sv = nullptr; size_t sl = 0;
+        c.sa_off.push_back(c.sa.size());
+        if (has_aux && aux_str(v.aux, v.rend, 'S', 'A', &sv, &sl)) c.sa.insert(c.sa.end(), sv, sv + sl);
+        c.sa.push_back(0);
+    }
+    if (want_seq & 2) { c.seq_ascii_off.push_back(c.seq_ascii.size()); unpack_text(v.seq, v.l_seq, c.seq_ascii); }
+    if (want_seq & 1) { c.seq_word_off.push_back(c.seq_words.size()); unpack_words(v.seq, v.l_seq, c.seq_words); }
+}
+
+// the records from where the stream stands to the end of the query (or of the file) into the cache
+int scan_records(fsv_bam *b, const Query &q, int want_seq)
+{
+    std::vector<uint8_t> rec;
+    for (;;) {
+        int32_t bs = 0;
+        if (!bgzf_read(b, &bs, 4)) return b->err.empty() ? FSV_OK : FSV_EINVAL;   // (err empty: a clean end of file)
+        if (bs < 32) return FSV_EINVAL;
+        rec.resize((size_t)bs + 8);
+        if (!bgzf_read(b, rec.data(), (size_t)bs)) return FSV_EINVAL;
+        const RecView v = view_record(rec.data(), bs);
+        int64_t ref_end = 0;
+        switch (judge(v, q, &ref_end)) {
+        case Verdict::bad: return FSV_EINVAL;
+        case Verdict::stop: return FSV_OK;
+        case Verdict::skip: break;
+        case Verdict::take: append_record(b->cache, v, ref_end, want_seq); break;
+        }
+    }
+}
+
+int bam_open_impl(const char *path, fsv_bam **out)
 {
     if (!path || !out) return FSV_EINVAL;
-    fsv_bam *b = new fsv_bam();
+    std::unique_ptr<fsv_bam> b(new fsv_bam());
     b->path = path;
-    b->f = fopen(path, "rb");
-    if (!b->f) { delete b; return FSV_EINVAL; }
+    b->f.reset(fopen(path, "rb"));
+    if (!b->f) return FSV_EINVAL;
     b->n_threads = (int)std::min(16u, std::max(1u, std::thread::hardware_concurrency()));
-    char magic[4]; int32_t l_text = 0, n_ref = 0;
-    bool ok = false;
-    try {
-    ok = bgzf_read(b, magic, 4) && !memcmp(magic, "BAM\1", 4) && bgzf_read(b, &l_text, 4) && l_text >= 0;
-    if (ok) { std::vector<char> text((size_t)l_text); ok = l_text == 0 || bgzf_read(b, text.data(), (size_t)l_text); }
-    ok = ok && bgzf_read(b, &n_ref, 4) && n_ref >= 0;
-    for (int32_t r = 0; ok && r < n_ref; r++) {
-        int32_t l_name = 0, l_ref = 0;
-        ok = bgzf_read(b, &l_name, 4) && l_name > 0 && l_name < (1 << 16);
-        std::vector<char> nm((size_t)std::max(1, l_name));
-        ok = ok && bgzf_read(b, nm.data(), (size_t)l_name) && bgzf_read(b, &l_ref, 4);
-        if (ok) { b->ref_name.emplace_back(nm.data(), strnlen(nm.data(), (size_t)l_name)); b->ref_len.push_back(l_ref); }   // the name may lack its NUL
-    }
-    if (ok) load_bai(b);
-    } catch (...) { fclose(b->f); delete b; throw; }
-    if (!ok) { fclose(b->f); delete b; return FSV_EINVAL; }
-    *out = b;
+    if (!read_header(b.get())) return FSV_EINVAL;
+    b->first_record_voff = bgzf_tell(b.get());
+    load_bai(b.get());
+    *out = b.release();
     return FSV_OK;
 }
 
-extern "C" void fsv_bam_close(fsv_bam *b)
+// Records of reference ref_id overlapping [beg, end) (end <= 0: to the end of the reference), in file order -- the iteration
+// pysam's fetch() gives.  Two calls: with rec == NULL the counts come back (n_rec, n_cigar, qname_bytes, seq_bases), then the
+// caller allocates and calls again.  want_seq bit 0: also the bases, 2 bits each as in the read store (N -> A), read r at word
+// seq_word_off[r]; bit 1: the bases as text (what pysam's read.seq gives), read r at seq_ascii + seq_ascii_off[r].  ref_id -1: every
+// record of the file, unmapped ones included -- fetch(until_eof=True) of output_fas.py:26.
+int bam_fetch_impl(fsv_bam *b, int ref_id, int64_t beg, int64_t end, fsv_bam_records *out, int want_seq)
 {
-    if (!b) return;
-    if (b->has_pending) { (void)b->pending.get(); b->has_pending = false; }
-    if (b->f) fclose(b->f);
-    delete b;
+    if (!b || !out || ref_id < -1 || ref_id >= (int)b->ref_name.size()) return FSV_EINVAL;
+    Query q{ref_id, beg, end, ref_id == -1};
+    if (q.all) { q.beg = 0; q.end = INT64_MAX; }
+    else if (q.end <= 0) q.end = b->ref_len[(size_t)ref_id];
+    if (q.beg < 0) q.beg = 0;
+    // one parse per query: the sizing call (pos == NULL) decodes into the reader's own arrays, the call with buffers copies them out
+    BamCache &c = b->cache;
+    if (c.valid && c.ref_id == ref_id && c.beg == q.beg && c.end == q.end && c.want == want_seq) return copy_out(b, out, want_seq);
+    switch (seek_to_query(b, q)) {
+    case Seek::failed: return FSV_EINVAL;
+    case Seek::no_records: c.clear(); return copy_out(b, out, want_seq);
+    case Seek::ok: break;
+    }
+    c.clear();
+    TRY(scan_records(b, q, want_seq));
+    c.valid = true; c.ref_id = ref_id; c.beg = q.beg; c.end = q.end; c.want = want_seq;
+    return copy_out(b, out, want_seq);
 }
+
+} // namespace
+
+extern "C" int fsv_bam_open(const char *path, fsv_bam **out) { BAM_GUARD(FSV_EINVAL, bam_open_impl(path, out)) }
+extern "C" int fsv_bam_fetch(fsv_bam *b, int ref_id, int64_t beg, int64_t end, fsv_bam_records *out, int want_seq)
+{
+    BAM_GUARD(FSV_EINVAL, bam_fetch_impl(b, ref_id, beg, end, out, want_seq))
+}
+extern "C" void fsv_bam_close(fsv_bam *b) { delete b; }   // (~fsv_bam lets nothing through)
 
 extern "C" int fsv_bam_ref_id(const fsv_bam *b, const char *name)
 {
@@ -391,141 +612,6 @@ extern "C" const char *fsv_bam_ref_name(const fsv_bam *b, int id) { return b && 
 extern "C" void fsv_bam_set_threads(fsv_bam *b, int n) { if (b) b->n_threads = n < 1 ? 1 : n; }
 extern "C" int64_t fsv_bam_ref_length(const fsv_bam *b, int id) { return b && id >= 0 && id < (int)b->ref_len.size() ? (int64_t)b->ref_len[(size_t)id] : -1; }
 extern "C" int fsv_bam_has_index(const fsv_bam *b) { return b && b->have_index ? 1 : 0; }
-
-// Records of reference ref_id overlapping [beg, end) (end <= 0: to the end of the reference), in file order -- the iteration
-// pysam's fetch() gives.  Two calls: with rec == NULL the counts come back (n_rec, n_cigar, qname_bytes, seq_bases), then the
-// caller allocates and calls again.  want_seq bit 0: also the bases, 2 bits each as in the read store (N -> A), read r at word
-// seq_word_off[r]; bit 1: the bases as text (what pysam's read.seq gives), read r at seq_ascii + seq_ascii_off[r].  ref_id -1: every
-// record of the file, unmapped ones included -- fetch(until_eof=True) of output_fas.py:26.
-static int fsv_bam_fetch_impl(fsv_bam *b, int ref_id, int64_t beg, int64_t end, fsv_bam_records *out, int want_seq)
-{
-    if (!b || !out || ref_id < -1 || ref_id >= (int)b->ref_name.size()) return FSV_EINVAL;
-    const bool all = ref_id == -1;   // every record of the file in file order, unmapped ones included: fetch(until_eof=True)
-    if (all) { beg = 0; end = INT64_MAX; }
-    else if (end <= 0) end = b->ref_len[(size_t)ref_id];
-    if (beg < 0) beg = 0;
-    // one parse per query: the sizing call (pos == NULL) decodes into the reader's own arrays, the call with buffers copies them out
-    BamCache &c = b->cache;
-    if (c.valid && c.ref_id == ref_id && c.beg == beg && c.end == end && c.want == want_seq) return copy_out(b, out, want_seq);
-    // where to start: with an index, the linear-index entry of the window that holds beg (or the reference's first chunk)
-    uint64_t start = 0;
-    bool seeked = false;
-    if (b->have_index && !all) {
-        uint64_t v = b->ref_first_voff[(size_t)ref_id];
-        const auto &lin = b->linear[(size_t)ref_id];
-        const size_t w = (size_t)(beg >> 14);
-        if (w < lin.size() && lin[w] != 0 && (v == ~0ull || lin[w] > v)) v = lin[w];
-        if (v == ~0ull) { c.clear(); return copy_out(b, out, want_seq); }   // no records on this reference
-        start = v; seeked = true;
-    }
-    if (seeked) { if (!bgzf_seek(b, start)) return FSV_EINVAL; }
-    else {
-        // no index: from the first record (skip the header again)
-        if (!bgzf_seek(b, 0)) return FSV_EINVAL;
-        char magic[4]; int32_t l_text = 0, n_ref = 0;
-        if (!bgzf_read(b, magic, 4) || !bgzf_read(b, &l_text, 4) || l_text < 0) return FSV_EINVAL;
-        std::vector<char> skip((size_t)l_text);
-        if (l_text && !bgzf_read(b, skip.data(), (size_t)l_text)) return FSV_EINVAL;
-        if (!bgzf_read(b, &n_ref, 4) || n_ref < 0) return FSV_EINVAL;
-        for (int32_t r = 0; r < n_ref; r++) {
-            int32_t l_name = 0, l_ref = 0;
-            if (!bgzf_read(b, &l_name, 4) || l_name <= 0 || l_name >= (1 << 16)) return FSV_EINVAL;
-            skip.resize((size_t)l_name);
-            if (!bgzf_read(b, skip.data(), (size_t)l_name) || !bgzf_read(b, &l_ref, 4)) return FSV_EINVAL;
-        }
-    }
-    c.clear();
-    std::vector<uint8_t> rec;
-    // =ACMGRSVTWYHKDBN -> A C G T (the rest A), two bases per packed byte -> 4 bits; and the same byte as two letters
-    struct Tabs {
-        uint8_t pair2[256];
-        uint16_t pairc[256];
-        Tabs() {
-            static const uint8_t code[16] = {0, 0, 1, 0, 2, 0, 0, 0, 3, 0, 0, 0, 0, 0, 0, 0};
-            for (int v = 0; v < 256; v++) {
-                pair2[v] = (uint8_t)(code[v >> 4] | code[v & 15] << 2);
-                pairc[v] = (uint16_t)((uint8_t)"=ACMGRSVTWYHKDBN"[v >> 4] | (uint16_t)(uint8_t)"=ACMGRSVTWYHKDBN"[v & 15] << 8);
-            }
-        }
-    };
-    static const Tabs tabs;
-    const uint8_t *pair2 = tabs.pair2;
-    const uint16_t *pairc = tabs.pairc;
-    for (;;) {
-        int32_t bs = 0;
-        if (!bgzf_read(b, &bs, 4)) { if (!b->err.empty()) return FSV_EINVAL; break; }   // clean end of file
-        if (bs < 32) return FSV_EINVAL;
-        rec.resize((size_t)bs + 8);
-        if (!bgzf_read(b, rec.data(), (size_t)bs)) return FSV_EINVAL;
-        const uint8_t *rend = rec.data() + bs;
-        int32_t refID, pos, l_seq; uint8_t l_read_name, mapq; uint16_t n_cigar_op, flag;
-        memcpy(&refID, rec.data(), 4); memcpy(&pos, rec.data() + 4, 4);
-        l_read_name = rec[8]; mapq = rec[9];
-        memcpy(&n_cigar_op, rec.data() + 12, 2); memcpy(&flag, rec.data() + 14, 2); memcpy(&l_seq, rec.data() + 16, 4);
-        if (!all) {
-            if (refID != ref_id) {
-                if (refID > ref_id || refID < 0) break;   // sorted file: past our reference (unmapped reads come last)
-                continue;
-            }
-            if (pos >= end) break;
-        }
-        const uint8_t *p = rec.data() + 32;
-        const char *qname = (const char *)p;
-        p += l_read_name;
-        if (l_seq < 0 || (size_t)(p - rec.data()) + (size_t)n_cigar_op * 4 + (size_t)(l_seq + 1) / 2 > (size_t)bs) return FSV_EINVAL;
-        int64_t ref_end = pos;
-        for (uint32_t k = 0; k < n_cigar_op; k++) {
-            uint32_t v; memcpy(&v, p + 4 * k, 4);
-            const uint32_t op = v & 0xf;
-            if (op == 0 || op == 2 || op == 3 || op == 7 || op == 8) ref_end += v >> 4;
-        }
-        if (!all) {
-            if (ref_end <= beg && !(n_cigar_op == 0 && pos >= beg)) continue;   // ends before the window
-            if (flag & 4) continue;                                               // unmapped but placed: fetch() skips it too
-        }
-        const uint8_t *sq = p + (size_t)n_cigar_op * 4;
-        const uint8_t *aux = sq + (size_t)(l_seq + 1) / 2 + (size_t)l_seq;
-        c.pos.push_back(pos); c.ref_end.push_back((int32_t)ref_end); c.flag.push_back(flag); c.mapq.push_back(mapq); c.ref.push_back(refID);
-        c.cigar_off.push_back(c.cigar.size()); c.n_cigar_op.push_back(n_cigar_op); c.qname_off.push_back(c.qname.size()); c.l_seq.push_back(l_seq);
-        int32_t v;
-        c.ps.push_back(aux <= rend && aux_int(aux, rend, 'P', 'S', &v) ? v : FSV_BAM_NO_TAG);
-        c.hp.push_back(aux <= rend && aux_int(aux, rend, 'H', 'P', &v) ? v : FSV_BAM_NO_TAG);
-        const size_t c0 = c.cigar.size();
-        c.cigar.resize(c0 + n_cigar_op);
-        if (n_cigar_op) memcpy(c.cigar.data() + c0, p, (size_t)n_cigar_op * 4);
-        c.qname.insert(c.qname.end(), qname, qname + l_read_name);
-        if (want_seq & 4) {   // the SA tag's text + NUL; a record without one takes the NUL alone
-            const char *sv = nullptr; size_t sl = 0;
-            c.sa_off.push_back(c.sa.size());
-            if (aux <= rend && aux_str(aux, rend, 'S', 'A', &sv, &sl)) c.sa.insert(c.sa.end(), sv, sv + sl);
-            c.sa.push_back(0);
-        }
-        const size_t nb = (size_t)(l_seq + 1) / 2;
-        if (want_seq & 2) {
-            const size_t a0 = c.seq_ascii.size();
-            c.seq_ascii_off.push_back(a0);
-            c.seq_ascii.resize(a0 + nb * 2);
-            char *w = c.seq_ascii.data() + a0;
-            for (size_t i = 0; i < nb; i++) memcpy(w + 2 * i, &pairc[sq[i]], 2);
-            c.seq_ascii.resize(a0 + (size_t)l_seq);
-        }
-        if (want_seq & 1) {
-            const size_t w0 = c.seq_words.size(), nw = (size_t)(l_seq + 15) / 16;
-            c.seq_word_off.push_back(w0);
-            c.seq_words.resize(w0 + nw);
-            uint32_t *w = c.seq_words.data() + w0;
-            for (size_t i = 0; i < nw; i++) {
-                uint32_t x = 0;
-                const size_t k1 = std::min<size_t>(8, nb - i * 8);
-                for (size_t k = 0; k < k1; k++) x |= (uint32_t)pair2[sq[i * 8 + k]] << (4 * k);
-                w[i] = x;
-            }
-            if (l_seq & 1) w[nw - 1] &= ~(3u << ((l_seq & 15) << 1));   // the padding nibble of an odd-length read is not a base
-        }
-    }
-    c.valid = true; c.ref_id = ref_id; c.beg = beg; c.end = end; c.want = want_seq;
-    return copy_out(b, out, want_seq);
-}
 
 // ---------------------------------------------------------------------------------------------------------------------
 // read-level signatures from CIGARs (extract_reads_signature.py:11-44): one thread per record
@@ -553,38 +639,34 @@ __global__ void k_cigar_sigs(const int32_t *__restrict__ pos, const uint8_t *__r
         }
     }
 }
-} // namespace
 
-static int fsv_read_signatures_impl(fsv_ctx *ctx, const fsv_bam_records *rec, int min_mapq, int min_svlen, fsv_read_sig *out, uint32_t cap, uint32_t *n_out)
+// the device buffers live for the call (a buffer kept on the context would change what the caller sees in free memory)
+int read_signatures_impl(fsv_ctx *ctx, const fsv_bam_records *rec, int min_mapq, int min_svlen, fsv_read_sig *out, uint32_t cap, uint32_t *n_out)
 {
     if (!ctx || !rec || !out || !n_out) return FSV_EINVAL;
     *n_out = 0;
     if (rec->n_rec == 0) return FSV_OK;
     FSV_HIP(ctx, hipSetDevice(ctx->device));
-    void *d_pos = nullptr, *d_mq = nullptr, *d_off = nullptr, *d_nop = nullptr, *d_cig = nullptr, *d_out = nullptr, *d_n = nullptr;
-    int rc = FSV_OK;
-    auto A = [&](void **p, size_t n) { if (rc == FSV_OK && hipMalloc(p, n + 64) != hipSuccess) rc = fsv_fail(ctx, FSV_ENOMEM, "hipMalloc failed"); };
-    auto U = [&](void *d, const void *h, size_t n) { if (rc == FSV_OK && n && hipMemcpyAsync(d, h, n, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) rc = fsv_fail(ctx, FSV_EHIP, "upload failed"); };
     const size_t n = (size_t)rec->n_rec;
-    A(&d_pos, n * 4); A(&d_mq, n); A(&d_off, n * 8); A(&d_nop, n * 4); A(&d_cig, (size_t)rec->n_cigar * 4); A(&d_out, (size_t)cap * sizeof(fsv_read_sig)); A(&d_n, 4);
-    U(d_pos, rec->pos, n * 4); U(d_mq, rec->mapq, n); U(d_off, rec->cigar_off, n * 8); U(d_nop, rec->n_cigar_op, n * 4); U(d_cig, rec->cigar, (size_t)rec->n_cigar * 4);
-    if (rc == FSV_OK) {
-        (void)hipMemsetAsync(d_n, 0, 4, ctx->stream);
-        hipLaunchKernelGGL(k_cigar_sigs, dim3(fsv_grid_for(rec->n_rec, 256)), dim3(256), 0, ctx->stream, (const int32_t *)d_pos, (const uint8_t *)d_mq,
-                           (const uint64_t *)d_off, (const uint32_t *)d_nop, (const uint32_t *)d_cig, (uint32_t)rec->n_rec, min_mapq, min_svlen,
-                           (fsv_read_sig *)d_out, cap, (uint32_t *)d_n);
-        uint32_t cnt = 0;
-        if (hipMemcpyAsync(&cnt, d_n, 4, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess)
-            rc = fsv_fail(ctx, FSV_EHIP, "signature kernel failed");
-        else if (cnt > cap) { *n_out = cnt; rc = FSV_ECAP; }
-        else {
-            *n_out = cnt;
-            if (cnt && (hipMemcpyAsync(out, d_out, (size_t)cnt * sizeof(fsv_read_sig), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
-                        hipStreamSynchronize(ctx->stream) != hipSuccess)) rc = fsv_fail(ctx, FSV_EHIP, "download failed");
-        }
-    }
-    for (void *p : {d_pos, d_mq, d_off, d_nop, d_cig, d_out, d_n}) if (p) (void)hipFree(p);
-    return rc;
+    Dev<int32_t> d_pos; Dev<uint8_t> d_mq; Dev<uint64_t> d_off; Dev<uint32_t> d_nop, d_cig, d_n; Dev<fsv_read_sig> d_out;
+    TRY(upload(ctx, d_pos, rec->pos, n)); TRY(upload(ctx, d_mq, rec->mapq, n)); TRY(upload(ctx, d_off, rec->cigar_off, n));
+    TRY(upload(ctx, d_nop, rec->n_cigar_op, n)); TRY(upload(ctx, d_cig, rec->cigar, (size_t)rec->n_cigar));
+    TRY(ensure(ctx, d_out, cap)); TRY(ensure(ctx, d_n, 1)); TRY(zero(ctx, d_n, 1));
+    FSV_LAUNCH(ctx, ctx->stream, k_cigar_sigs, dim3(fsv_grid_for(rec->n_rec, 256)), dim3(256), 0, d_pos.p, d_mq.p, d_off.p, d_nop.p, d_cig.p, (uint32_t)n,
+               min_mapq, min_svlen, d_out.p, cap, d_n.p);
+    uint32_t cnt = 0;
+    TRY(download(ctx, &cnt, d_n, 1));
+    FSV_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    *n_out = cnt;
+    if (cnt > cap) return FSV_ECAP;
+    if (cnt) { TRY(download(ctx, out, d_out, cnt)); FSV_HIP(ctx, hipStreamSynchronize(ctx->stream)); }
+    return FSV_OK;
+}
+} // namespace
+
+extern "C" int fsv_read_signatures(fsv_ctx *ctx, const fsv_bam_records *rec, int min_mapq, int min_svlen, fsv_read_sig *out, uint32_t cap, uint32_t *n_out)
+{
+    BAM_GUARD(FSV_EINVAL, read_signatures_impl(ctx, rec, min_mapq, min_svlen, out, cap, n_out))
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -651,15 +733,15 @@ struct TempFile {
     ~TempFile() { if (f) fclose(f); if (!tmp.empty()) unlink(tmp.c_str()); }
 };
 
-int bam_write_impl(const char *path, const fsv_bam_out *in, int n_threads)
+// the arguments and every record, in the order that decides which error a doubly wrong input gets; ref_span[i]: the reference bases of record i
+int check_records(const char *path, const fsv_bam_out *in, std::vector<int64_t> &ref_span)
 {
     if (!path || !in || (in->n_refs && (!in->ref_name || !in->ref_len))) return FSV_EINVAL;
     const uint64_t n = in->n_rec;
     if (n && (!in->ref_id || !in->pos || !in->flag || !in->mapq || !in->qname_off || !in->qname || !in->cigar_off || !in->n_cigar_op || !in->seq_off)) return FSV_EINVAL;
     if ((in->cs_off == nullptr) != (in->cs == nullptr) || (in->sa_off == nullptr) != (in->sa == nullptr)) return FSV_EINVAL;
     for (uint32_t r = 0; r < in->n_refs; r++) if (!in->ref_name[r] || in->ref_len[r] < 0) return FSV_EINVAL;
-    // checks, reference spans, the order
-    std::vector<int64_t> ref_span(n, 0);
+    ref_span.assign(n, 0);
     for (uint64_t i = 0; i < n; i++) {
         const int32_t rid = in->ref_id[i];
         if (strlen(in->qname + in->qname_off[i]) > 254 || in->seq_off[i + 1] < in->seq_off[i] || in->seq_off[i + 1] - in->seq_off[i] > 0x7fffffffull) return FSV_EINVAL;
@@ -670,19 +752,28 @@ int bam_write_impl(const char *path, const fsv_bam_out *in, int n_threads)
         for (uint32_t k = 0; k < in->n_cigar_op[i]; k++) {
             const uint32_t c = in->cigar[in->cigar_off[i] + k], op = c & 0xf;
             if (op > 8) return FSV_EINVAL;
-            if (op == 0 || op == 2 || op == 3 || op == 7 || op == 8) ref_span[i] += c >> 4;
+            if (cigar_consumes_ref(op)) ref_span[i] += c >> 4;
         }
         if (ref_span[i] == 0) return FSV_EINVAL;
         if ((int64_t)in->pos[i] + ref_span[i] > (1ll << 29)) return FSV_EUNSUP;     // beyond what a .bai can index
     }
-    std::vector<uint64_t> order(n);
+    return FSV_OK;
+}
+
+// the records by (reference, position), equal ones in input order, unmapped ones (-1) last
+std::vector<uint64_t> stable_order(const fsv_bam_out *in)
+{
+    std::vector<uint64_t> order(in->n_rec);
     std::iota(order.begin(), order.end(), 0ull);
     std::stable_sort(order.begin(), order.end(), [&](uint64_t a, uint64_t b) {
         const uint32_t ra = (uint32_t)in->ref_id[a], rb = (uint32_t)in->ref_id[b];     // -1 sorts last
         return ra != rb ? ra < rb : (ra != 0xffffffffu && in->pos[a] < in->pos[b]);
     });
-    // the uncompressed stream: header, then the records; start[i]: where record order[i] begins
-    std::vector<uint8_t> st;
+    return order;
+}
+
+void encode_header(const fsv_bam_out *in, std::vector<uint8_t> &st)
+{
     const char *text = in->header_text ? in->header_text : "";
     st.insert(st.end(), {'B', 'A', 'M', 1});
     put_le<int32_t>(st, (int32_t)strlen(text));
@@ -694,72 +785,82 @@ int bam_write_impl(const char *path, const fsv_bam_out *in, int n_threads)
         st.insert(st.end(), in->ref_name[r], in->ref_name[r] + l);
         put_le<int32_t>(st, in->ref_len[r]);
     }
-    uint8_t nib[256];
-    memset(nib, 15, sizeof(nib));
-    for (int c = 0; c < 16; c++) nib[(uint8_t)"=ACMGRSVTWYHKDBN"[c]] = (uint8_t)c;
-    std::vector<uint64_t> start(n + 1);
-    for (uint64_t k = 0; k < n; k++) {
-        const uint64_t i = order[k];
+}
+
+// record i behind what st holds; FSV_EUNSUP when it is longer than a block_size can say
+int encode_record(const fsv_bam_out *in, uint64_t i, int64_t ref_span, std::vector<uint8_t> &st)
+{
+    const size_t at0 = st.size();
+    const char *name = in->qname + in->qname_off[i];
+    const size_t l_name = strlen(name) + 1;
+    const int32_t l_seq = (int32_t)(in->seq_off[i + 1] - in->seq_off[i]);
+    const int64_t end = (int64_t)in->pos[i] + std::max<int64_t>(1, ref_span);
+    put_le<int32_t>(st, 0);     // block_size, set below
+    put_le<int32_t>(st, in->ref_id[i]); put_le<int32_t>(st, in->pos[i]);
+    st.push_back((uint8_t)l_name); st.push_back(in->mapq[i]);
+    put_le<uint16_t>(st, (uint16_t)reg2bin(in->pos[i], end)); put_le<uint16_t>(st, (uint16_t)in->n_cigar_op[i]); put_le<uint16_t>(st, in->flag[i]);
+    put_le<int32_t>(st, l_seq); put_le<int32_t>(st, -1); put_le<int32_t>(st, -1); put_le<int32_t>(st, 0);
+    st.insert(st.end(), name, name + l_name);
+    if (in->n_cigar_op[i]) { const uint8_t *c = (const uint8_t *)(in->cigar + in->cigar_off[i]); st.insert(st.end(), c, c + (size_t)in->n_cigar_op[i] * 4); }
+    const uint8_t *sq = (const uint8_t *)(in->seq ? in->seq + in->seq_off[i] : nullptr);
+    const size_t at = st.size();
+    st.resize(at + (size_t)(l_seq + 1) / 2, 0);
+    for (int32_t j = 0; j < l_seq; j++) st[at + (size_t)(j >> 1)] |= (uint8_t)(base_tabs.nib[sq[j]] << ((j & 1) ? 0 : 4));
+    st.insert(st.end(), (size_t)l_seq, 0xff);
+    if (in->nm && in->nm[i] != FSV_BAM_NO_TAG) { st.insert(st.end(), {'N', 'M', 'i'}); put_le<int32_t>(st, in->nm[i]); }
+    if (in->cs && in->cs_off[i + 1] > in->cs_off[i]) {
+        st.insert(st.end(), {'c', 's', 'Z'});
+        st.insert(st.end(), in->cs + in->cs_off[i], in->cs + in->cs_off[i + 1]);
+        st.push_back(0);
+    }
+    if (in->sa && in->sa[in->sa_off[i]]) {
+        const char *sa = in->sa + in->sa_off[i];
+        st.insert(st.end(), {'S', 'A', 'Z'});
+        st.insert(st.end(), sa, sa + strlen(sa) + 1);
+    }
+    const uint64_t body = st.size() - at0 - 4;
+    if (body > 0x7fffffffull) return FSV_EUNSUP;
+    const int32_t bs = (int32_t)body;
+    memcpy(st.data() + at0, &bs, 4);
+    return FSV_OK;
+}
+
+// the uncompressed stream: header, then the records; start[k]: where record order[k] begins, start[n]: the end
+int encode_stream(const fsv_bam_out *in, const std::vector<uint64_t> &order, const std::vector<int64_t> &ref_span, std::vector<uint8_t> &st,
+                  std::vector<uint64_t> &start)
+{
+    encode_header(in, st);
+    start.resize(order.size() + 1);
+    for (size_t k = 0; k < order.size(); k++) {
         start[k] = st.size();
-        const char *name = in->qname + in->qname_off[i];
-        const size_t l_name = strlen(name) + 1;
-        const int32_t l_seq = (int32_t)(in->seq_off[i + 1] - in->seq_off[i]);
-        const int64_t end = (int64_t)in->pos[i] + std::max<int64_t>(1, ref_span[i]);
-        put_le<int32_t>(st, 0);     // block_size, set below
-        put_le<int32_t>(st, in->ref_id[i]); put_le<int32_t>(st, in->pos[i]);
-        st.push_back((uint8_t)l_name); st.push_back(in->mapq[i]);
-        put_le<uint16_t>(st, (uint16_t)reg2bin(in->pos[i], end)); put_le<uint16_t>(st, (uint16_t)in->n_cigar_op[i]); put_le<uint16_t>(st, in->flag[i]);
-        put_le<int32_t>(st, l_seq); put_le<int32_t>(st, -1); put_le<int32_t>(st, -1); put_le<int32_t>(st, 0);
-        st.insert(st.end(), name, name + l_name);
-        if (in->n_cigar_op[i]) { const uint8_t *c = (const uint8_t *)(in->cigar + in->cigar_off[i]); st.insert(st.end(), c, c + (size_t)in->n_cigar_op[i] * 4); }
-        const uint8_t *sq = (const uint8_t *)(in->seq ? in->seq + in->seq_off[i] : nullptr);
-        const size_t at = st.size();
-        st.resize(at + (size_t)(l_seq + 1) / 2, 0);
-        for (int32_t j = 0; j < l_seq; j++) st[at + (size_t)(j >> 1)] |= (uint8_t)(nib[sq[j]] << ((j & 1) ? 0 : 4));
-        st.insert(st.end(), (size_t)l_seq, 0xff);
-        if (in->nm && in->nm[i] != FSV_BAM_NO_TAG) { st.insert(st.end(), {'N', 'M', 'i'}); put_le<int32_t>(st, in->nm[i]); }
-        if (in->cs && in->cs_off[i + 1] > in->cs_off[i]) {
-            st.insert(st.end(), {'c', 's', 'Z'});
-            st.insert(st.end(), in->cs + in->cs_off[i], in->cs + in->cs_off[i + 1]);
-            st.push_back(0);
-        }
-        if (in->sa && in->sa[in->sa_off[i]]) {
-            const char *sa = in->sa + in->sa_off[i];
-            st.insert(st.end(), {'S', 'A', 'Z'});
-            st.insert(st.end(), sa, sa + strlen(sa) + 1);
-        }
-        const uint64_t body = st.size() - start[k] - 4;
-        if (body > 0x7fffffffull) return FSV_EUNSUP;
-        const int32_t bs = (int32_t)body;
-        memcpy(st.data() + start[k], &bs, 4);
+        TRY(encode_record(in, order[k], ref_span[order[k]], st));
     }
-    start[n] = st.size();
-    // BGZF: blocks of BGZF_PAYLOAD bytes, deflated side by side, then the end-of-file marker
+    start[order.size()] = st.size();
+    return FSV_OK;
+}
+
+// BGZF: blocks of BGZF_PAYLOAD bytes, deflated side by side, then the end-of-file marker
+bool deflate_blocks(const std::vector<uint8_t> &st, int n_threads, std::vector<std::vector<uint8_t>> &blk)
+{
     const size_t nb = (st.size() + BGZF_PAYLOAD - 1) / BGZF_PAYLOAD;
-    std::vector<std::vector<uint8_t>> blk(nb + 1);
+    blk.resize(nb + 1);
     const unsigned nt = (unsigned)std::min<size_t>((size_t)std::min(16, std::max(1, n_threads)), std::max<size_t>(1, nb / 4));
-    std::atomic<bool> ok{true};
-    auto work = [&](unsigned t) {
-        try { for (size_t b = t; b < nb; b += nt) if (!bgzf_block(st.data() + b * BGZF_PAYLOAD, std::min(BGZF_PAYLOAD, st.size() - b * BGZF_PAYLOAD), blk[b])) ok = false; }
-        catch (...) { ok = false; }
-    };
-    if (nt <= 1) work(0);
-    else {
-        std::vector<std::thread> th;
-        try { for (unsigned t = 1; t < nt; t++) th.emplace_back(work, t); }
-        catch (...) { for (auto &t : th) t.join(); throw; }
-        work(0);
-        for (auto &t : th) t.join();
-    }
-    if (!ok || !bgzf_block(nullptr, 0, blk[nb])) return FSV_EINTERNAL;
-    std::vector<uint64_t> caddr(nb + 2, 0);
-    for (size_t b = 0; b <= nb; b++) caddr[b + 1] = caddr[b] + blk[b].size();
+    const bool ok = fan_out(nb, nt, [&](size_t b) { return bgzf_block(st.data() + b * BGZF_PAYLOAD, std::min(BGZF_PAYLOAD, st.size() - b * BGZF_PAYLOAD), blk[b]); });
+    return ok && bgzf_block(nullptr, 0, blk[nb]);
+}
+
+// the index: per reference the bins' chunks (neighbours in file order joined) and the linear index
+std::vector<uint8_t> build_bai(const fsv_bam_out *in, const std::vector<uint64_t> &order, const std::vector<int64_t> &ref_span,
+                               const std::vector<uint64_t> &start, const std::vector<std::vector<uint8_t>> &blk)
+{
+    std::vector<uint64_t> caddr(blk.size() + 1, 0);
+    for (size_t b = 0; b < blk.size(); b++) caddr[b + 1] = caddr[b] + blk[b].size();
     auto voff = [&](uint64_t u) { return caddr[u / BGZF_PAYLOAD] << 16 | (u % BGZF_PAYLOAD); };
-    // the index: per reference the bins' chunks (neighbours in file order joined) and the linear index
+    const uint64_t n = in->n_rec;
     std::vector<uint8_t> bai;
     bai.insert(bai.end(), {'B', 'A', 'I', 1});
     put_le<int32_t>(bai, (int32_t)in->n_refs);
-    uint64_t k = 0, n_no_coor = 0;
+    uint64_t k = 0;
     for (uint32_t r = 0; r < in->n_refs; r++) {
         std::map<uint32_t, std::vector<std::pair<uint64_t, uint64_t>>> bins;
         std::vector<uint64_t> lin;
@@ -782,12 +883,16 @@ int bam_write_impl(const char *path, const fsv_bam_out *in, int n_threads)
         uint64_t last = 0;
         for (uint64_t v : lin) { if (v != ~0ull) last = v; put_le<uint64_t>(bai, last); }     // an empty window carries the previous offset forward
     }
-    n_no_coor = n - k;
-    put_le<uint64_t>(bai, n_no_coor);
-    // both files whole under temporary names, then renamed
+    put_le<uint64_t>(bai, n - k);     // the records without a coordinate
+    return bai;
+}
+
+// both files whole under temporary names, then renamed
+int write_files(const char *path, const std::vector<std::vector<uint8_t>> &blk, const std::vector<uint8_t> &bai)
+{
     TempFile fb(path), fi(std::string(path) + ".bai");
     bool w = fb.f && fi.f;
-    for (size_t b = 0; w && b <= nb; b++) w = fb.write(blk[b].data(), blk[b].size());
+    for (size_t b = 0; w && b < blk.size(); b++) w = fb.write(blk[b].data(), blk[b].size());
     w = w && fi.write(bai.data(), bai.size());
     w = w && fb.flush() && fi.flush();
     if (!w || !fb.commit()) return FSV_EINTERNAL;
@@ -795,35 +900,19 @@ int bam_write_impl(const char *path, const fsv_bam_out *in, int n_threads)
     return FSV_OK;
 }
 
+int bam_write_impl(const char *path, const fsv_bam_out *in, int n_threads)
+{
+    std::vector<int64_t> ref_span;
+    TRY(check_records(path, in, ref_span));
+    const std::vector<uint64_t> order = stable_order(in);
+    std::vector<uint8_t> st;
+    std::vector<uint64_t> start;
+    TRY(encode_stream(in, order, ref_span, st, start));
+    std::vector<std::vector<uint8_t>> blk;
+    if (!deflate_blocks(st, n_threads, blk)) return FSV_EINTERNAL;
+    return write_files(path, blk, build_bai(in, order, ref_span, start, blk));
+}
+
 } // namespace
 
-extern "C" int fsv_bam_write(const char *path, const fsv_bam_out *in, int n_threads)
-{
-    try { return bam_write_impl(path, in, n_threads); }
-    catch (const std::bad_alloc &) { return FSV_ENOMEM; }
-    catch (...) { return FSV_EINTERNAL; }
-}
-
-// no C++ exception crosses the C ABI (a caller through ctypes would see std::terminate)
-extern "C" int fsv_bam_open(const char *path, fsv_bam **out)
-{
-    try { return fsv_bam_open_impl(path, out); }
-    catch (const std::bad_alloc &) { return FSV_ENOMEM; }
-    catch (...) { return FSV_EINVAL; }
-}
-
-// no C++ exception crosses the C ABI (a caller through ctypes would see std::terminate)
-extern "C" int fsv_bam_fetch(fsv_bam *b, int ref_id, int64_t beg, int64_t end, fsv_bam_records *out, int want_seq)
-{
-    try { return fsv_bam_fetch_impl(b, ref_id, beg, end, out, want_seq); }
-    catch (const std::bad_alloc &) { return FSV_ENOMEM; }
-    catch (...) { return FSV_EINVAL; }
-}
-
-// no C++ exception crosses the C ABI (a caller through ctypes would see std::terminate)
-extern "C" int fsv_read_signatures(fsv_ctx *ctx, const fsv_bam_records *rec, int min_mapq, int min_svlen, fsv_read_sig *out, uint32_t cap, uint32_t *n_out)
-{
-    try { return fsv_read_signatures_impl(ctx, rec, min_mapq, min_svlen, out, cap, n_out); }
-    catch (const std::bad_alloc &) { return FSV_ENOMEM; }
-    catch (...) { return FSV_EINVAL; }
-}
+extern "C" int fsv_bam_write(const char *path, const fsv_bam_out *in, int n_threads) { BAM_GUARD(FSV_EINTERNAL, bam_write_impl(path, in, n_threads)) }

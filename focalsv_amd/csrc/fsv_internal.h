@@ -197,13 +197,14 @@ template <class T> int ensure(fsv_ctx *ctx, Dev<T> &b, size_t n)
     return FSV_OK;
 }
 
-// (an empty vector still leaves a valid pointer behind: kernels are handed b.p whatever the count)
-template <class T> int upload(fsv_ctx *ctx, Dev<T> &b, const std::vector<T> &v)
+// n host elements, or a vector, into the buffer (none still leaves a valid pointer behind: kernels are handed b.p whatever the count)
+template <class T> int upload(fsv_ctx *ctx, Dev<T> &b, const T *host, size_t n)
 {
-    TRY(ensure(ctx, b, v.empty() ? 1 : v.size()));
-    if (!v.empty()) FSV_HIP(ctx, hipMemcpyAsync(b.p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, ctx->stream));
+    TRY(ensure(ctx, b, n ? n : 1));
+    if (n) FSV_HIP(ctx, hipMemcpyAsync(b.p, host, n * sizeof(T), hipMemcpyHostToDevice, ctx->stream));
     return FSV_OK;
 }
+template <class T> int upload(fsv_ctx *ctx, Dev<T> &b, const std::vector<T> &v) { return upload(ctx, b, v.data(), v.size()); }
 
 // the first n elements zeroed / copied to the host, on the context's stream
 template <class T> int zero(fsv_ctx *ctx, Dev<T> &b, size_t n) { FSV_HIP(ctx, hipMemsetAsync(b.p, 0, n * sizeof(T), ctx->stream)); return FSV_OK; }

@@ -28,11 +28,11 @@ def _ref_len(cigar):
 
 
 def encode_aux(tags):
-    """tags: [(two-letter tag, type char, value)] for the types A c C s S i I f Z"""
+    """tags: [(two-letter tag, type char, value)] for the types A c C s S i I f Z H B (H: the hex digits as text; B: (sub-type, values))"""
     out = b""
     for tag, ty, v in tags:
         out += tag.encode() + ty.encode()
-        if ty == "Z":
+        if ty in "ZH":
             out += v.encode() + b"\0"
         elif ty == "A":
             out += v.encode()
@@ -44,21 +44,24 @@ def encode_aux(tags):
     return out
 
 
-def encode_record(ref_id, pos, mapq, flag, qname, cigar, seq, tags=()):
-    """cigar: [(op, len)] with BAM op codes; seq: str ('' allowed)"""
+def encode_record(ref_id, pos, mapq, flag, qname, cigar, seq, tags=(), pad_nibble=0):
+    """cigar: [(op, len)] with BAM op codes; seq: str ('' allowed); tags: as encode_aux takes them, or the aux block's bytes as they
+    are (a damaged one); pad_nibble: what the low half of the last packed byte of an odd-length seq holds (htslib writes 0)"""
     name = qname.encode() + b"\0"
     end = pos + max(1, _ref_len(cigar))
     l_seq = len(seq)
     packed = bytearray((l_seq + 1) // 2)
     for i, c in enumerate(seq):
         packed[i >> 1] |= _NIB.get(c, 15) << (4 if i % 2 == 0 else 0)
+    if l_seq % 2:
+        packed[-1] |= pad_nibble
     body = struct.pack("<iiBBHHHiiii", ref_id, pos, len(name), mapq, reg2bin(pos, end), len(cigar), flag, l_seq, -1, -1, 0) + name + \
-        b"".join(struct.pack("<I", n << 4 | op) for op, n in cigar) + bytes(packed) + b"\xff" * l_seq + encode_aux(tags)
+        b"".join(struct.pack("<I", n << 4 | op) for op, n in cigar) + bytes(packed) + b"\xff" * l_seq + (tags if isinstance(tags, bytes) else encode_aux(tags))
     return struct.pack("<i", len(body)) + body
 
 
 def write_bam(path, refs, records, block=0xff00, index=True, header_text="@HD\tVN:1.6\tSO:coordinate\n"):
-    """refs: [(name, length)]; records: dicts with ref (index), pos, mapq, flag, qname, cigar, seq"""
+    """refs: [(name, length)]; records: dicts with ref (index), pos, mapq, flag, qname, cigar, seq, tags, pad_nibble (encode_record)"""
     text = header_text.encode()
     head = b"BAM\1" + struct.pack("<i", len(text)) + text + struct.pack("<i", len(refs))
     for name, ln in refs:
@@ -67,7 +70,7 @@ def write_bam(path, refs, records, block=0xff00, index=True, header_text="@HD\tV
     stream = bytearray(head)
     spans = []   # per record: (uncompressed start, uncompressed end)
     for r in records:
-        e = encode_record(r["ref"], r["pos"], r.get("mapq", 60), r.get("flag", 0), r["qname"], r["cigar"], r.get("seq", ""), r.get("tags", ()))
+        e = encode_record(r["ref"], r["pos"], r.get("mapq", 60), r.get("flag", 0), r["qname"], r["cigar"], r.get("seq", ""), r.get("tags", ()), r.get("pad_nibble", 0))
         spans.append((len(stream), len(stream) + len(e)))
         stream += e
     caddr, out = [], bytearray()

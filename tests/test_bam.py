@@ -537,3 +537,192 @@ def test_reader_on_the_second_htslib_bam(golden_dir):
         assert q == int(r.l_seq[i]) == len(r.seq_text(i)) and set(r.seq_text(i)) <= set("ACGTN")
         assert int(r.ref_end[i]) == int(r.pos[i]) + sum(n for op, n in seg.cigar if op in (0, 2, 3, 7, 8))
         assert r.sa_tag(i).count(";") >= 1
+
+
+# ---- the first record's offset, the aux walk, the base decoders at the word edges ---------------------------------------------------
+_REFS3 = [("chr1", 200000), ("chr2", 150000), ("chrX", 90000)]
+_LONG_HEADER = "@HD\tVN:1.6\tSO:coordinate\n" + "".join("@CO\tline %d of a header that does not fit one small block\n" % i for i in range(30))
+
+
+def _header_bytes(refs, text):
+    return 12 + len(text.encode()) + sum(8 + len(nm) + 1 for nm, _ in refs)
+
+
+def _assert_fetch(got, exp):
+    assert got.names == [r["qname"] for r in exp]
+    assert got.pos.tolist() == [r["pos"] for r in exp] and got.flag.tolist() == [r["flag"] for r in exp]
+    assert got.ref_id.tolist() == [r["ref"] for r in exp]
+    for k, r in enumerate(exp):
+        assert got.segment(k).cigar == r["cigar"] and got.seq_text(k) == r["seq"]
+
+
+@pytest.mark.parametrize("block", [700, "header"])
+def test_scan_without_index_starts_at_the_first_record(tmp_path, block):
+    """a header longer than one BGZF block: the first record lies in a later block, at a non-zero offset inside it (block 700) or
+    right at its start (a block as long as the header); four fetches on one handle, each from the first record again"""
+    recs = make_records(13, n=30)
+    first = _header_bytes(_REFS3, _LONG_HEADER)
+    bl = first if block == "header" else block
+    assert first // 700 >= 1 and first % 700 != 0 and first // bl >= 1 and (first % bl != 0) == (block == 700)
+    path = W.write_bam(str(tmp_path / "h.bam"), _REFS3, recs, block=bl, index=False, header_text=_LONG_HEADER)
+    with B.BamFile(path) as bam:
+        assert not bam.has_index and bam.references == [nm for nm, _ in _REFS3]
+        a = bam.fetch(until_eof=True, want_seq=2)
+        _assert_fetch(a, recs)
+        _assert_fetch(bam.fetch("chrX", want_seq=2), expect(recs, 2))
+        _assert_fetch(bam.fetch("chr1", 50000, 90000, want_seq=2), expect(recs, 0, 50000, 90000))
+        z = bam.fetch(until_eof=True, want_seq=2)
+        _assert_fetch(z, recs)
+        assert len(a) == 90 and 0 < len(expect(recs, 0, 50000, 90000)) < 30
+        for f in ("pos", "ref_end", "flag", "mapq", "cigar_off", "n_cigar_op", "qname_off", "l_seq", "ref_id", "ps", "hp", "seq_ascii_off"):
+            assert getattr(a, f).tolist() == getattr(z, f).tolist(), f
+        assert a.cigar.tobytes() == z.cigar.tobytes() and a.qname_buf.tobytes() == z.qname_buf.tobytes() and a.seq_ascii.tobytes() == z.seq_ascii.tobytes()
+
+
+@pytest.mark.parametrize("header", ["short", "long", "block"])
+def test_header_only_file_has_no_records_and_no_error(tmp_path, header):
+    """no record behind the header: it ends inside the only block, inside a later one, or exactly with its block"""
+    text = _LONG_HEADER if header != "short" else "@HD\tVN:1.6\tSO:coordinate\n"
+    bl = _header_bytes(_REFS3, text) if header == "block" else 700
+    path = W.write_bam(str(tmp_path / "e.bam"), _REFS3, [], block=bl, index=False, header_text=text)
+    with B.BamFile(path) as bam:
+        assert bam.references == [nm for nm, _ in _REFS3]
+        for _ in range(2):
+            assert len(bam.fetch(until_eof=True, want_seq=7)) == 0
+            assert len(bam.fetch("chrX", want_seq=7)) == 0
+            assert len(bam.fetch("chr1", 50000, 90000, want_seq=7)) == 0
+
+
+_INT_TAGS = {"c": (-100, -2), "C": (200, 2), "s": (-30000, -1), "S": (60000, 1), "i": (-(1 << 31) + 5, 2), "I": ((1 << 31) - 1, 1)}    # type: (PS, HP)
+_SA = "chr2,7,+,100M,60,0;"
+
+
+def _front_tags():
+    """one tag of every type that is not an integer: A, f, Z, H, and a B array of each sub-type with no and with three elements"""
+    t = [("xa", "A", "q"), ("xf", "f", 2.5), ("xz", "Z", "PS HP SA"), ("xh", "H", "1AE301")]
+    for k, st in enumerate("cCsSiIf"):
+        t += [("a%d" % k, "B", (st, [])), ("b%d" % k, "B", (st, [1, 2, 3]))]
+    return t
+
+
+def _aux_records(tail_of):
+    return [{"ref": 0, "pos": 100 + k, "mapq": 60, "flag": 0, "qname": "aux_%s" % ty, "cigar": [(0, 10)], "seq": "ACGTACGTAC", "tags": tail_of(ty)}
+            for k, ty in enumerate(_INT_TAGS)]
+
+
+def _fetch_tags(tmp_path, name, recs):
+    path = W.write_bam(str(tmp_path / name), [("chr1", 200000)], recs, index=False)
+    with B.BamFile(path) as bam:
+        got = bam.fetch("chr1", want_seq=6)
+    assert got.names == [r["qname"] for r in recs] and all(got.seq_text(k) == "ACGTACGTAC" for k in range(len(recs)))
+    return [(got.tag(k, "PS"), got.tag(k, "HP"), got.sa_tag(k)) for k in range(len(recs))]
+
+
+def test_aux_walk_over_every_tag_type(tmp_path):
+    """PS / HP of every integer type behind one tag of every other type, SA:Z last: the values as written"""
+    got = _fetch_tags(tmp_path, "a.bam", _aux_records(lambda ty: _front_tags() + [("PS", ty, _INT_TAGS[ty][0]), ("HP", ty, _INT_TAGS[ty][1]), ("SA", "Z", _SA)]))
+    assert got == [(ps, hp, _SA) for ps, hp in _INT_TAGS.values()]
+
+
+def test_aux_walk_malformed_tags(tmp_path):
+    """a PS stored as Z and an HP stored as f are 'no tag' and the walk goes on behind them; an aux block that ends inside a B array
+    (inside its elements, or inside its count) has no tag from there on; the record itself comes back in every case"""
+    ps_z = _fetch_tags(tmp_path, "z.bam", _aux_records(lambda ty: _front_tags() + [("PS", "Z", "77"), ("HP", ty, _INT_TAGS[ty][1]), ("SA", "Z", _SA)]))
+    assert ps_z == [(None, hp, _SA) for _, hp in _INT_TAGS.values()]
+    hp_f = _fetch_tags(tmp_path, "f.bam", _aux_records(lambda ty: _front_tags() + [("PS", ty, _INT_TAGS[ty][0]), ("HP", "f", 1.0), ("SA", "Z", _SA)]))
+    assert hp_f == [(ps, None, _SA) for ps, _ in _INT_TAGS.values()]
+    for cut in (6, 14):       # the last B array (f, three elements) is 3 + 1 + 4 + 12 bytes: 6 cuts its elements, 14 its count
+        tail = lambda ty: W.encode_aux(_front_tags())[:-cut]
+        assert _fetch_tags(tmp_path, "c%d.bam" % cut, _aux_records(tail)) == [(None, None, "")] * len(_INT_TAGS)
+    # the tags in front of the cut array, and a value that overruns the block: PS whole in front of the damage, HP cut inside its value
+    front = W.encode_aux([("PS", "i", 77)] + _front_tags())
+    assert _fetch_tags(tmp_path, "p.bam", _aux_records(lambda ty: front[:-6])) == [(77, None, "")] * len(_INT_TAGS)
+    assert _fetch_tags(tmp_path, "o.bam", _aux_records(lambda ty: W.encode_aux([("PS", "C", 7), ("HP", "i", 1)])[:-2])) == [(7, None, "")] * len(_INT_TAGS)
+
+
+def test_base_decoders_at_the_word_edges(tmp_path):
+    """read lengths around the 16-base words of the 2-bit store, every 4-bit code among the bases, and an odd-length read's padding
+    nibble set: the text is the input, the words are fsv_pack_reads of it (letters other than ACGT as A), nothing above the last base"""
+    import numpy as np
+    from focalsv_amd import _lib
+    alphabet = "=ACMGRSVTWYHKDBN"
+    lens = [0, 1, 2, 15, 16, 17, 31, 32, 33]
+    seqs = [(alphabet * 4)[3 * k: 3 * k + n] for k, n in enumerate(lens)]
+    assert set("".join(seqs)) == set(alphabet) and all(set(s) == set(alphabet) for s in seqs if len(s) >= 16)
+    recs = [{"ref": 0, "pos": 10 * k, "mapq": 60, "flag": 0, "qname": "len_%d" % len(s), "cigar": [(0, max(1, len(s)))], "seq": s, "pad_nibble": 8}
+            for k, s in enumerate(seqs)]
+    path = W.write_bam(str(tmp_path / "b.bam"), [("chr1", 200000)], recs, index=False)
+    with B.BamFile(path) as bam:
+        got = bam.fetch(until_eof=True, want_seq=3)
+    words, word_off, _ = _lib.pack_reads(seqs)
+    assert got.l_seq.tolist() == lens
+    for k, s in enumerate(seqs):
+        nw = (len(s) + 15) // 16
+        w = got.seq_words[int(got.seq_word_off[k]): int(got.seq_word_off[k]) + nw]
+        assert got.seq_text(k) == s
+        assert np.array_equal(w, words[int(word_off[k]): int(word_off[k]) + nw]), s
+        assert got.sequence(k) == "".join(c if c in "ACGT" else "A" for c in s)
+        if len(s) % 16:
+            assert int(w[-1]) >> (2 * (len(s) % 16)) == 0
+    assert len(got.seq_words) == sum((n + 15) // 16 for n in lens)
+
+
+def _sig_records(n):
+    """n records, each with a deletion and an insertion of the threshold length (30) and one of each a base below it"""
+    recs = []
+    for k in range(n):
+        m = 20 + k % 7
+        recs.append({"ref": 0, "pos": 100 + 3 * k, "mapq": 60, "flag": 16 * (k % 2), "qname": "s%d" % k,
+                     "cigar": [(0, m), (2, 30), (0, 11), (1, 30), (0, m), (2, 29), (0, 9), (1, 29), (0, 5)], "seq": ""})
+    return recs
+
+
+def _expected_sigs(got, min_mapq=50, min_svlen=30):
+    from focalsv_amd.dippav import reads_signature as RS
+    ed, ei = [], []
+    for r in range(len(got)):
+        s = got.segment(r)
+        if s.mapq >= min_mapq and s.cigar:
+            d, i = RS.extract_sig_from_cigar(s, min_svlen)
+            ed += d
+            ei += i
+    return sorted(ed), sorted(ei)
+
+
+@pytest.mark.gpu
+def test_gpu_cigar_signatures_block_edges_edge_records_and_caps(tmp_path):
+    """fsv_read_signatures around its 256-thread block (buffers grow and shrink between calls on one context), on the records the
+    kernel treats apart, and with a caller buffer of exactly, and one below, the number of signatures"""
+    import ctypes as C
+    import numpy as np
+    from focalsv_amd import _lib
+    edge = [{"ref": 1, "pos": 500, "mapq": 60, "flag": 0, "qname": "hard_soft", "cigar": [(5, 10), (4, 5), (0, 100), (2, 30), (0, 50), (1, 30), (0, 20)], "seq": ""},
+            {"ref": 1, "pos": 600, "mapq": 60, "flag": 0, "qname": "only_m", "cigar": [(0, 200)], "seq": ""},
+            {"ref": 1, "pos": 700, "mapq": 60, "flag": 0, "qname": "no_ops", "cigar": [], "seq": ""},
+            {"ref": 1, "pos": 800, "mapq": 49, "flag": 0, "qname": "mapq_49", "cigar": [(0, 100), (2, 40), (0, 50), (1, 40), (0, 20)], "seq": ""}]
+    path = W.write_bam(str(tmp_path / "s.bam"), [("chr1", 200000), ("chr2", 200000)], _sig_records(513) + edge)
+    with B.BamFile(path) as bam:
+        many, few = bam.fetch("chr1"), bam.fetch("chr2")
+    assert len(many) == 513 and few.names == [r["qname"] for r in edge]
+    with _lib.Context(0) as ctx:
+        for n in (1, 255, 256, 257, 513, 1):
+            sub = many.subset(range(n))
+            dels, inss = B.cigar_signatures(ctx, sub, 50, 30)
+            ed, ei = _expected_sigs(sub)
+            assert (sorted(dels), sorted(inss)) == (ed, ei) and len(ed) == len(ei) == n, n
+        dels, inss = B.cigar_signatures(ctx, few, 50, 30)
+        assert (sorted(dels), sorted(inss)) == _expected_sigs(few)
+        assert [(d[4], d[2], d[5]) for d in dels] == [("hard_soft", 600, 115)] and [(i[4], i[2], i[5]) for i in inss] == [("hard_soft", 680, 165)]
+
+        def raw(recs, cap):
+            out, n = np.zeros(max(1, cap), _lib.READ_SIG_DTYPE), C.c_uint32(12345)
+            st = recs.struct(False)
+            rc = ctx._lib.fsv_read_signatures(ctx._h, C.byref(st), 50, 30, out.ctypes.data, cap, C.byref(n))
+            return rc, n.value, out[:min(n.value, cap)]
+        sub = many.subset(range(257))
+        need = 2 * 257
+        rc, n, sig = raw(sub, need)
+        assert (rc, n) == (0, need)
+        assert sorted((int(s["rec"]), int(s["type"])) for s in sig) == [(r, t) for r in range(257) for t in (0, 1)] and (sig["len"] == 30).all()
+        assert raw(sub, need - 1)[:2] == (_lib.ECAP, need)
+        assert raw(many.subset([]), 16)[:2] == (0, 0)
